@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- Msamples/s of the path-tracing hot path on MI355X (BASELINE.json's metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the JSON line ("roofline": null).  --full adds what the
+headline figure does not need: the counting launch and the isolated-kernel steps behind "roofline", and the CPU oracle's
+"cpu_baseline".  --dump-outputs DIR writes the image of the last timed step as DIR/image.npy (float32 [rows, W, 4],
+row 0 = bottom); inputs are fixed, so two builds can be compared output for output.
 
 A "step" is one full progressive render of the frame: reset the accumulation buffer, trace every sample
 of the workload (W x H x spp paths: ray generation, BVH traversal, shading, accumulate, resolve) and,
@@ -35,6 +40,7 @@ os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md "Chip-level parameters")
 STRIPE_ROWS = 8
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs: all files together
 
 # name: (scene key in tests/scenes.py, W, H, spp, depth)   -- BASELINE.json "configs"
 WORKLOADS = {
@@ -56,17 +62,41 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--warmup", type=int, default=6)
     ap.add_argument("--workload", default="cornell_box_1080p_8spp_d8", choices=sorted(WORKLOADS))
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU work for the cpu_baseline leg (0 = skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target CPU work for the cpu_baseline leg of --full (0 = skip)")
     ap.add_argument("--frames-in-flight", type=int, default=0,
                     help="independent frames (steps) kept in flight, each on its own renderer + HIP stream: the drain of one "
                          "frame overlaps the ramp-up of the next (1 = strictly one after the other).  Default 4; 2 for the "
                          "workload whose step is a second long (room 4K / 64 spp: 800 ms with 2 in flight, 896 with 3)")
     ap.add_argument("--emulate-shard", default="", help="R/W: render only rank R's stripes of a W-way split on ONE GPU, no gather "
                     "(what one GPU of a W-GPU run computes; for tuning small-shard behaviour on a 1-GPU box)")
-    ap.add_argument("--no-roofline-counters", action="store_true", help="skip the counting launch (roofline = null)")
+    ap.add_argument("--no-roofline-counters", action="store_true", help="--full: skip the counting launch (no algorithmic terms in roofline)")
     ap.add_argument("--group", action="store_true", help="ONE process drives all --gpus devices through the C ABI's drt_group_* (stripes "
                     "per device, gathered into device 0's image with RCCL send / recv inside the library) instead of one rank per GPU")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: roofline (counting launch "
+                    "+ isolated-kernel steps) and cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write the image of the last timed step as DIR/image.npy "
+                    "(float32; a fixed, seeded sample of its pixels plus DIR/image_index.npy when above %d MB)" % (DUMP_LIMIT_BYTES >> 20))
     return ap.parse_args()
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: DIR/<name>.npy per array, float32 (float64 kept), at most DUMP_LIMIT_BYTES in all.  An array that does not
+    fit is replaced by a fixed sample of its pixels (rows of the array flattened to [pixels, channels], seed 0, in pixel order)
+    and DIR/<name>_index.npy holds their flat pixel indices (float64, exact)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES - 4096 * len(arrays)            # (room for the .npy headers)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > budget:
+            flat = a.reshape(-1, a.shape[-1])
+            n = budget // (flat.shape[1] * a.itemsize + 8)
+            index = np.sort(np.random.default_rng(0).permutation(flat.shape[0])[:n])
+            np.save(os.path.join(out_dir, name + "_index.npy"), index.astype(np.float64))
+            a = flat[index]
+            budget -= index.size * 8
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        budget -= a.nbytes
 
 
 def usable_cores():
@@ -196,6 +226,8 @@ def main_group(args):
         step(i)
     drain()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"image": groups[(args.steps - 1) % len(groups)].GetRenderTargetImage()})
     out = {"metric": "Msamples/sec at 1920x1080, 8spp, cornell_box" if args.workload == "cornell_box_1080p_8spp_d8" else "Msamples/sec",
            "value": round(W * H * spp * args.steps / elapsed / 1e6, 3), "unit": "Msamples/s", "n_gpus": args.gpus, "steps": args.steps,
            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "strong",
@@ -335,10 +367,10 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    # exact algorithmic work of one launch on this rank (counting variant of the same kernel, untimed)
+    # exact algorithmic work of one launch on this rank (counting variant of the same kernel, untimed; --full)
     alg_bytes = None
     counters = None
-    if not args.no_roofline_counters:
+    if args.full and not args.no_roofline_counters:
         r.setCounting(True)
         r.resetAccumulationBuffer()
         r.RenderBatch(cam, scene, spp)
@@ -359,16 +391,21 @@ def main():
     drain()
     sync()
     elapsed = time.perf_counter() - t0
-    image = slots[(args.steps - 1) % len(slots)].image
+    last = slots[(args.steps - 1) % len(slots)]
+    image = last.image
     if dist_on:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path holds after the last step: the assembled frame on rank 0, else this renderer's rows
+        out_img = image if image is not None else last.rgba[:last.r.getLocalRows()]
+        dump_outputs(args.dump_outputs, {"image": out_img.cpu().numpy()})
 
     # The tracing kernel ALONE: with several frames in flight the launches share the GPU and neither a stream-event interval
-    # nor an execution span of one launch is a kernel time.  A few more steps, one launch at a time, blocking, untimed.
+    # nor an execution span of one launch is a kernel time.  A few more steps, one launch at a time, blocking, untimed (--full).
     iso_span, iso_events, iso_launches = [], [], 0
-    if True:                                   # (every rank: the ranks stay in step; their launches are their shards)
+    if args.full:                              # (every rank: the ranks stay in step; their launches are their shards)
         iso = slots[0].r
         iso.setFramesInFlight(1)
         for _ in range(max(1, min(args.steps, 10 if spp * W * H < 10 ** 8 else 2))):
@@ -452,7 +489,7 @@ def main():
         if args.workload == "mc_transparency_843x460_50spp_d5":
             out["config"]["reference_screenshot"] = {"value": 53.6, "unit": "Msamples/s", "hardware": "GTX 1650 (presumed)",
                                                      "source": "DustRayTracer/beforeBVHbuildrefactor_col.png", "ratio": round(value / 53.6, 1)}
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             out["cpu_baseline"] = cpu_baseline(scene_key, W, H, depth, args.cpu_seconds)
         print(json.dumps(out), flush=True)
     if dist_on:

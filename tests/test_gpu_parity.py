@@ -552,13 +552,13 @@ def test_randomised_cases_match_oracle():
 
 
 def test_bench_line_has_the_contracted_shape():
-    """bench.py prints ONE JSON line with the keys the driver reads, the roofline and cpu_baseline objects included."""
+    """bench.py --full prints ONE JSON line with the keys the driver reads, the roofline and cpu_baseline objects included."""
     import json
     import os
     import subprocess
     import sys
     from tests.scenes import ROOT
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--cpu-seconds", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "6", "--warmup", "2", "--cpu-seconds", "1"],
                        capture_output=True, text=True, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -585,6 +585,37 @@ def test_bench_line_has_the_contracted_shape():
     assert abs(hbm["frac"] - hbm["achieved"] / hbm["peak"]) < 1e-3
     cpu = d["cpu_baseline"]
     assert cpu["kind"] == "port" and cpu["unit"] == "Msamples/s" and cpu["value"] > 0 and cpu["cores"] >= 1 and "samples" in cpu["sample"]
+
+
+def test_plain_bench_line_and_dumped_outputs(tmp_path):
+    """A plain bench.py run times exactly --steps steps and measures nothing else (roofline null, no cpu_baseline); with
+    --dump-outputs it writes the last step's image, which is the image a renderer on its own makes of the same workload."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from tests.scenes import ROOT
+    out_dir = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "1",
+                        "--dump-outputs", str(out_dir)], capture_output=True, text=True, cwd=ROOT, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert (d["steps"], d["warmup"], d["roofline"], d["unit"], d["dtype"], d["higher_is_better"]) == (5, 1, None, "Msamples/s", "f32", True)
+    assert "cpu_baseline" not in d and d["ms_per_step"] > 0
+    assert abs(d["value"] - 1920 * 1080 * 8 / (d["ms_per_step"] * 1e-3) / 1e6) < 0.01 * d["value"]
+    assert sorted(os.listdir(out_dir)) == ["image.npy"]
+    got = np.load(out_dir / "image.npy")
+    assert got.dtype == np.float32 and got.shape == (1080, 1920, 4)
+    name, W, H, spp, depth = "cornell_box", 1920, 1080, 8, 8               # bench.py's default workload
+    sc, _ = make_pair(name)
+    cam, _ = cameras(name)
+    rr = drt.Renderer(0)
+    rr.m_RendererSettings = drt.RendererSettings(ray_bounce_limit=depth, max_samples=spp + 1)
+    rr.ResizeBuffer(W, H)
+    rr.RenderBatch(cam, sc, spp)
+    assert np.array_equal(bits(got), bits(rr.GetRenderTargetImage()))
 
 
 def test_bench_two_rank_rehearsal_assembles_the_single_device_image():

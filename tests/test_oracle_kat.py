@@ -145,16 +145,42 @@ def test_texture_fetch_matches_reference(kat_golden):
     assert (g["texalpha3"] == 1).all()                      # <4 channels: opaque (Texture.cu:62-63)
 
 
+def _kat3():
+    """tests/golden/kat_ref3.json and the inputs its generator (tests/golden/make_kat_golden3.py) ran the reference binary on."""
+    import importlib.util
+    import json
+    import os
+    from tests.scenes import ROOT
+    gen = os.path.join(ROOT, "tests", "golden", "make_kat_golden3.py")
+    spec = importlib.util.spec_from_file_location("make_kat_golden3", gen)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    with open(os.path.join(ROOT, "tests", "golden", "kat_ref3.json")) as f:
+        return mod, mod.inputs(), json.load(f)
+
+
+def _equals_stored(mod, got, want, what):
+    """Bit for bit: every byte through its SHA-256; on a mismatch, the first stored values say where."""
+    s = mod.summary(got)
+    assert (s["dtype"], s["shape"]) == (want["dtype"], want["shape"]), what
+    assert s["head_bits"] == want["head_bits"], "%s: first difference at element %d" % (
+        what, next(i for i, (a, b) in enumerate(zip(s["head_bits"], want["head_bits"])) if a != b))
+    assert s["sha256"] == want["sha256"], "%s: differs beyond the first %d elements" % (what, len(want["head_bits"]))
+
+
 def test_live_reference_binary_when_present(kat_golden):
-    """In the build container oracle/_ref/ref_kat exists: re-run it on fresh random seeds."""
+    """50 000 seeds through the reference's randomInUnitSphere: its outputs are pinned in tests/golden/kat_ref3.json
+    (tests/golden/make_kat_golden3.py); where oracle/_ref/ref_kat is built, the binary itself is re-run on the same seeds."""
     from oracle import ref_kat as rk
-    if not rk.available():
-        pytest.skip("oracle/_ref/ref_kat not built here (needs /root/reference)")
-    rng = np.random.default_rng(7)
-    seeds = rng.integers(0, 2 ** 32, 50000, dtype=np.uint64).astype(np.uint32)
+    mod, x, g = _kat3()
+    seeds = x["sphere_seeds"]
+    assert len(np.unique(seeds)) > 49000                          # the hash spreads them
     v, s, _ = oracle.kat_unitsphere(seeds)
-    rv, rs = rk.unitsphere(seeds)
-    assert np.array_equal(bits(v), bits(rv)) and np.array_equal(s, rs)
+    _equals_stored(mod, np.asarray(v, "<f4"), g["sphere_v"], "unit-sphere vectors")
+    _equals_stored(mod, np.asarray(s, "<u4"), g["sphere_seed_end"], "seeds after the draw")
+    if rk.available():
+        rv, rs = rk.unitsphere(seeds)
+        assert np.array_equal(bits(v), bits(rv)) and np.array_equal(s, rs)
 
 
 def test_sphere_accept_shortcut():
@@ -213,12 +239,14 @@ def test_remaining_reference_leaf_functions(kat_golden):
     assert np.array_equal(bits(col), bits(g["miss_out_color"])) and np.array_equal(bits(t), bits(g["miss_t"]))
     assert np.array_equal(has_prim, g["miss_has_prim"]) and np.array_equal(front, g["miss_front"]) and not has_prim.any() and (t == -1).all()
     assert np.array_equal(bits(oracle.kat_bounds_centroid(g["boxes"])), bits(g["boundscentroid"]))
+    # random intervals and huge boxes: the reference's outputs pinned in kat_ref3.json (tests/golden/make_kat_golden3.py)
+    mod, x, g3 = _kat3()
+    iv, boxes = x["iv"], x["boxes"]
+    _equals_stored(mod, np.asarray(oracle.kat_surrounds(iv), "<i4"), g3["surrounds"], "Interval::surrounds")
+    _equals_stored(mod, np.asarray(oracle.kat_bounds_centroid(boxes), "<f4"), g3["boundscentroid"], "Bounds3f::getCentroid")
     from oracle import ref_kat as rk
-    if rk.available():                                       # build container: the reference binary itself, fresh inputs
-        rng = np.random.default_rng(11)
-        iv = rng.normal(size=(5000, 3)).astype(np.float32)
+    if rk.available():                                       # build container: the reference binary itself, same inputs
         assert np.array_equal(oracle.kat_surrounds(iv), rk.surrounds(iv))
-        boxes = rng.normal(size=(5000, 6)).astype(np.float32) * np.float32(1e30)
         assert np.array_equal(bits(oracle.kat_bounds_centroid(boxes)), bits(rk.boundscentroid(boxes)))
 
 

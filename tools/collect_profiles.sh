@@ -1,6 +1,6 @@
 # GPU box: everything profiles/ is built from.  Output under gpurun_out/prof/ (tools/install_profiles.py copies what is kept).
 #   bash tools/collect_profiles.sh [round-tag] [counters|bench|all] [workload ...]
-# counters: per workload, one `bench.py --frames-in-flight 1` run each under rocprofv3 --kernel-trace --stats and under six --pmc
+# counters: per workload, one `bench.py --full --frames-in-flight 1` run each under rocprofv3 --kernel-trace --stats and under six --pmc
 #           passes (SQ instruction mix; SQ wave time; L2 requests / hits; vector-memory + LDS instructions; FETCH_SIZE; WRITE_SIZE --
 #           separate passes, MI355X_MICROARCH.md "HBM"), then tools/roofline_from_profiles.py -> <tag>_roofline_<workload>.json
 # bench:    the bench lines of every workload (they read the roofline JSONs written above), emulated shards, pool statistics
@@ -18,7 +18,7 @@ if [ "$WHAT" != "bench" ]; then
 for wl in $WLS; do
   steps=6; warm=1; [ $wl = room_4k_64spp_d16 ] && steps=2
   [ $wl = cornell_box_256_1spp_d4 ] && steps=40
-  B="python3 $R/bench.py --workload $wl --frames-in-flight 1 --cpu-seconds 0 --steps $steps --warmup $warm --no-roofline-counters"
+  B="python3 $R/bench.py --full --workload $wl --frames-in-flight 1 --cpu-seconds 0 --steps $steps --warmup $warm --no-roofline-counters"
   rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_kt_$wl -o kt -- $B > $O/${TAG}_bench_f1_under_rocprof_$wl.json 2> /tmp/p_kt.log
   cp /tmp/p_kt_$wl/kt_kernel_stats.csv $O/${TAG}_bench_f1_kernel_stats_$wl.csv
   rocprofv3 --pmc $SQ1 --output-format csv -d /tmp/p_sq1_$wl -o sq -- $B > /dev/null 2> /tmp/p_sq1.log
@@ -40,13 +40,13 @@ if [ "$WHAT" != "counters" ]; then
 # the bench lines (they read the roofline JSONs written above: install them first for this run)
 cp $O/${TAG}_roofline_*.json $R/profiles/ 2>/dev/null || true
 cd $R
-python3 bench.py > $O/${TAG}_bench_default.json
-(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_f3 -o f3 -- python3 $R/bench.py --cpu-seconds 0 > $O/${TAG}_bench_default_under_rocprof.json 2> /tmp/p_f3.log; cp /tmp/p_f3/f3_kernel_stats.csv $O/${TAG}_bench_default_kernel_stats.csv)
-python3 bench.py --workload room_4k_64spp_d16 --cpu-seconds 10 --steps 4 --warmup 1 > $O/${TAG}_bench_room_4k_64spp_d16.json
+python3 bench.py --full > $O/${TAG}_bench_default.json
+(cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_f3 -o f3 -- python3 $R/bench.py --full --cpu-seconds 0 > $O/${TAG}_bench_default_under_rocprof.json 2> /tmp/p_f3.log; cp /tmp/p_f3/f3_kernel_stats.csv $O/${TAG}_bench_default_kernel_stats.csv)
+python3 bench.py --full --workload room_4k_64spp_d16 --cpu-seconds 10 --steps 4 --warmup 1 > $O/${TAG}_bench_room_4k_64spp_d16.json
 for wl in suzanne_plane_1080p_8spp_d2 dense_monkey_1080p_16spp_d2 cs16_dust_1080p_8spp_d5 cornell_box_256_1spp_d4 mc_transparency_843x460_50spp_d5; do
-  python3 bench.py --workload $wl --cpu-seconds 3 > $O/${TAG}_bench_$wl.json
+  python3 bench.py --full --workload $wl --cpu-seconds 3 > $O/${TAG}_bench_$wl.json
 done
-for s in 0/2 0/4 0/8; do python3 bench.py --emulate-shard $s --cpu-seconds 0 --steps 200 --warmup 20 > $O/${TAG}_bench_shard_${s/\//of}.json; done
+for s in 0/2 0/4 0/8; do python3 bench.py --full --emulate-shard $s --cpu-seconds 0 --steps 200 --warmup 20 > $O/${TAG}_bench_shard_${s/\//of}.json; done
 python3 tools/pool_stats.py cornell_box 1920 1080 8 8 > $O/${TAG}_pool_stats_cornell.txt 2>&1
 python3 tools/pool_stats.py room 1920 1080 4 16 > $O/${TAG}_pool_stats_room.txt 2>&1
 python3 tools/small_launches.py > $O/${TAG}_small_launches.txt 2>&1
