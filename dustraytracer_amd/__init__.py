@@ -13,6 +13,7 @@ There is no CPU fallback: importing works anywhere the shared library loads, but
 without a GPU raises DrtError.  A missing shared library raises ImportError (build it with
 `python -c "import __graft_entry__ as g; g.build()"` or `make -C dustraytracer_amd/csrc`).
 """
+import collections
 import ctypes as C
 import os
 
@@ -258,6 +259,8 @@ _sig("drt_debug_wave_queue_plans", C.c_int, _P, C.c_char_p, C.c_size_t)
 _sig("drt_debug_pool_stats", C.c_int, _P, _P, C.c_int32)
 _sig("drt_debug_check_rcp", C.c_int, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
 _sig("drt_debug_check_sqrt", C.c_int, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
+_sig("drt_renderer_trace_rays", C.c_int, _P, _P, _P, _P, C.c_uint32, _P)
+_sig("drt_renderer_occluded", C.c_int, _P, _P, _P, _P, C.c_uint32, _P)
 
 EXPORTED_SYMBOLS = [n for n in dir(_lib) if n.startswith("drt_")]
 
@@ -466,6 +469,74 @@ class RendererGroup:
         return buf.value.decode()
 
 
+FLT_MAX = float(np.finfo(np.float32).max)
+RayHits = collections.namedtuple("RayHits", "t prim u v")     # closest-hit query results (Renderer.traceRays)
+
+
+def _ray_batch(torch, dev, origins, directions, tmin, tmax):
+    """(rays [N, 8] float32 on `dev`, came_from_numpy).  Raises DrtError(ERR_INVALID) on a wrong dtype, shape or device."""
+    def bad(msg):
+        return DrtError(ERR_INVALID, msg)
+
+    def as_tensor(a, what, shape_tail):
+        if isinstance(a, np.ndarray):
+            if a.dtype != np.float32:
+                raise bad("%s: dtype %s, float32 expected" % (what, a.dtype))
+            t = torch.from_numpy(np.ascontiguousarray(a))
+        elif torch.is_tensor(a):
+            if a.dtype != torch.float32:
+                raise bad("%s: dtype %s, torch.float32 expected" % (what, a.dtype))
+            if a.device != dev:
+                raise bad("%s: on %s, the renderer is on %s" % (what, a.device, dev))
+            t = a
+        else:
+            raise bad("%s: a numpy array or a torch tensor expected" % what)
+        if t.dim() != 1 + len(shape_tail) or tuple(t.shape[1:]) != shape_tail:
+            raise bad("%s: shape %s, [N%s] expected" % (what, tuple(t.shape), "".join(", %d" % d for d in shape_tail)))
+        return t
+
+    first = origins
+    from_numpy = isinstance(first, np.ndarray)
+    if directions is None:
+        rays = as_tensor(origins, "rays", (8,))
+        parts = [rays]
+    else:
+        org, dirs = as_tensor(origins, "origins", (3,)), as_tensor(directions, "directions", (3,))
+        if org.shape[0] != dirs.shape[0]:
+            raise bad("origins and directions hold %d and %d rays" % (org.shape[0], dirs.shape[0]))
+        parts = [org, dirs]
+    n = parts[0].shape[0]
+    interval = []
+    for name, v in (("tmin", tmin), ("tmax", tmax)):
+        if v is None or isinstance(v, (int, float, np.floating, np.integer)):
+            interval.append(v)
+        else:
+            t = as_tensor(v, name, ())
+            if t.shape[0] != n:
+                raise bad("%s holds %d values for %d rays" % (name, t.shape[0], n))
+            interval.append(t)
+            parts.append(t)
+    if len({isinstance(p, np.ndarray) for p in (origins, directions, tmin, tmax) if isinstance(p, np.ndarray) or torch.is_tensor(p)}) > 1:
+        raise bad("mix of numpy arrays and device tensors")
+    if from_numpy:
+        parts = [p.to(dev) for p in parts]
+    if directions is None:
+        rays = parts[0]
+        if interval[0] is not None or interval[1] is not None:
+            raise bad("packed rays carry their own tmin / tmax")
+        if not rays.is_contiguous() or rays.data_ptr() % 16:
+            rays = rays.contiguous().clone()
+        return rays, from_numpy
+    org, dirs = parts[0], parts[1]
+    rest = iter(parts[2:])
+    rays = torch.empty((n, 8), dtype=torch.float32, device=dev)       # packed on the device, on the current stream
+    rays[:, 0:3] = org
+    rays[:, 4:7] = dirs
+    for col, v in ((3, interval[0]), (7, interval[1])):
+        rays[:, col] = next(rest) if torch.is_tensor(v) or isinstance(v, np.ndarray) else float(v)
+    return rays, from_numpy
+
+
 class Renderer:
     """Core/Renderer.hpp:14-47."""
 
@@ -473,7 +544,45 @@ class Renderer:
         self._h = _lib.drt_renderer_create(device)
         if not self._h:
             raise DrtError(ERR_DEVICE, (_lib.drt_last_error() or b"").decode())
+        self._device = device
         self.m_RendererSettings = RendererSettings()
+
+    def _ray_query(self, scene, origins, directions, tmin, tmax, occluded):
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        rays, from_numpy = _ray_batch(torch, dev, origins, directions, tmin, tmax)
+        n = rays.shape[0]
+        if occluded:
+            out = torch.empty(n, dtype=torch.uint8, device=dev)
+            fn = _lib.drt_renderer_occluded
+        else:
+            out = torch.empty((n, 4), dtype=torch.float32, device=dev)
+            fn = _lib.drt_renderer_trace_rays
+        if n:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(fn(self._h, scene._h, rays.data_ptr(), out.data_ptr(), n, stream))
+        if occluded:
+            res = out.view(torch.bool)
+            return res.cpu().numpy() if from_numpy else res
+        if from_numpy:
+            h = out.cpu().numpy()
+            return RayHits(h[:, 0].copy(), h.view(np.int32)[:, 1].copy(), h[:, 2].copy(), h[:, 3].copy())
+        return RayHits(out[:, 0], out.view(torch.int32)[:, 1], out[:, 2], out[:, 3])
+
+    def traceRays(self, scene, origins, directions=None, tmin=0.0, tmax=FLT_MAX):
+        """Closest hit of every ray (drt_renderer_trace_rays): RayHits(t, prim, u, v), prim -1 = miss (then t = tmax).
+        origins / directions [N, 3] float32, or origins = packed rays [N, 8] (org, tmin, dir, tmax) and directions None;
+        tmin / tmax scalars or [N] arrays.  Device tensors in, device tensors out (enqueued on the current torch stream);
+        numpy in, numpy out."""
+        if directions is None and (tmin, tmax) == (0.0, FLT_MAX):
+            tmin = tmax = None
+        return self._ray_query(scene, origins, directions, tmin, tmax, False)
+
+    def occluded(self, scene, origins, directions=None, tmin=0.0, tmax=float("inf")):
+        """Whether anything lies on each ray within (tmin, tmax) (drt_renderer_occluded): bool [N].  Arguments as traceRays."""
+        if directions is None and tmin == 0.0 and tmax == float("inf"):
+            tmin = tmax = None
+        return self._ray_query(scene, origins, directions, tmin, tmax, True)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None

@@ -18,6 +18,7 @@
 
 #include "device_scene.hpp"
 #include "render_kernels.hpp"
+#include "ray_query.hpp"
 #include "scene_host.hpp"
 #include "bvh_build_device.hpp"
 #include "png_decode.hpp"
@@ -135,6 +136,15 @@ struct drt_renderer {
     DeviceArray<uint8_t> d_texels;
     SceneView view;
     int bvh_depth = 0;
+    // batched ray queries (drt_renderer_trace_rays / _occluded): claim heads, HBM stack levels, and the event after the last
+    // query launch -- the next query waits for it on its own stream (they share heads and stack), a scene re-upload on the host
+    hipEvent_t ev_query = nullptr;
+    hipStream_t query_stream = nullptr;
+    bool query_recorded = false;
+    unsigned int *rq_heads = nullptr;
+    void *rq_stack = nullptr;
+    size_t rq_stack_bytes = 0;
+    int rq_refill_min = 16;                    // DRT_RQ_REFILL: idle lanes that make a wave claim new rays (64 = only when all are)
 
     float *cur_accum() const { return ext_accum ? ext_accum : accum; }
     float *cur_rgba() const { return ext_rgba ? ext_rgba : rgba; }
@@ -384,7 +394,9 @@ drt_renderer *drt_renderer_create(int32_t device) {
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) r->num_cus = cus;
     int khz = 0;
     if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) == hipSuccess && khz > 0) r->wall_clock_khz = khz;
+    r->rq_refill_min = std::min(64, std::max(1, env_int("DRT_RQ_REFILL", r->rq_refill_min)));
     if (hipEventCreate(&r->ev_start) != hipSuccess || hipEventCreate(&r->ev_stop) != hipSuccess ||
+        hipEventCreateWithFlags(&r->ev_query, hipEventDisableTiming) != hipSuccess ||
         hipMalloc((void **)&r->counters, sizeof(drt_counters)) != hipSuccess ||
         hipMalloc((void **)&r->records, sizeof(unsigned long long) * 4 * drt_renderer::kRecords) != hipSuccess ||
         hipMemset(r->records, 0, sizeof(unsigned long long) * 4 * drt_renderer::kRecords) != hipSuccess ||
@@ -415,6 +427,9 @@ void drt_renderer_destroy(drt_renderer *r) {
     if (r->pool_scratch.aux_next) (void)hipFree(r->pool_scratch.aux_next);
     if (r->pool_scratch.aux_stack) (void)hipFree(r->pool_scratch.aux_stack);
     if (r->samples) (void)hipFree(r->samples);
+    if (r->rq_heads) (void)hipFree(r->rq_heads);
+    if (r->rq_stack) (void)hipFree(r->rq_stack);
+    if (r->ev_query) (void)hipEventDestroy(r->ev_query);
     if (r->ev_start) (void)hipEventDestroy(r->ev_start);
     if (r->ev_stop) (void)hipEventDestroy(r->ev_stop);
     delete r;
@@ -581,6 +596,7 @@ static int upload_scene(drt_renderer *r, const drt_scene *scene) {
     if (r->uploaded_scene == scene && r->uploaded_revision == scene->host.revision) return DRT_OK;
     PackedScene ps;
     try { ps = scene->host.pack(); } catch (...) { return from_exception(); }
+    if (r->query_recorded) HIP_TRY(hipEventSynchronize(r->ev_query));     // a query launch in flight reads the old buffers
     r->free_scene();
     HIP_TRY(r->d_inner.upload(ps.inner));
     HIP_TRY(r->d_leaves.upload(ps.leaves));
@@ -794,6 +810,62 @@ int drt_renderer_wait(drt_renderer *r, float *delta_ms) {
                                                                                                    "0x40000 path id from a queue, 0x80000 shading record)"));
     }
     return DRT_OK;
+}
+
+// ------------------------------------------------------------------ batched ray queries (kernel_ray_query.hip)
+static int ray_query_impl(drt_renderer *r, const drt_scene *scene, const drt_ray *rays, void *out, uint32_t n, void *hip_stream,
+                          bool occluded) {
+    if (!r || !scene) return fail(DRT_ERR_INVALID, "null argument");
+    if (n == 0) return DRT_OK;
+    if (!rays || !out) return fail(DRT_ERR_INVALID, "null ray or result pointer");
+    if (((uintptr_t)rays & 15u) != 0 || (!occluded && ((uintptr_t)out & 15u) != 0))
+        return fail(DRT_ERR_INVALID, "rays and hits must be 16-byte aligned");
+    if (n > 0x7fffffffu) return fail(DRT_ERR_INVALID, "at most 2^31 - 1 rays per call");
+    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
+    HIP_TRY(hipSetDevice(r->device));
+    (void)hipGetLastError();                   // (see render_batch_impl: only this call's own errors count)
+    for (const void *p : { (const void *)rays, (const void *)out }) {
+        hipPointerAttribute_t at;
+        std::memset(&at, 0, sizeof at);
+        const hipError_t e = hipPointerGetAttributes(&at, p);
+        (void)hipGetLastError();
+        if (e != hipSuccess || !(at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged) || at.device != r->device)
+            return fail(DRT_ERR_INVALID, "rays and results must be device memory on the renderer's device");
+    }
+    int rc = upload_scene(r, scene);
+    if (rc != DRT_OK) return rc;
+    if (r->bvh_depth > 64) return fail(DRT_ERR_UNSUPPORTED, "BVH deeper than 64 levels (the reference's traversal stack, BVHTraversal.cuh:17)");
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : r->stream;
+    if (r->query_recorded && r->query_stream != s) HIP_TRY(hipStreamWaitEvent(s, r->ev_query, 0));
+    if (!r->rq_heads) HIP_TRY(hipMalloc((void **)&r->rq_heads, sizeof(unsigned int) * kRqHeadWords));
+    const size_t stack_bytes = ray_query_stack_bytes(r->num_cus, r->bvh_depth, occluded);
+    if (stack_bytes > r->rq_stack_bytes) {
+        if (r->query_recorded) HIP_TRY(hipEventSynchronize(r->ev_query));
+        if (r->rq_stack) { (void)hipFree(r->rq_stack); r->rq_stack = nullptr; r->rq_stack_bytes = 0; }
+        HIP_TRY(hipMalloc(&r->rq_stack, stack_bytes));
+        r->rq_stack_bytes = stack_bytes;
+    }
+    HIP_TRY(hipMemsetAsync(r->rq_heads, 0, sizeof(unsigned int) * kRqHeadWords, s));
+    RayQueryArgs a;
+    a.rays = rays; a.out = out; a.n = n;
+    a.stack_levels = (uint32_t)std::max(1, r->bvh_depth);
+    a.refill_min = (uint32_t)r->rq_refill_min;
+    a.heads = r->rq_heads;
+    a.stack_hbm = (uint32_t *)r->rq_stack;
+    const char *name = nullptr;                // (kernel_info names the last render kernel: queries leave it alone)
+    HIP_TRY(launch_ray_query(r->view, occluded, a, r->num_cus, s, &name));
+    HIP_TRY(hipEventRecord(r->ev_query, s));
+    r->query_stream = s;
+    r->query_recorded = true;
+    return DRT_OK;
+}
+
+int drt_renderer_trace_rays(drt_renderer *r, const drt_scene *scene, const drt_ray *rays, drt_hit *hits, uint32_t n, void *hip_stream) {
+    return ray_query_impl(r, scene, rays, hits, n, hip_stream, false);
+}
+
+int drt_renderer_occluded(drt_renderer *r, const drt_scene *scene, const drt_ray *rays, uint8_t *occluded, uint32_t n, void *hip_stream) {
+    return ray_query_impl(r, scene, rays, occluded, n, hip_stream, true);
 }
 
 int drt_renderer_render(drt_renderer *r, const drt_camera *cam, const drt_scene *scene, float *delta_ms) {

@@ -273,6 +273,14 @@ public:
         drt::check(group ? drt_group_read_rgba32f(group, dst, n) : drt_renderer_read_rgba32f(handle, dst, n));
     }
     void *DeviceRenderTarget() { return group ? drt_group_device_rgba(group) : drt_renderer_device_rgba(handle); }
+    // Batched ray queries (drt_renderer_trace_rays / _occluded: device arrays, enqueued on `stream`, NULL = the renderer's).
+    // A multi-device renderer answers them on its first device (handle = drt_group_renderer(group, 0)).
+    void TraceRays(const Scene &scene, const drt_ray *rays, drt_hit *hits, uint32_t n, void *stream = nullptr) {
+        drt::check(drt_renderer_trace_rays(handle, scene.handle, rays, hits, n, stream));
+    }
+    void Occluded(const Scene &scene, const drt_ray *rays, uint8_t *occluded, uint32_t n, void *stream = nullptr) {
+        drt::check(drt_renderer_occluded(handle, scene.handle, rays, occluded, n, stream));
+    }
 
     RendererSettings m_RendererSettings;
     drt_renderer *handle = nullptr;       // the (first) device's renderer

@@ -25,7 +25,8 @@
 extern "C" {
 #endif
 
-/* 2: drt_counters grew by sampler_tries; drt_group_* and drt_material_model entry points (round 2) are part of it */
+/* 2: drt_counters grew by sampler_tries; drt_group_* and drt_material_model entry points (round 2) are part of it; the ray-query
+ * entry points (drt_renderer_trace_rays / _occluded) are additions to it */
 #define DRT_ABI_VERSION 2
 
 typedef enum {
@@ -219,6 +220,30 @@ int           drt_renderer_read_rgba32f(drt_renderer *r, float *dst, size_t dst_
 int           drt_renderer_read_accum(drt_renderer *r, float *dst, size_t dst_floats);     /* width*local_rows*3 */
 void         *drt_renderer_device_rgba(drt_renderer *r);                      /* device float4[width*local_rows] */
 void         *drt_renderer_device_accum(drt_renderer *r);                     /* device float3[width*local_rows] */
+
+/* ---- batched ray queries (new; the reference has TraceRay / RayTest, Kernel/TraceRay.cu:15-38, but no public entry) ----
+ * One ray = org, tmin, dir, tmax (fp32).  dir is used as given (not normalised; t is in units of |dir|), inv_dir = 1/dir as
+ * the renderer computes it.  The traversals are the renderer's, bit for bit (BVH/BVHTraversal.cuh:14-134):
+ *   drt_renderer_trace_rays  traverseBVH started as TraceRay starts it: closest.t = tmax (TraceRay.cu:18), a node is culled
+ *                            by !(-1 < d && d < tmax) (:38, the interval (-1, tmax) of RayGen), far child pushed first, strict <
+ *                            (the first triangle found wins a tie), AnyHit alpha test.  Departure: a triangle hit counts only if
+ *                            t > tmin (the reference's TODO "inner clipping", :37).  tmin = 0, tmax = FLT_MAX is TraceRay's hit.
+ *   drt_renderer_occluded    traverseBVH_raytest.  Departures: the root is skipped if d < 0 || d > tmax, a child is pushed iff
+ *                            d >= 0 && !(d > tmax) (tmax culls boxes), a triangle counts iff t > tmin && t < tmax && AnyHit.
+ *                            tmin = 0, tmax = +inf is RayTest, the renderer's shadow test.
+ * Results: drt_hit {t, prim, u, v}: prim = triangle index in drt_scene_get_triangles order, u, v = uvw.y, uvw.z of
+ * Intersection.cu (uvw.x = 1 - u - v); a miss is {tmax, -1, 0, 0}.  occluded: one byte per ray, 0 or 1.  A result depends on
+ * its ray and the scene only (not on its position in the array, the batch size or the scheduling).
+ * rays / hits / occluded are device pointers on the renderer's device, rays and hits 16-byte aligned, n < 2^31; n == 0 is a
+ * no-op.  hip_stream NULL = the renderer's stream.  The call enqueues and returns (nothing is synchronised); queries of one
+ * renderer run in the order they were made, whatever their streams.  The scene is uploaded as for rendering (once, shared);
+ * DRT_ERR_UNSUPPORTED for trees deeper than 64 levels; DRT_ERR_INVALID for null / misaligned / host or other-device pointers
+ * and while a drt_renderer_render_batch_async batch is pending.  The framebuffer, sample count, counters and kernel info are
+ * not touched. */
+typedef struct drt_ray { float org[3]; float tmin; float dir[3]; float tmax; } drt_ray;      /* 32 B */
+typedef struct drt_hit { float t; int32_t prim; float u, v; } drt_hit;                      /* 16 B */
+int           drt_renderer_trace_rays(drt_renderer *r, const drt_scene *scene, const drt_ray *rays, drt_hit *hits, uint32_t n, void *hip_stream);
+int           drt_renderer_occluded(drt_renderer *r, const drt_scene *scene, const drt_ray *rays, uint8_t *occluded, uint32_t n, void *hip_stream);
 
 /* ---- multi-GPU sharding (new; the reference is single-device) ---- */
 /* This renderer owns the rows y with (y / stripe_rows) % world == rank, stored compactly in stripe order.
