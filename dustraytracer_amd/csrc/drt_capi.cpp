@@ -109,19 +109,16 @@ struct drt_renderer {
     size_t sample_budget = (size_t)1 << 30;   // frames of one batch are split so that a launch needs at most this much
     int num_cus = 256;
     int frames_in_flight = 1;                 // drt_renderer_set_frames_in_flight
-    bool use_pixel_walk = false;              // DRT_KERNEL=pixel_walk selects the first (non-persistent) kernel
-    int use_path_pool = 1;                    // path_pool where it applies (lean paths, scene in LDS); DRT_KERNEL=wave_queue: never
-    bool pool_launched = false;               // the batch in flight launched path_pool at least once
+    Tuning tune;                              // the environment switches, read by drt_renderer_create
+    TracerChoice choice;                      // the tracing kernel of the last batch (choose_tracer) ...
+    LaunchShape shape;                        // ... and the shape of its last launch
     WaveQueueCache wq_cache;                  // measured choice among wave_queue's launch packagings
     PoolScratch pool_scratch;
-    PoolTuning pool_tuning;                   // DRT_POOL_THREADS / _PATHS / _MIN_FILL / _PATIENCE
     uint32_t pool_t_class[3] = { 0, 0, 0 };   // leaf-size classes of the uploaded scene (path_pool's T queues)
     bool scene_has_alpha = false;
     int vote_node = 12, vote_shade = 44, vote_dir = 4, vote_spec = 8;
     int leaf_chain = -1;                              // DRT_LEAF_CHAIN: -1 = by tree depth (<= 4 levels), 0 / 1 = forced
     int vote_tail_node = 4, vote_tail_shade = 36;    // once the queue is empty (DRT_VOTE_TN / DRT_VOTE_TS): pops stop waiting for company   // wave_queue phase-voting thresholds (DRT_VOTE_N/S/R/P override)
-    const char *kernel_name = "";
-    int launch_shape[5] = { 0, 0, 0, 0, 0 }; // wave_queue: stack slots per lane, workgroups per CU, LDS KiB per workgroup, threads per workgroup; path_pool: + pool paths
     // device copy of the scene last rendered
     const drt_scene *uploaded_scene = nullptr;
     uint64_t uploaded_revision = 0;
@@ -360,14 +357,15 @@ drt_renderer *drt_renderer_create(int32_t device) {
     try { r = new drt_renderer(); } catch (...) { from_exception(); return nullptr; }
     r->device = device;
     drt_default_settings(&r->settings);
+    Tuning &t = r->tune;
     const char *which = std::getenv("DRT_KERNEL");
-    r->use_pixel_walk = which && std::strcmp(which, "pixel_walk") == 0;
-    if (r->use_pixel_walk && !pixel_walk_built_in()) {
+    if (which && std::strcmp(which, "pixel_walk") == 0) t.kernel = Tracer::pixel_walk;
+    if (which && std::strcmp(which, "wave_queue") == 0) t.kernel = Tracer::wave_queue;
+    if (t.kernel == Tracer::pixel_walk && !pixel_walk_built_in()) {
         fail(DRT_ERR_UNSUPPORTED, "DRT_KERNEL=pixel_walk: that kernel is not part of this library (the tests build libdrt_hip_pixel_walk.so: make pixel-walk)");
         delete r;
         return nullptr;
     }
-    r->use_path_pool = !(which && (std::strcmp(which, "wave_queue") == 0 || std::strcmp(which, "pixel_walk") == 0));
     auto env_int = [](const char *name, int dflt) { const char *v = std::getenv(name); return (v && *v) ? std::atoi(v) : dflt; };
     r->vote_node = std::max(1, env_int("DRT_VOTE_N", r->vote_node));
     r->vote_shade = std::max(1, env_int("DRT_VOTE_S", r->vote_shade));
@@ -377,19 +375,22 @@ drt_renderer *drt_renderer_create(int32_t device) {
     r->vote_tail_shade = std::max(1, env_int("DRT_VOTE_TS", r->vote_tail_shade));
     r->leaf_chain = env_int("DRT_LEAF_CHAIN", r->leaf_chain);
     r->sample_budget = (size_t)std::max(1, env_int("DRT_SAMPLE_MB", 1024)) << 20;
-    r->pool_tuning.threads = env_int("DRT_POOL_THREADS", 0); r->pool_tuning.paths = env_int("DRT_POOL_PATHS", 0);
-    r->pool_tuning.stack_lds = env_int("DRT_POOL_STACK_LDS", r->pool_tuning.stack_lds);
-    r->pool_tuning.min_fill = env_int("DRT_POOL_MIN_FILL", r->pool_tuning.min_fill);
-    r->pool_tuning.patience = env_int("DRT_POOL_PATIENCE", r->pool_tuning.patience);
-    r->pool_tuning.n_loop = env_int("DRT_POOL_N_LOOP", r->pool_tuning.n_loop);
-    r->pool_tuning.n_min_lanes = env_int("DRT_POOL_N_MIN", r->pool_tuning.n_min_lanes);
-    r->pool_tuning.n_fuse_loop = env_int("DRT_POOL_N_FUSE_LOOP", r->pool_tuning.n_fuse_loop);
-    r->pool_tuning.n_fuse_min = env_int("DRT_POOL_N_FUSE_MIN", r->pool_tuning.n_fuse_min);
-    r->pool_tuning.cold_lds_kb = env_int("DRT_POOL_COLD_KB", r->pool_tuning.cold_lds_kb);
-    r->pool_tuning.share_grid = env_int("DRT_POOL_SHARE_GRID", r->pool_tuning.share_grid);
-    r->pool_tuning.dir_tries = env_int("DRT_POOL_DIR_TRIES", r->pool_tuning.dir_tries);
-    if (env_int("DRT_POOL_STATS", 0) != 0 && hipMalloc((void **)&r->pool_tuning.stats, 40 * sizeof(unsigned long long)) == hipSuccess)
-        (void)hipMemset(r->pool_tuning.stats, 0, 40 * sizeof(unsigned long long));
+    t.pool_scene_bytes = (size_t)env_int("DRT_POOL_SCENE_KB", (int)(kLdsSceneBytes / 1024)) * 1024;
+    t.lds_scene_bytes = (size_t)env_int("DRT_LDS_SCENE_KB", (int)(kLdsSceneBytes / 1024)) * 1024;
+    t.pool_hbm = env_int("DRT_POOL_HBM", 1) != 0;
+    t.pool_verbose = std::getenv("DRT_POOL_VERBOSE") != nullptr;
+    if (const char *e = std::getenv("DRT_POOL_T_CLASSES")) t.t_class_set = std::sscanf(e, "%u,%u,%u", &t.t_class[0], &t.t_class[1], &t.t_class[2]) == 3;
+    t.threads = env_int("DRT_POOL_THREADS", 0); t.paths = env_int("DRT_POOL_PATHS", 0); t.stack_lds = env_int("DRT_POOL_STACK_LDS", t.stack_lds);
+    t.min_fill = env_int("DRT_POOL_MIN_FILL", t.min_fill); t.patience = env_int("DRT_POOL_PATIENCE", t.patience);
+    t.n_loop = env_int("DRT_POOL_N_LOOP", t.n_loop); t.n_min_lanes = env_int("DRT_POOL_N_MIN", t.n_min_lanes);
+    t.n_fuse_loop = env_int("DRT_POOL_N_FUSE_LOOP", t.n_fuse_loop); t.n_fuse_min = env_int("DRT_POOL_N_FUSE_MIN", t.n_fuse_min);
+    t.cold_lds_kb = env_int("DRT_POOL_COLD_KB", t.cold_lds_kb); t.share_grid = env_int("DRT_POOL_SHARE_GRID", t.share_grid);
+    t.dir_tries = env_int("DRT_POOL_DIR_TRIES", t.dir_tries);
+    if (env_int("DRT_POOL_STATS", 0) != 0 && hipMalloc((void **)&t.stats, 40 * sizeof(unsigned long long)) == hipSuccess)
+        (void)hipMemset(t.stats, 0, 40 * sizeof(unsigned long long));
+    t.wq_only_small = env_int("DRT_WG_THREADS", 0) == 256; t.wq_only_wide = env_int("DRT_STACK_REF16", 1) == 0; t.wq_tris_wide = env_int("DRT_TRIS_WIDE", 1) != 0;
+    if (std::getenv("DRT_MAX_BLOCKS_PER_CU")) t.max_blocks_per_cu = std::max(1, env_int("DRT_MAX_BLOCKS_PER_CU", 1));
+    if (std::getenv("DRT_CHUNKS_PER_WG")) t.chunks_per_wg = std::max(1, env_int("DRT_CHUNKS_PER_WG", 1));
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cus > 0) r->num_cus = cus;
     int khz = 0;
@@ -420,7 +421,7 @@ void drt_renderer_destroy(drt_renderer *r) {
     if (r->records) (void)hipFree(r->records);
     if (r->records_host) (void)hipHostFree(r->records_host);
     if (r->tile_counter) (void)hipFree(r->tile_counter);
-    if (r->pool_tuning.stats) (void)hipFree(r->pool_tuning.stats);
+    if (r->tune.stats) (void)hipFree(r->tune.stats);
     if (r->pool_scratch.aux) (void)hipFree(r->pool_scratch.aux);
     if (r->pool_scratch.aux_slot) (void)hipFree(r->pool_scratch.aux_slot);
     if (r->pool_scratch.aux_light) (void)hipFree(r->pool_scratch.aux_light);
@@ -572,23 +573,27 @@ int drt_renderer_kernel_span(const drt_renderer *r, float *ms) {
 
 int32_t drt_renderer_launch_count(const drt_renderer *r) { return r ? r->launches_last : 0; }
 
+// path_pool<lean|materials[+alpha][+sun],lds-scene|hbm-scene>, wave_queue<lean|general|counting[+alpha][+sun],...> or pixel_walk<stackN>,
+// then the shape of the last launch
 int drt_renderer_kernel_info(const drt_renderer *r, char *buf, size_t cap) {
     if (!r || !buf || cap == 0) return fail(DRT_ERR_INVALID, "bad argument");
-    if (r->launch_shape[1] > 0 && std::strncmp(r->kernel_name, "path_pool", 9) == 0)
-    {
-        // (launch_shape[0]: stack levels | levels kept in LDS << 8)
-        const int levels = r->launch_shape[0] & 255, in_lds = r->launch_shape[0] >> 8;
-        char stack[48];
-        if (in_lds < levels) std::snprintf(stack, sizeof stack, "%d(%d in LDS)", levels, in_lds);
-        else std::snprintf(stack, sizeof stack, "%d", levels);
-        std::snprintf(buf, cap, "%s stack=%s wg/CU=%d threads=%d paths=%d lds=%dKiB", r->kernel_name, stack, r->launch_shape[1],
-                      r->launch_shape[3], r->launch_shape[4], r->launch_shape[2]);
-    }
-    else if (r->launch_shape[1] > 0 && std::strncmp(r->kernel_name, "wave_queue", 10) == 0)
-        std::snprintf(buf, cap, "%s stack=%d%s wg/CU=%d%s lds=%dKiB", r->kernel_name, r->launch_shape[0], (r->launch_shape[3] & 1) ? "x6B" : ((r->launch_shape[3] & 2) ? " tris=3" : ""),
-                      r->launch_shape[1], r->launch_shape[3] >= 512 ? "x512" : "", r->launch_shape[2]);
+    static const char *const wave_queue_builds[6] = { "lean", "general", "counting", "lean+alpha", "lean+sun", "lean+alpha+sun" };
+    const TracerChoice &c = r->choice;
+    const LaunchShape &s = r->shape;
+    char stack[48];
+    if (s.levels_in_lds < s.stack_levels) std::snprintf(stack, sizeof stack, "%d(%d in LDS)", s.stack_levels, s.levels_in_lds);
+    else std::snprintf(stack, sizeof stack, "%d", s.stack_levels);
+    if (c.family == Tracer::path_pool)
+        std::snprintf(buf, cap, "path_pool<%s%s%s,%s> stack=%s wg/CU=%d threads=%d paths=%d lds=%dKiB", (c.pool_flags & 16) ? "materials" : "lean",
+                      (c.pool_flags & 4) ? "+alpha" : "", (c.pool_flags & 2) ? "+sun" : "", (c.pool_flags & 8) ? "hbm-scene" : "lds-scene", stack,
+                      s.groups_per_cu, s.threads, s.paths, s.lds_kib);
+    else if (c.family == Tracer::wave_queue)
+        std::snprintf(buf, cap, "wave_queue<%s,%s> stack=%s%s wg/CU=%d%s lds=%dKiB", wave_queue_builds[c.wq_mode], c.wq_lds_scene ? "lds-scene" : "hbm-scene",
+                      stack, s.entry_bytes == 6 ? "x6B" : (s.tris == 3 ? " tris=3" : ""), s.groups_per_cu, s.threads >= 512 ? "x512" : "", s.lds_kib);
+    else if (c.family == Tracer::pixel_walk)
+        std::snprintf(buf, cap, "pixel_walk<stack%d>", c.stack);
     else
-        std::snprintf(buf, cap, "%s", r->kernel_name);
+        buf[0] = 0;
     return DRT_OK;
 }
 
@@ -617,11 +622,8 @@ static int upload_scene(drt_renderer *r, const drt_scene *scene) {
     r->bvh_depth = ps.depth;
     r->scene_has_alpha = ps.any_alpha_texture;
     path_pool_leaf_classes(ps.leaves, r->pool_t_class);
-    if (const char *e = std::getenv("DRT_POOL_T_CLASSES")) {              // experiments: "a,b,c" = upper step counts of T0, T1, T2
-        unsigned a0 = 0, a1 = 0, a2 = 0;
-        if (std::sscanf(e, "%u,%u,%u", &a0, &a1, &a2) == 3) { r->pool_t_class[0] = a0; r->pool_t_class[1] = a1; r->pool_t_class[2] = a2; }
-    }
-    if (std::getenv("DRT_POOL_VERBOSE")) std::fprintf(stderr, "path_pool leaf classes: %u %u %u\n", r->pool_t_class[0], r->pool_t_class[1], r->pool_t_class[2]);
+    if (r->tune.t_class_set) std::memcpy(r->pool_t_class, r->tune.t_class, sizeof r->pool_t_class);
+    if (r->tune.pool_verbose) std::fprintf(stderr, "path_pool leaf classes: %u %u %u\n", r->pool_t_class[0], r->pool_t_class[1], r->pool_t_class[2]);
     r->uploaded_scene = scene;
     r->uploaded_revision = scene->host.revision;
     return DRT_OK;
@@ -682,12 +684,44 @@ static void fill_frame_params(const drt_renderer *r, const drt_camera *cam, Fram
     fp.leaf_chain = r->leaf_chain < 0 ? (r->bvh_depth <= 4 ? 1 : 0) : (r->leaf_chain != 0);
 }
 
+// The tracing kernel of a batch and its build: every rule that chooses one is here.  Returns nullptr, or why the
+// batch cannot be rendered (DRT_ERR_UNSUPPORTED).
+static const char *choose_tracer(const Tuning &tune, const SceneView &sc, int bvh_depth, bool scene_has_alpha, const FrameParams &fp, TracerChoice &c) {
+    const bool material = fp.ext_emissive || fp.ext_specular || fp.ext_transmission, counting = fp.counters != nullptr;
+    c = TracerChoice{};
+    if (tune.kernel == Tracer::pixel_walk && !material) {        // (round 1's kernel has no material model)
+        c.family = Tracer::pixel_walk;
+        c.stack = bvh_depth <= 8 ? 8 : (bvh_depth <= 16 ? 16 : (bvh_depth <= 32 ? 32 : 64));      // (a stack never holds more than `depth` entries)
+        return nullptr;
+    }
+    // path_pool: no debug views, bounce index in 16 bits (15 in the material-model builds), stack height in 8, no statistics build of
+    // the material model; the lds-scene build has 12-bit triangle indices, the hbm-scene build 16-bit node references on its stacks
+    const size_t scene_bytes = wave_queue_scene_lds_bytes(sc);
+    const bool pool = tune.kernel == Tracer::path_pool && fp.render_mode == 0 && fp.bounce_limit <= (material ? 30000 : 60000) && bvh_depth <= 200 &&
+                      sc.root_ref != kNoNode && !(counting && material);
+    const bool in_lds = pool && scene_bytes <= tune.pool_scene_bytes && sc.n_tris < 4095u && path_pool_fits(sc, bvh_depth, scene_bytes, false);
+    if (in_lds || (pool && tune.pool_hbm && sc.n_inner < 32768u && sc.n_leaves < 32768u && path_pool_fits(sc, bvh_depth, 0, true))) {
+        c.family = Tracer::path_pool;
+        c.pool_flags = ((counting || tune.stats) && !material ? 1 : 0) | (fp.enable_sunlight ? 2 : 0) | (scene_has_alpha ? 4 : 0) | (in_lds ? 0 : 8) | (material ? 16 : 0);
+        return nullptr;
+    }
+    if (fp.ext_transmission)
+        return "the dielectric lobe of drt_material_model is rendered by path_pool only (not: debug views, counting, DRT_KERNEL=wave_queue or pixel_walk, "
+               "trees beyond 32 767 nodes, bounce limits beyond 30 000)";
+    // wave_queue: the counting build, the general one (debug views, the emissive term and mirror lobe), else lean
+    c.family = Tracer::wave_queue;
+    c.wq_mode = counting ? 2 : ((material || fp.render_mode != 0) ? 1 : (fp.enable_sunlight ? (scene_has_alpha ? 5 : 4) : (scene_has_alpha ? 3 : 0)));
+    // (a small scene under a degenerate, very deep tree: the stacks of one 256-thread group, 8 bytes per level and lane, and the scene
+    // copy must fit the CU's 160 KB together, else the tree is read from HBM and the stacks have the LDS to themselves)
+    c.wq_lds_scene = scene_bytes <= tune.lds_scene_bytes && scene_bytes + (size_t)std::max(bvh_depth, 1) * 256 * 8 <= 160u * 1024u;
+    return nullptr;
+}
+
 static int render_batch_impl(drt_renderer *r, const drt_camera *cam, const drt_scene *scene, uint32_t n_frames,
                              float *delta_ms, bool blocking) {
     if (!r || !cam || !scene) return fail(DRT_ERR_INVALID, "null argument");
     if (delta_ms) *delta_ms = 0.f;
     r->pending = false;
-    r->pool_launched = false;
     if (r->width == 0 || r->height == 0) return fail(DRT_ERR_INVALID, "ResizeBuffer has not been called");
     // Renderer.cu:82: nothing happens once m_FrameIndex == max_samples, so at most max_samples-1 frames accumulate.
     if ((int64_t)r->frame_index == (int64_t)r->settings.max_samples) return DRT_OK;
@@ -707,13 +741,15 @@ static int render_batch_impl(drt_renderer *r, const drt_camera *cam, const drt_s
     fill_frame_params(r, cam, fp);
     fp.frame_first = r->frame_index;
     fp.n_frames = n_frames;
+    if (const char *why = choose_tracer(r->tune, r->view, r->bvh_depth, r->scene_has_alpha, fp, r->choice)) return fail(DRT_ERR_UNSUPPORTED, why);
+    const TracerChoice &choice = r->choice;
+    r->shape = LaunchShape{};
     if (r->counting) HIP_TRY(hipMemsetAsync(r->counters, 0, sizeof(drt_counters), r->stream));
 
     r->spans_used = 0;
     HIP_TRY(hipEventRecord(r->ev_start, r->stream));                   // Renderer.cu:97
-    const bool material_ext = fp.ext_emissive || fp.ext_specular;          // only the general wave_queue kernel implements it
-    if (r->use_pixel_walk && !material_ext) {
-        HIP_TRY(launch_render(r->view, fp, r->bvh_depth, r->counting, r->stream, &r->kernel_name));
+    if (choice.family == Tracer::pixel_walk) {
+        HIP_TRY(launch_render(r->view, fp, choice, r->counting, r->stream));
         r->launches_last = 1;
     } else {
         // split the batch so that the per-sample colour buffer of one launch stays within the budget
@@ -745,17 +781,11 @@ static int render_batch_impl(drt_renderer *r, const drt_camera *cam, const drt_s
                 r->counters_used = 0;
             }
             unsigned int *const queue_head = r->tile_counter + (size_t)(r->counters_used++) * kQueueHeadBlockWords;
-            bool pool_hbm_scene = false;
-            const bool use_pool = r->use_path_pool && path_pool_supports(r->view, fp, r->bvh_depth, wave_queue_scene_lds_bytes(r->view), &pool_hbm_scene);
-            if (use_pool) r->pool_launched = true;
-            if (use_pool)
-                HIP_TRY(launch_path_pool(r->view, fp, r->bvh_depth, r->scene_has_alpha, pool_hbm_scene, r->pool_t_class, r->pool_tuning, r->pool_scratch, queue_head, r->samples, launch_status,
-                                         r->num_cus, r->stream, &r->kernel_name, r->launch_shape));
-            else if (fp.ext_transmission)
-                return fail(DRT_ERR_UNSUPPORTED, "the dielectric lobe of drt_material_model is rendered by path_pool only (not: debug views, DRT_KERNEL=wave_queue, trees beyond 32 767 nodes, bounce limits beyond 30 000)");
+            if (choice.family == Tracer::path_pool)
+                HIP_TRY(launch_path_pool(r->view, fp, r->bvh_depth, choice, r->pool_t_class, r->tune, r->pool_scratch, queue_head, r->samples, launch_status,
+                                         r->num_cus, r->stream, &r->shape));
             else
-            HIP_TRY(launch_wave_queue(r->view, fp, r->bvh_depth, r->counting ? 2 : (material_ext ? 1 : 0), r->scene_has_alpha, queue_head,
-                                      r->samples, r->num_cus, r->stream, &r->kernel_name, r->launch_shape, r->wq_cache));
+                HIP_TRY(launch_wave_queue(r->view, fp, r->bvh_depth, choice, r->tune, queue_head, r->samples, r->num_cus, r->stream, &r->shape, r->wq_cache));
         }
     }
     // the launches' records (execution span, status bits) travel to pinned host memory on the stream: drt_renderer_wait reads them
@@ -801,14 +831,11 @@ int drt_renderer_wait(drt_renderer *r, float *delta_ms) {
     }
     wave_queue_report(r->wq_cache, r->span_ms);
     r->pending = false;
-    if (r->pool_launched) {
-        r->pool_launched = false;
-        if (status != 0)
-            return fail(DRT_ERR_DEVICE, "path_pool kernel: status " + std::to_string(status) + (status < 0x100u ? " (a queue wait exceeded its bound; the launch was abandoned)"
-                                                                                                 : " (bits 8..: an index out of range was caught and clamped -- 0x100 triangle, 0x200 node, 0x400 leaf, "
-                                                                                                   "0x800 / 0x1000 hit triangle, 0x2000 material, 0x4000 texture, 0x8000 sample slot, 0x10000 / 0x20000 stack level, "
-                                                                                                   "0x40000 path id from a queue, 0x80000 shading record)"));
-    }
+    if (r->choice.family == Tracer::path_pool && status != 0)
+        return fail(DRT_ERR_DEVICE, "path_pool kernel: status " + std::to_string(status) + (status < 0x100u ? " (a queue wait exceeded its bound; the launch was abandoned)"
+                                                                                             : " (bits 8..: an index out of range was caught and clamped -- 0x100 triangle, 0x200 node, 0x400 leaf, "
+                                                                                               "0x800 / 0x1000 hit triangle, 0x2000 material, 0x4000 texture, 0x8000 sample slot, 0x10000 / 0x20000 stack level, "
+                                                                                               "0x40000 path id from a queue, 0x80000 shading record)"));
     return DRT_OK;
 }
 
@@ -974,13 +1001,14 @@ int drt_debug_wave_queue_plans(const drt_renderer *r, char *buf, size_t cap) {
     return DRT_OK;
 }
 
+// (path_pool's statistics builds only: launches of the material-model builds gather no statistics)
 int drt_debug_pool_stats(drt_renderer *r, uint64_t out[40], int32_t reset) {
     if (!r || !out) return fail(DRT_ERR_INVALID, "null argument");
-    if (!r->pool_tuning.stats) return fail(DRT_ERR_INVALID, "renderer was not created with DRT_POOL_STATS=1");
+    if (!r->tune.stats) return fail(DRT_ERR_INVALID, "renderer was not created with DRT_POOL_STATS=1");
     HIP_TRY(hipSetDevice(r->device));
     HIP_TRY(hipStreamSynchronize(r->stream));
-    HIP_TRY(hipMemcpy(out, r->pool_tuning.stats, 40 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (reset) HIP_TRY(hipMemset(r->pool_tuning.stats, 0, 40 * sizeof(uint64_t)));
+    HIP_TRY(hipMemcpy(out, r->tune.stats, 40 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (reset) HIP_TRY(hipMemset(r->tune.stats, 0, 40 * sizeof(uint64_t)));
     return DRT_OK;
 }
 

@@ -43,6 +43,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <utility>
 
 #include "device_access.hpp"
 #include "device_math.hpp"
@@ -1087,32 +1088,24 @@ __global__ __launch_bounds__(pool_max_threads(FLAGS)) __attribute__((amdgpu_wave
     }
 }
 
+// The builds of path_pool_kernel in this translation unit, and the one of `flags` among them (nullptr: not built here)
+#ifdef DRT_POOL_EXT_TU
+using PoolBuilds = std::integer_sequence<int, 16, 18, 20, 22, 24, 26, 28, 30, 48, 50, 52, 54, 56, 58, 60, 62>;     // the material model: no statistics builds
+#else
+using PoolBuilds = std::integer_sequence<int, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 32, 33, 34, 35, 36, 37, 38, 39, 40, 41, 42, 43, 44, 45, 46, 47>;
+#endif
+template <int... F>
+const void *pool_kernel(int flags, std::integer_sequence<int, F...>) {
+    const void *k = nullptr;
+    ((k = flags == F ? reinterpret_cast<const void *>(path_pool_kernel<F>) : k), ...);
+    return k;
+}
+
 }  // namespace
 
 #ifdef DRT_POOL_EXT_TU
 // ---- this translation unit (kernel_path_pool_ext.o): the material-model variants of the kernel, nothing else ----
-const void *path_pool_ext_kernel(int flags) {        // (untyped: the argument struct lives in each translation unit's anonymous namespace)
-    if (flags & 32) switch (flags & 14) {
-    case 0: return reinterpret_cast<const void *>(path_pool_kernel<48>);
-    case 2: return reinterpret_cast<const void *>(path_pool_kernel<50>);
-    case 4: return reinterpret_cast<const void *>(path_pool_kernel<52>);
-    case 6: return reinterpret_cast<const void *>(path_pool_kernel<54>);
-    case 8: return reinterpret_cast<const void *>(path_pool_kernel<56>);
-    case 10: return reinterpret_cast<const void *>(path_pool_kernel<58>);
-    case 12: return reinterpret_cast<const void *>(path_pool_kernel<60>);
-    default: return reinterpret_cast<const void *>(path_pool_kernel<62>);
-    }
-    switch (flags & 14) {
-    case 0: return reinterpret_cast<const void *>(path_pool_kernel<16>);
-    case 2: return reinterpret_cast<const void *>(path_pool_kernel<18>);
-    case 4: return reinterpret_cast<const void *>(path_pool_kernel<20>);
-    case 6: return reinterpret_cast<const void *>(path_pool_kernel<22>);
-    case 8: return reinterpret_cast<const void *>(path_pool_kernel<24>);
-    case 10: return reinterpret_cast<const void *>(path_pool_kernel<26>);
-    case 12: return reinterpret_cast<const void *>(path_pool_kernel<28>);
-    default: return reinterpret_cast<const void *>(path_pool_kernel<30>);
-    }
-}
+const void *path_pool_ext_kernel(int flags) { return pool_kernel(flags, PoolBuilds{}); }   // (untyped: PoolArgs lives in each translation unit's anonymous namespace)
 }  // namespace drt
 #else
 const void *path_pool_ext_kernel(int flags);                    // kernel_path_pool_ext.o
@@ -1146,30 +1139,20 @@ void path_pool_leaf_classes(const std::vector<LeafRange> &leaves, uint32_t out[3
             }
 }
 
-// Does the pool apply, and in which build: *hbm_scene = the traversal data does not fit LDS next to a pool and is read from global memory.
-bool path_pool_supports(const SceneView &sc, const FrameParams &fp, int bvh_depth, size_t scene_lds_bytes, bool *hbm_scene) {
-    if (fp.render_mode != 0) return false;                                                // no debug views (wave_queue's general build)
-    if (fp.bounce_limit > 60000 || bvh_depth > 200) return false;                         // bounce index in 16 bits, stack height in 8
-    if ((fp.ext_emissive || fp.ext_specular || fp.ext_transmission) && fp.bounce_limit > 30000) return false;      // (material-model builds: 15 bits)
-    if (sc.root_ref == kNoNode) return false;
-    static const size_t scene_limit = std::getenv("DRT_POOL_SCENE_KB") ? (size_t)std::atoi(std::getenv("DRT_POOL_SCENE_KB")) * 1024 : kLdsSceneBytes;
-    static const bool hbm_allowed = !(std::getenv("DRT_POOL_HBM") && std::atoi(std::getenv("DRT_POOL_HBM")) == 0);
+bool path_pool_fits(const SceneView &sc, int bvh_depth, size_t scene_lds_bytes, bool hbm_scene) {
     const uint32_t stack_entries = (uint32_t)std::max(bvh_depth - 1, 1);
-    // lds-scene build: 12-bit triangle indices, and a pool of at least 256 paths has to fit the CU's LDS next to the scene copy
-    // (a very deep tree's stacks may not leave room)
-    bool in_lds = scene_lds_bytes <= scene_limit && sc.n_tris < 4095u;
-    if (in_lds && pool_layout(512u, 512u, stack_entries, pool_scene_bytes(sc), 0u, (uint32_t)kNQ).total > 160u * 1024u &&
-        (scene_lds_bytes > kLdsSceneBytes || pool_layout(256u, 256u, stack_entries, pool_scene_bytes(sc), 0u, (uint32_t)kNQ).total > 160u * 1024u)) in_lds = false;
-    if (hbm_scene) *hbm_scene = !in_lds;
-    if (in_lds) return true;
-    return hbm_allowed && sc.n_inner < 32768u && sc.n_leaves < 32768u &&               // 16-bit node references on the stacks
-           pool_layout(256u, 256u, stack_entries, 0u, 0u, (uint32_t)kNQ, 16u, 6u).total <= 160u * 1024u;
+    if (hbm_scene) return pool_layout(256u, 256u, stack_entries, 0u, 0u, (uint32_t)kNQ, 16u, 6u).total <= 160u * 1024u;
+    // (a very deep tree's stacks may not leave room next to the scene copy)
+    return pool_layout(512u, 512u, stack_entries, pool_scene_bytes(sc), 0u, (uint32_t)kNQ).total <= 160u * 1024u ||
+           (scene_lds_bytes <= kLdsSceneBytes && pool_layout(256u, 256u, stack_entries, pool_scene_bytes(sc), 0u, (uint32_t)kNQ).total <= 160u * 1024u);
 }
 
-hipError_t launch_path_pool(const SceneView &sc, const FrameParams &fp, int bvh_depth, bool scene_has_alpha, bool hbm_scene, const uint32_t t_class[3], const PoolTuning &tune,
+hipError_t launch_path_pool(const SceneView &sc, const FrameParams &fp, int bvh_depth, const TracerChoice &choice, const uint32_t t_class[3], const Tuning &tune,
                             PoolScratch &scratch, unsigned int *sample_counter, void *samples, unsigned int *status, int num_cus,
-                            hipStream_t stream, const char **kernel_name, int *launch_shape) {
+                            hipStream_t stream, LaunchShape *shape) {
     if (fp.width == 0 || fp.local_rows == 0 || fp.n_frames == 0) return hipSuccess;
+    const int flags = choice.pool_flags;           // (+ 32 below when the stacks' upper levels go to HBM)
+    const bool hbm_scene = (flags & 8) != 0, material_model = (flags & 16) != 0;
     const int env_threads = tune.threads, env_paths = tune.paths, env_fill = tune.min_fill, env_patience = tune.patience;
     const uint32_t tiles_x = (fp.width + 7) / 8, tiles_y = (fp.local_rows + 7) / 8;
     const uint64_t n_chunks = (uint64_t)tiles_x * tiles_y * fp.n_frames;
@@ -1206,13 +1189,12 @@ hipError_t launch_path_pool(const SceneView &sc, const FrameParams &fp, int bvh_
     // entries: 2.56 ms with all 9 levels in LDS, 2.66 with 8 and 1280 paths.)
     // (tools/experiments/r03/sweep_stack_lds.sh, room_two_pools.sh)
     const uint32_t n_rings = fp.enable_sunlight ? (uint32_t)kNQ : (uint32_t)kNQ - 1u;
-    const uint32_t stats_bytes = (tune.stats || fp.counters) ? kStatsBytes : 0u;         // (the statistics build keeps its per-queue sums in LDS)
+    const uint32_t stats_bytes = (flags & 1) ? kStatsBytes : 0u;         // (the statistics build keeps its per-queue sums in LDS)
     auto lds_for = [&](uint32_t paths, uint32_t &cap, uint32_t levels) {
         cap = 64;
         while (cap < paths) cap *= 2;
         return pool_layout(paths, cap, levels, scene_bytes, cold_bytes, n_rings, word_bytes, stack_entry_bytes, stats_bytes).total;
     };
-    const int flags = ((tune.stats || fp.counters) ? 1 : 0) | (fp.enable_sunlight ? 2 : 0) | (scene_has_alpha ? 4 : 0) | (hbm_scene ? 8 : 0);
     const int max_threads = pool_max_threads(flags);
     auto threads_for = [&](uint32_t paths, int g) {
         // hbm-scene: every step waits for L2, so all the waves a workgroup can have (even a few more lanes than paths: measured on cs16_dust)
@@ -1242,7 +1224,7 @@ hipError_t launch_path_pool(const SceneView &sc, const FrameParams &fp, int bvh_
             stack_lds = best_levels;
         };
         best_shape();
-        // path_pool_supports sizes its smallest pool without the staged shading records: a small scene under a very deep tree may
+        // path_pool_fits sizes its smallest pool without the staged shading records: a small scene under a very deep tree may
         // leave no room for them -- the records then stay in global memory rather than the launch failing
         if (P == 0 && cold_bytes > 0) { cold_bytes = 0; best_shape(); }
         if (P == 0) return hipErrorInvalidValue;
@@ -1251,26 +1233,9 @@ hipError_t launch_path_pool(const SceneView &sc, const FrameParams &fp, int bvh_
     const PoolLayout lay = pool_layout(P, ring_cap, stack_lds, scene_bytes, cold_bytes, n_rings, word_bytes, stack_entry_bytes, stats_bytes);
     if (lay.total > 160u * 1024u) return hipErrorInvalidValue;
     const int threads = env_threads > 0 ? std::max(64, std::min(env_threads, max_threads) / 64 * 64) : threads_for(P, groups);
-    typedef void (*PoolKernel)(const PoolArgs);
-    static const PoolKernel kernels[32] = { path_pool_kernel<0>, path_pool_kernel<1>, path_pool_kernel<2>, path_pool_kernel<3>,
-                                            path_pool_kernel<4>, path_pool_kernel<5>, path_pool_kernel<6>, path_pool_kernel<7>,
-                                            path_pool_kernel<8>, path_pool_kernel<9>, path_pool_kernel<10>, path_pool_kernel<11>,
-                                            path_pool_kernel<12>, path_pool_kernel<13>, path_pool_kernel<14>, path_pool_kernel<15>,
-                                            // (deep trees: the stacks' upper levels in HBM)
-                                            path_pool_kernel<32>, path_pool_kernel<33>, path_pool_kernel<34>, path_pool_kernel<35>,
-                                            path_pool_kernel<36>, path_pool_kernel<37>, path_pool_kernel<38>, path_pool_kernel<39>,
-                                            path_pool_kernel<40>, path_pool_kernel<41>, path_pool_kernel<42>, path_pool_kernel<43>,
-                                            path_pool_kernel<44>, path_pool_kernel<45>, path_pool_kernel<46>, path_pool_kernel<47> };
-    static const char *const names[16] = { "path_pool<lean,lds-scene>", "path_pool<lean+sun,lds-scene>", "path_pool<lean+alpha,lds-scene>",
-                                           "path_pool<lean+alpha+sun,lds-scene>", "path_pool<lean,hbm-scene>", "path_pool<lean+sun,hbm-scene>",
-                                           "path_pool<lean+alpha,hbm-scene>", "path_pool<lean+alpha+sun,hbm-scene>",
-                                           "path_pool<materials,lds-scene>", "path_pool<materials+sun,lds-scene>", "path_pool<materials+alpha,lds-scene>",
-                                           "path_pool<materials+alpha+sun,lds-scene>", "path_pool<materials,hbm-scene>", "path_pool<materials+sun,hbm-scene>",
-                                           "path_pool<materials+alpha,hbm-scene>", "path_pool<materials+alpha+sun,hbm-scene>" };
-    const bool material_model = fp.ext_emissive || fp.ext_specular || fp.ext_transmission;
-    // (the material-model variants live in a translation unit of their own, kernel_path_pool_ext.o: no statistics builds of them)
-    const bool deep = stack_lds < stack_entries;
-    const void *const kernel = material_model ? path_pool_ext_kernel((flags & ~1) | (deep ? 32 : 0)) : reinterpret_cast<const void *>(kernels[flags + (deep ? 16 : 0)]);
+    const int build = flags | (stack_lds < stack_entries ? 32 : 0);
+    const void *const kernel = material_model ? path_pool_ext_kernel(build) : pool_kernel(build, PoolBuilds{});
+    if (!kernel) return hipErrorInvalidValue;
     if (lay.total > 64u * 1024u) {
         hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lay.total);
         if (e != hipSuccess) return e;
@@ -1335,8 +1300,7 @@ hipError_t launch_path_pool(const SceneView &sc, const FrameParams &fp, int bvh_
     pp.aux_light = static_cast<float4 *>(scratch.aux_light);
     pp.aux_next = static_cast<float4 *>(scratch.aux_next);
     hipError_t e = hipSuccess;                 // (sample_counter: kPoolSampleShards zeroed counters, kPoolSampleShardStride words apart -- drt_capi.cpp hands out zeroed blocks)
-    if (kernel_name) *kernel_name = names[(flags >> 1) + (material_model ? 8 : 0)];
-    if (launch_shape) { launch_shape[0] = (int)(stack_entries | (stack_lds << 8)); launch_shape[1] = per_cu; launch_shape[2] = (int)(lay.total / 1024); launch_shape[3] = threads; launch_shape[4] = (int)P; }
+    *shape = LaunchShape{ (int)stack_entries, (int)stack_lds, per_cu, (int)(lay.total / 1024), threads, (int)P, (int)stack_entry_bytes, 2 };
     FrameParams fq = fp;
     fq.inline_resolve = fp.n_frames == 1 ? 1 : 0;
     PoolArgs args;

@@ -727,7 +727,7 @@ int groups_per_cu(int threads, size_t lds) {
 
 template <int MODE, bool LDS_SCENE, bool REF16, int TRIS = 2>
 hipError_t launch_config(const SceneView &sc, const FrameParams &fp, unsigned int *chunk_counter, float4 *samples, uint32_t stack_entries,
-                         size_t lds_bytes, int threads, int per_cu, int num_cus, hipStream_t stream) {
+                         size_t lds_bytes, int threads, int per_cu, int chunks_per_wg, int num_cus, hipStream_t stream) {
     const uint32_t tiles_x = (fp.width + 7) / 8, tiles_y = (fp.local_rows + 7) / 8;
     auto kernel = wave_queue_kernel<MODE, LDS_SCENE, REF16, TRIS>;
     const int waves_per_wg = threads / 64;
@@ -746,10 +746,9 @@ hipError_t launch_config(const SceneView &sc, const FrameParams &fp, unsigned in
     // A launch that has the GPU to itself wants every slot it can fill: one chunk per wave.
     // (the grid never drops below this launch's fair share of the GPU, slots / frames in flight: tiny launches must not
     // leave the machine empty)
-    static const uint64_t chunks_per_wg_env = std::getenv("DRT_CHUNKS_PER_WG") ? (uint64_t)std::max(1, std::atoi(std::getenv("DRT_CHUNKS_PER_WG"))) : 0;
     const uint64_t slots = (uint64_t)num_cus * per_cu;
     uint64_t want = std::min<uint64_t>(slots, (n_chunks + waves_per_wg - 1) / waves_per_wg);      // at least one chunk per wave
-    if (chunks_per_wg_env) want = std::min<uint64_t>(want, (n_chunks + chunks_per_wg_env - 1) / chunks_per_wg_env);
+    if (chunks_per_wg) want = std::min<uint64_t>(want, (n_chunks + chunks_per_wg - 1) / (uint64_t)chunks_per_wg);
     else if (fp.frames_in_flight > 1)
         want = std::min<uint64_t>(want, std::max<uint64_t>((n_chunks + 16 * waves_per_wg - 1) / (16 * waves_per_wg), slots / (uint64_t)fp.frames_in_flight));
     const int blocks = (int)std::max<uint64_t>(1, want);
@@ -771,28 +770,23 @@ hipError_t launch_config(const SceneView &sc, const FrameParams &fp, unsigned in
 // Round 1 chose among them by rules fitted to four views (camera inside the scene's bounds or not); what used to be the rule
 // is now only the order in which the candidates are tried.
 template <int MODE, bool LDS_SCENE>
-std::vector<WqVariant> wave_queue_candidates(const SceneView &sc, uint32_t stack_entries, size_t scene_lds_bytes, bool camera_inside) {
+std::vector<WqVariant> wave_queue_candidates(const SceneView &sc, uint32_t stack_entries, size_t scene_lds_bytes, bool camera_inside, const Tuning &tune) {
     constexpr bool kLean = MODE == 0 || MODE == 3 || MODE == 4 || MODE == 5;
-    static const bool only_small = std::getenv("DRT_WG_THREADS") && std::atoi(std::getenv("DRT_WG_THREADS")) == kThreads;      // A/B switches
-    static const bool only_wide = std::getenv("DRT_STACK_REF16") && std::atoi(std::getenv("DRT_STACK_REF16")) == 0;
-    static const bool wide_allowed = !(std::getenv("DRT_TRIS_WIDE") && std::atoi(std::getenv("DRT_TRIS_WIDE")) == 0);
     std::vector<WqVariant> out;
     auto add = [&](int threads, int entry, int tris, int per_cu) {
-        if (per_cu < 1) return;
-        if (const char *cap = std::getenv("DRT_MAX_BLOCKS_PER_CU")) per_cu = std::max(1, std::min(per_cu, std::atoi(cap)));
-        out.push_back(WqVariant{ threads, entry, tris, per_cu });
+        if (per_cu >= 1) out.push_back(WqVariant{ threads, entry, tris, std::max(1, std::min(per_cu, tune.max_blocks_per_cu)) });
     };
     const int plain = groups_per_cu<MODE, LDS_SCENE, false>(kThreads, (size_t)stack_entries * kThreads * 8 + scene_lds_bytes);
     add(kThreads, 8, 2, plain);
-    if (LDS_SCENE && scene_lds_bytes >= 4096 && !only_small) {
+    if (LDS_SCENE && scene_lds_bytes >= 4096 && !tune.wq_only_small) {
         const int n = groups_per_cu<MODE, LDS_SCENE, false>(kBigThreads, (size_t)stack_entries * kBigThreads * 8 + scene_lds_bytes);
         if (n * kBigThreads > plain * kThreads) add(kBigThreads, 8, 2, n);                 // only when it keeps more waves resident
     }
-    if (kLean && !LDS_SCENE && !only_wide && sc.n_inner < 0x8000u && sc.n_leaves < 0x8000u) {
+    if (kLean && !LDS_SCENE && !tune.wq_only_wide && sc.n_inner < 0x8000u && sc.n_leaves < 0x8000u) {
         const int n = groups_per_cu<MODE, LDS_SCENE, kLean && !LDS_SCENE>(kThreads, (size_t)stack_entries * kThreads * 6 + scene_lds_bytes);
         if (n > plain) add(kThreads, 6, 2, n);
     }
-    if (MODE == 0 && !LDS_SCENE && wide_allowed)
+    if (MODE == 0 && !LDS_SCENE && tune.wq_tris_wide)
         add(kThreads, 8, 3, groups_per_cu<MODE, LDS_SCENE, false, (MODE == 0 && !LDS_SCENE) ? 3 : 2>(kThreads, (size_t)stack_entries * kThreads * 8 + scene_lds_bytes));
     if (out.empty()) out.push_back(WqVariant{ kThreads, 8, 2, 1 });
     // the order of the trials = round 1's rules: from inside, more waves first; from outside (sky around), more loads in flight first
@@ -803,41 +797,22 @@ std::vector<WqVariant> wave_queue_candidates(const SceneView &sc, uint32_t stack
 }
 
 template <int MODE, bool LDS_SCENE>
-hipError_t launch_one(const SceneView &sc, const FrameParams &fp, unsigned int *chunk_counter, float4 *samples,
-                      uint32_t stack_entries, size_t scene_lds_bytes, int num_cus, hipStream_t stream, int *launch_shape, WaveQueueCache &cache) {
+hipError_t launch_one(const SceneView &sc, const FrameParams &fp, unsigned int *chunk_counter, float4 *samples, uint32_t stack_entries,
+                      size_t scene_lds_bytes, const Tuning &tune, int num_cus, hipStream_t stream, LaunchShape *shape, WaveQueueCache &cache) {
     constexpr bool kLean = MODE == 0 || MODE == 3 || MODE == 4 || MODE == 5;
     bool camera_inside = true;
     for (int k = 0; k < 3; k++) camera_inside = camera_inside && fp.cam_pos[k] >= sc.root_min[k] && fp.cam_pos[k] <= sc.root_max[k];
     // one plan per (kernel, scene shape, view class)
     const uint64_t key = ((((uint64_t)scene_lds_bytes * 131u + stack_entries) * 131u + sc.n_tris) * 16u + (uint64_t)MODE * 2u + (LDS_SCENE ? 1u : 0u)) * 2u + (camera_inside ? 1u : 0u);
     const WqVariant v = measured_choice(cache, key, (double)fp.width * fp.local_rows * fp.n_frames,
-                                        [&] { return wave_queue_candidates<MODE, LDS_SCENE>(sc, stack_entries, scene_lds_bytes, camera_inside); });
+                                        [&] { return wave_queue_candidates<MODE, LDS_SCENE>(sc, stack_entries, scene_lds_bytes, camera_inside, tune); });
     const size_t lds_bytes = (size_t)stack_entries * v.threads * v.entry_bytes + scene_lds_bytes;
-    if (launch_shape) { launch_shape[0] = (int)stack_entries; launch_shape[1] = v.per_cu; launch_shape[2] = (int)(lds_bytes / 1024); launch_shape[3] = v.threads + (v.entry_bytes == 6 ? 1 : 0) + (v.tris == 3 ? 2 : 0); }
+    *shape = LaunchShape{ (int)stack_entries, (int)stack_entries, v.per_cu, (int)(lds_bytes / 1024), v.threads, 0, v.entry_bytes, v.tris };
     if (v.tris == 3)
-        return launch_config<MODE, LDS_SCENE, false, (MODE == 0 && !LDS_SCENE) ? 3 : 2>(sc, fp, chunk_counter, samples, stack_entries, lds_bytes, v.threads, v.per_cu, num_cus, stream);
+        return launch_config<MODE, LDS_SCENE, false, (MODE == 0 && !LDS_SCENE) ? 3 : 2>(sc, fp, chunk_counter, samples, stack_entries, lds_bytes, v.threads, v.per_cu, tune.chunks_per_wg, num_cus, stream);
     if (v.entry_bytes == 6)
-        return launch_config<MODE, LDS_SCENE, kLean && !LDS_SCENE>(sc, fp, chunk_counter, samples, stack_entries, lds_bytes, v.threads, v.per_cu, num_cus, stream);
-    return launch_config<MODE, LDS_SCENE, false>(sc, fp, chunk_counter, samples, stack_entries, lds_bytes, v.threads, v.per_cu, num_cus, stream);
-}
-
-hipError_t launch_mode(const SceneView &sc, const FrameParams &fp, int mode, bool lds_scene, unsigned int *chunk_counter,
-                       float4 *samples, uint32_t stack_entries, size_t scene_lds_bytes, int num_cus, hipStream_t stream, int *launch_shape,
-                       WaveQueueCache &cache) {
-    if (lds_scene) {
-        if (mode == 0) return launch_one<0, true>(sc, fp, chunk_counter, samples, stack_entries, scene_lds_bytes, num_cus, stream, launch_shape, cache);
-        if (mode == 1) return launch_one<1, true>(sc, fp, chunk_counter, samples, stack_entries, scene_lds_bytes, num_cus, stream, launch_shape, cache);
-        if (mode == 3) return launch_one<3, true>(sc, fp, chunk_counter, samples, stack_entries, scene_lds_bytes, num_cus, stream, launch_shape, cache);
-        if (mode == 4) return launch_one<4, true>(sc, fp, chunk_counter, samples, stack_entries, scene_lds_bytes, num_cus, stream, launch_shape, cache);
-        if (mode == 5) return launch_one<5, true>(sc, fp, chunk_counter, samples, stack_entries, scene_lds_bytes, num_cus, stream, launch_shape, cache);
-        return launch_one<2, true>(sc, fp, chunk_counter, samples, stack_entries, scene_lds_bytes, num_cus, stream, launch_shape, cache);
-    }
-    if (mode == 0) return launch_one<0, false>(sc, fp, chunk_counter, samples, stack_entries, scene_lds_bytes, num_cus, stream, launch_shape, cache);
-    if (mode == 1) return launch_one<1, false>(sc, fp, chunk_counter, samples, stack_entries, scene_lds_bytes, num_cus, stream, launch_shape, cache);
-    if (mode == 3) return launch_one<3, false>(sc, fp, chunk_counter, samples, stack_entries, scene_lds_bytes, num_cus, stream, launch_shape, cache);
-    if (mode == 4) return launch_one<4, false>(sc, fp, chunk_counter, samples, stack_entries, scene_lds_bytes, num_cus, stream, launch_shape, cache);
-    if (mode == 5) return launch_one<5, false>(sc, fp, chunk_counter, samples, stack_entries, scene_lds_bytes, num_cus, stream, launch_shape, cache);
-    return launch_one<2, false>(sc, fp, chunk_counter, samples, stack_entries, scene_lds_bytes, num_cus, stream, launch_shape, cache);
+        return launch_config<MODE, LDS_SCENE, kLean && !LDS_SCENE>(sc, fp, chunk_counter, samples, stack_entries, lds_bytes, v.threads, v.per_cu, tune.chunks_per_wg, num_cus, stream);
+    return launch_config<MODE, LDS_SCENE, false>(sc, fp, chunk_counter, samples, stack_entries, lds_bytes, v.threads, v.per_cu, tune.chunks_per_wg, num_cus, stream);
 }
 
 }  // namespace
@@ -916,31 +891,21 @@ void wave_queue_report(WaveQueueCache &cache, float span_ms) {
     }
 }
 
-hipError_t launch_wave_queue(const SceneView &sc, const FrameParams &fp, int bvh_depth, int mode, bool scene_has_alpha,
-                             unsigned int *chunk_counter, void *samples, int num_cus, hipStream_t stream, const char **kernel_name,
-                             int *launch_shape, WaveQueueCache &cache) {
+hipError_t launch_wave_queue(const SceneView &sc, const FrameParams &fp, int bvh_depth, const TracerChoice &choice, const Tuning &tune,
+                             unsigned int *chunk_counter, void *samples, int num_cus, hipStream_t stream, LaunchShape *shape, WaveQueueCache &cache) {
     if (fp.width == 0 || fp.local_rows == 0 || fp.n_frames == 0) return hipSuccess;
-    if (mode == 0 && fp.render_mode != 0) mode = 1;                                    // debug views: the general kernel
-    if (mode == 0) mode = fp.enable_sunlight ? (scene_has_alpha ? 5 : 4) : (scene_has_alpha ? 3 : 0);
     // one slot per BVH level is all a depth-first walk that pushes both children can ever hold (BVHTraversal.cuh:20
     // fixes it at 64, which is also the reference's limit)
-    if (bvh_depth > 64) return hipErrorInvalidValue;
-    const int stack = std::max(bvh_depth, 1);
-    const size_t scene_bytes = wave_queue_scene_lds_bytes(sc);
-    static const size_t lds_scene_budget = std::getenv("DRT_LDS_SCENE_KB") ? (size_t)std::atoi(std::getenv("DRT_LDS_SCENE_KB")) * 1024 : kLdsSceneBytes;
-    // (a small scene under a degenerate, very deep tree: the stacks of one 256-thread group and the scene copy must fit the
-    // CU's 160 KB together, else the tree is read from HBM and the stacks have the LDS to themselves)
-    const bool lds_scene = scene_bytes <= lds_scene_budget && scene_bytes + (size_t)stack * kThreads * sizeof(StackEntry) <= 160u * 1024u;
-    hipError_t e = hipSuccess;                 // (*chunk_counter is zero: drt_capi.cpp hands out zeroed counters)
-    static const char *names[2][6] = { { "wave_queue<lean,hbm-scene>", "wave_queue<general,hbm-scene>", "wave_queue<counting,hbm-scene>", "wave_queue<lean+alpha,hbm-scene>",
-                                         "wave_queue<lean+sun,hbm-scene>", "wave_queue<lean+alpha+sun,hbm-scene>" },
-                                       { "wave_queue<lean,lds-scene>", "wave_queue<general,lds-scene>", "wave_queue<counting,lds-scene>", "wave_queue<lean+alpha,lds-scene>",
-                                         "wave_queue<lean+sun,lds-scene>", "wave_queue<lean+alpha+sun,lds-scene>" } };
-    if (kernel_name) *kernel_name = names[lds_scene ? 1 : 0][mode];
-    float4 *s4 = static_cast<float4 *>(samples);
+    if (bvh_depth > 64 || choice.wq_mode < 0 || choice.wq_mode > 5) return hipErrorInvalidValue;
+    typedef hipError_t (*LaunchOne)(const SceneView &, const FrameParams &, unsigned int *, float4 *, uint32_t, size_t, const Tuning &, int, hipStream_t,
+                                    LaunchShape *, WaveQueueCache &);
+    static const LaunchOne builds[2][6] = { { launch_one<0, false>, launch_one<1, false>, launch_one<2, false>, launch_one<3, false>, launch_one<4, false>, launch_one<5, false> },
+                                            { launch_one<0, true>, launch_one<1, true>, launch_one<2, true>, launch_one<3, true>, launch_one<4, true>, launch_one<5, true> } };
+    // (*chunk_counter is zero: drt_capi.cpp hands out zeroed counters)
     // (the one-frame shortcut of path_pool -- accumulate and resolve inside the tracing kernel -- costs this kernel a register
     // too many: its 6-byte-stack variants go from 80 to 81 VGPRs = 6 -> 5 waves per SIMD)
-    e = launch_mode(sc, fp, mode, lds_scene, chunk_counter, s4, (uint32_t)stack, lds_scene ? scene_bytes : 0, num_cus, stream, launch_shape, cache);
+    const hipError_t e = builds[choice.wq_lds_scene ? 1 : 0][choice.wq_mode](sc, fp, chunk_counter, static_cast<float4 *>(samples), (uint32_t)std::max(bvh_depth, 1),
+                                                                             choice.wq_lds_scene ? wave_queue_scene_lds_bytes(sc) : 0, tune, num_cus, stream, shape, cache);
     if (e != hipSuccess) return e;
     return launch_resolve(fp, samples, stream);
 }

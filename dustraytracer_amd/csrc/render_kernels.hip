@@ -322,19 +322,19 @@ hipError_t launch_stack(const SceneView &sc, const FrameParams &fp, bool count, 
 
 #ifdef DRT_WITH_PIXEL_WALK
 bool pixel_walk_built_in() { return true; }
-hipError_t launch_render(const SceneView &sc, const FrameParams &fp, int bvh_depth, bool count, hipStream_t stream,
-                         const char **kernel_name) {
+hipError_t launch_render(const SceneView &sc, const FrameParams &fp, const TracerChoice &choice, bool count, hipStream_t stream) {
     if (fp.width == 0 || fp.local_rows == 0 || fp.n_frames == 0) return hipSuccess;
-    // the stack never holds more than `depth` entries (one per level below the root, plus the root itself)
-    if (bvh_depth <= 8)  { if (kernel_name) *kernel_name = "pixel_walk<stack8>";  return launch_stack<8>(sc, fp, count, stream); }
-    if (bvh_depth <= 16) { if (kernel_name) *kernel_name = "pixel_walk<stack16>"; return launch_stack<16>(sc, fp, count, stream); }
-    if (bvh_depth <= 32) { if (kernel_name) *kernel_name = "pixel_walk<stack32>"; return launch_stack<32>(sc, fp, count, stream); }
-    if (bvh_depth <= 64) { if (kernel_name) *kernel_name = "pixel_walk<stack64>"; return launch_stack<64>(sc, fp, count, stream); }
+    switch (choice.stack) {
+    case 8: return launch_stack<8>(sc, fp, count, stream);
+    case 16: return launch_stack<16>(sc, fp, count, stream);
+    case 32: return launch_stack<32>(sc, fp, count, stream);
+    case 64: return launch_stack<64>(sc, fp, count, stream);
+    }
     return hipErrorInvalidValue;     // the reference's own stack is 64 deep (BVHTraversal.cuh:17)
 }
 #else
 bool pixel_walk_built_in() { return false; }
-hipError_t launch_render(const SceneView &, const FrameParams &, int, bool, hipStream_t, const char **) { return hipErrorNotSupported; }
+hipError_t launch_render(const SceneView &, const FrameParams &, const TracerChoice &, bool, hipStream_t) { return hipErrorNotSupported; }
 #endif
 
 hipError_t launch_kat(int which, const void *d_in, void *d_out, uint32_t n, const FrameParams &fp, hipStream_t stream) {

@@ -122,6 +122,18 @@ def test_pixel_walk_child():
     r, ref, _ = _render_with_env({"DRT_KERNEL": "pixel_walk"}, "suzanne_plane", 128, 72, 2, 2)
     assert r.kernelInfo().startswith("pixel_walk")
     compare(r.GetRenderTargetImage(), ref, "pixel_walk")
+    # round 1's kernel has no material model: the emissive term goes to wave_queue's general build, the dielectric lobe is refused
+    from tests.test_gpu_parity import make_pair, cameras
+    sc, _ = make_pair("suzanne_plane")
+    cam, _ = cameras("suzanne_plane")
+    r.setMaterialModel(1, 0, 1.0)
+    r.resetAccumulationBuffer()
+    r.RenderBatch(cam, sc, 1)
+    assert r.kernelInfo().startswith("wave_queue<general"), r.kernelInfo()
+    r.setMaterialModel(0, 0, 1.0, 1)
+    with pytest.raises(drt.DrtError) as e:
+        r.RenderBatch(cam, sc, 1)
+    assert e.value.code == drt.ERR_UNSUPPORTED
 
 
 @pytest.mark.parametrize("kernel", ["path_pool", "wave_queue"])

@@ -228,7 +228,8 @@ def test_renderer_state_machine(renderer):
 def test_counters_match_oracle(renderer, scene, kw):
     """drt_counters are counted by the tracing kernel that is measured -- path_pool's statistics build (FLAGS & 1), in every
     variant: scene in LDS / read from global memory, sunlight, alpha cut-outs -- and equal the oracle's counts exactly: SURVEY 8(d)'s
-    algorithmic bytes are a function of them.  The general wave_queue kernel (debug views, the material model) counts the same."""
+    algorithmic bytes are a function of them.  wave_queue's counting build counts the same; it is what counts debug views and the
+    material model, which has no statistics build of path_pool (tests/test_material_model.py)."""
     sc, osc = make_pair(scene)
     cam, ocam = cameras(scene)
     s, o = settings_pair(**kw)

@@ -277,3 +277,61 @@ def test_dielectric_lobe_on_the_production_kernel(model, n_extra):
     rq.setMaterialModel(0, 0, 1.0, 1)
     with pytest.raises(drt.DrtError):
         rq.RenderBatch(cam, sc, 1)
+
+
+_COUNTER_NAMES = ("samples", "rays", "node_visits", "inner_visits", "tri_tests", "hits_textured", "hits_flat", "shadow_rays", "inner_visits_shadow",
+                  "tri_tests_shadow")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n_extra", [0, 3000])
+@pytest.mark.parametrize("model", [(1, 0, 1.0), (0, 1, 1.0)])
+def test_counting_with_the_material_model_runs_the_counting_build(model, n_extra):
+    """path_pool has no statistics build of the material model: with counting on, the emissive term and the mirror lobe go to
+    wave_queue's counting build -- scene in LDS and read from global memory -- whose counters and image equal the oracle's."""
+    sc, osc = _glass_scene(n_extra)
+    pos, fwd = (0.3, 1.6, 2.8), (-0.1, -0.15, -1.0)
+    cam = drt.Camera(pos); cam.m_Forward_dir = np.array(fwd, np.float32)
+    ocam = oracle.default_camera(position=pos, forward=fwd)
+    W, H, frames, depth = 96, 54, 2, 5
+    osc.material_model = model
+    ref, _, cnt = oracle.render(osc, ocam, oracle.default_settings(ray_bounce_limit=depth), W, H, 1, frames, want_counters=True)
+    want = cnt.as_dict()
+    r = drt.Renderer(0)
+    r.m_RendererSettings = drt.RendererSettings(ray_bounce_limit=depth)
+    r.ResizeBuffer(W, H)
+    r.setMaterialModel(*model)
+    r.setCounting(True)
+    r.RenderBatch(cam, sc, frames)
+    got = r.getCounters().as_dict()
+    assert r.kernelInfo().startswith("wave_queue<counting,%s>" % ("hbm-scene" if n_extra else "lds-scene")), r.kernelInfo()
+    img = r.GetRenderTargetImage()
+    assert np.array_equal(bits(img), bits(ref)), "%d pixels differ from the oracle" % int((bits(img) != bits(ref)).any(axis=-1).sum())
+    for k in _COUNTER_NAMES:
+        assert got[k] == want[k], (k, got[k], want[k])
+    # the dielectric lobe has no counting build at all: refused, not counted as zero
+    r.setMaterialModel(0, 0, 1.0, 1)
+    with pytest.raises(drt.DrtError) as e:
+        r.RenderBatch(cam, sc, 1)
+    assert e.value.code == drt.ERR_UNSUPPORTED
+
+
+@pytest.mark.gpu
+def test_pool_statistics_builds_leave_the_material_model_to_its_own_build():
+    """DRT_POOL_STATS=1 with the material model on an hbm-scene: the material-model build runs, sized as itself (it has no statistics
+    build), and renders the oracle's image."""
+    from tests.test_gpu_parity import _renderer_with_env
+    sc, osc = _glass_scene(3000)
+    pos, fwd = (0.3, 1.6, 2.8), (-0.1, -0.15, -1.0)
+    cam = drt.Camera(pos); cam.m_Forward_dir = np.array(fwd, np.float32)
+    W, H, frames, depth, model = 160, 90, 2, 6, (1, 1, 1.5, 1)
+    r = _renderer_with_env({"DRT_POOL_STATS": "1"})
+    r.m_RendererSettings = drt.RendererSettings(ray_bounce_limit=depth)
+    r.ResizeBuffer(W, H)
+    r.setMaterialModel(*model)
+    r.RenderBatch(cam, sc, frames)
+    assert r.kernelInfo().startswith("path_pool<materials,hbm-scene>"), r.kernelInfo()
+    osc.material_model = model
+    ref, _, _ = oracle.render(osc, oracle.default_camera(position=pos, forward=fwd), oracle.default_settings(ray_bounce_limit=depth), W, H, 1, frames)
+    img = r.GetRenderTargetImage()
+    assert np.array_equal(bits(img), bits(ref)), "%d pixels differ from the oracle" % int((bits(img) != bits(ref)).any(axis=-1).sum())
