@@ -152,6 +152,17 @@ class _TexInfo(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("components", C.c_int32)]
 
 
+class DenoiseParams(C.Structure):
+    """include/drt.h drt_denoise_params: a-trous passes and the three edge-stopping sigmas (defaults 5, 0.5, 0.1, 0.1)."""
+    _fields_ = [("iterations", C.c_int32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        _lib.drt_default_denoise_params(C.byref(self))
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("samples", "rays", "node_visits", "inner_visits", "tri_tests",
                                            "hits_textured", "hits_flat", "shadow_rays", "inner_visits_shadow",
@@ -261,6 +272,11 @@ _sig("drt_debug_check_rcp", C.c_int, C.c_int32, C.POINTER(C.c_uint64), C.POINTER
 _sig("drt_debug_check_sqrt", C.c_int, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
 _sig("drt_renderer_trace_rays", C.c_int, _P, _P, _P, _P, C.c_uint32, _P)
 _sig("drt_renderer_occluded", C.c_int, _P, _P, _P, _P, C.c_uint32, _P)
+_sig("drt_renderer_render_guides", C.c_int, _P, C.POINTER(_CameraPOD), _P, C.c_uint32, _P, _P)
+_sig("drt_default_denoise_params", None, C.POINTER(DenoiseParams))
+_sig("drt_renderer_denoise", C.c_int, _P, C.POINTER(_CameraPOD), _P, C.POINTER(DenoiseParams), C.POINTER(C.c_float))
+_sig("drt_renderer_read_denoised_rgba32f", C.c_int, _P, _P, C.c_size_t)
+_sig("drt_renderer_device_denoised", _P, _P)
 
 EXPORTED_SYMBOLS = [n for n in dir(_lib) if n.startswith("drt_")]
 
@@ -471,6 +487,7 @@ class RendererGroup:
 
 FLT_MAX = float(np.finfo(np.float32).max)
 RayHits = collections.namedtuple("RayHits", "t prim u v")     # closest-hit query results (Renderer.traceRays)
+Guides = collections.namedtuple("Guides", "albedo normal t prim")  # first-hit guide buffers (Renderer.renderGuides)
 
 
 def _ray_batch(torch, dev, origins, directions, tmin, tmax):
@@ -546,6 +563,7 @@ class Renderer:
             raise DrtError(ERR_DEVICE, (_lib.drt_last_error() or b"").decode())
         self._device = device
         self.m_RendererSettings = RendererSettings()
+        self.m_LastDenoiseMs = 0.0               # device time of the last Denoise (guides + filter)
 
     def _ray_query(self, scene, origins, directions, tmin, tmax, occluded):
         import torch                             # (only here: importing the package does not import torch)
@@ -583,6 +601,44 @@ class Renderer:
         if directions is None and tmin == 0.0 and tmax == float("inf"):
             tmin = tmax = None
         return self._ray_query(scene, origins, directions, tmin, tmax, True)
+
+    def renderGuides(self, cam, scene, frame_index=1, as_torch=False):
+        """First-hit guide buffers of frame `frame_index` (drt_renderer_render_guides): Guides(albedo [H, W, 3], normal [H, W, 3],
+        t [H, W], prim [H, W] int32), row 0 = bottom.  as_torch=True: device tensors, the work enqueued on the current torch stream;
+        else numpy arrays."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        self._push_settings()                    # (the sky colour and intensity of a miss come from the settings)
+        g = torch.empty((self.getBufferHeight(), self.getBufferWidth(), 8), dtype=torch.float32, device=dev)
+        pod = cam._pod()
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _check(_lib.drt_renderer_render_guides(self._h, C.byref(pod), scene._h, int(frame_index), g.data_ptr(), stream))
+        if not as_torch:
+            h = g.cpu().numpy()
+            return Guides(h[..., 0:3].copy(), h[..., 4:7].copy(), h[..., 3].copy(), h.view(np.int32)[..., 7].copy())
+        return Guides(g[..., 0:3], g[..., 4:7], g[..., 3], g.view(torch.int32)[..., 7])
+
+    def Denoise(self, cam, scene, iterations=5, sigma_color=0.5, sigma_normal=0.1, sigma_albedo=0.1):
+        """Edge-avoiding a-trous filter of the current framebuffer, guided by frame 1's albedo and normal (drt_renderer_denoise):
+        float32 [H, W, 4], row 0 = bottom.  The framebuffer and the accumulation are left as they are."""
+        self._push_settings()
+        p = DenoiseParams(iterations=int(iterations), sigma_color=float(sigma_color), sigma_normal=float(sigma_normal),
+                          sigma_albedo=float(sigma_albedo))
+        ms = C.c_float(0)
+        pod = cam._pod()
+        _check(_lib.drt_renderer_denoise(self._h, C.byref(pod), scene._h, C.byref(p), C.byref(ms)))
+        self.m_LastDenoiseMs = ms.value
+        return self.GetDenoisedImage()
+
+    def GetDenoisedImage(self):
+        """The last Denoise result as numpy float32 [H, W, 4] (drt_renderer_read_denoised_rgba32f)."""
+        out = np.zeros((self.getBufferHeight(), self.getBufferWidth(), 4), np.float32)
+        _check(_lib.drt_renderer_read_denoised_rgba32f(self._h, out.ctypes.data, out.size))
+        return out
+
+    def DeviceDenoisedTarget(self):
+        """Device address of the last Denoise result (float4 [H * W]), None before the first Denoise."""
+        return _lib.drt_renderer_device_denoised(self._h)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None

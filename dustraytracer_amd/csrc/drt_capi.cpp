@@ -19,6 +19,7 @@
 #include "device_scene.hpp"
 #include "render_kernels.hpp"
 #include "ray_query.hpp"
+#include "denoise.hpp"
 #include "scene_host.hpp"
 #include "bvh_build_device.hpp"
 #include "png_decode.hpp"
@@ -142,6 +143,12 @@ struct drt_renderer {
     void *rq_stack = nullptr;
     size_t rq_stack_bytes = 0;
     int rq_refill_min = 16;                    // DRT_RQ_REFILL: idle lanes that make a wave claim new rays (64 = only when all are)
+    // drt_renderer_denoise: frame 1's guides and the two float4 buffers the passes ping-pong between, allocated by the first call,
+    // freed by resize; denoised = the one that holds the last result (-1: none yet)
+    void *dn_guides = nullptr;
+    float4 *dn_buf[2] = { nullptr, nullptr };
+    int denoised = -1;
+    hipEvent_t ev_dn_start = nullptr, ev_dn_stop = nullptr;
 
     float *cur_accum() const { return ext_accum ? ext_accum : accum; }
     float *cur_rgba() const { return ext_rgba ? ext_rgba : rgba; }
@@ -149,6 +156,12 @@ struct drt_renderer {
         d_inner.release(); d_leaves.release(); d_hot.release(); d_cold.release();
         d_mats.release(); d_mats_ext.release(); d_texs.release(); d_texels.release();
         uploaded_scene = nullptr;
+    }
+    void free_denoise() {
+        if (dn_guides) (void)hipFree(dn_guides);
+        for (float4 *&b : dn_buf) { if (b) (void)hipFree(b); b = nullptr; }
+        dn_guides = nullptr;
+        denoised = -1;
     }
 };
 
@@ -336,6 +349,7 @@ static int realloc_buffers(drt_renderer *r) {
     HIP_TRY(hipSetDevice(r->device));
     if (r->accum) { (void)hipFree(r->accum); r->accum = nullptr; }
     if (r->rgba) { (void)hipFree(r->rgba); r->rgba = nullptr; }
+    r->free_denoise();
     r->local_rows = drt_shard_rows(r->height, r->stripe_rows, r->rank, r->world);
     size_t px = std::max<size_t>((size_t)r->width * r->local_rows, 1);
     HIP_TRY(hipMalloc((void **)&r->accum, px * 3 * sizeof(float)));
@@ -431,6 +445,9 @@ void drt_renderer_destroy(drt_renderer *r) {
     if (r->rq_heads) (void)hipFree(r->rq_heads);
     if (r->rq_stack) (void)hipFree(r->rq_stack);
     if (r->ev_query) (void)hipEventDestroy(r->ev_query);
+    r->free_denoise();
+    if (r->ev_dn_start) (void)hipEventDestroy(r->ev_dn_start);
+    if (r->ev_dn_stop) (void)hipEventDestroy(r->ev_dn_stop);
     if (r->ev_start) (void)hipEventDestroy(r->ev_start);
     if (r->ev_stop) (void)hipEventDestroy(r->ev_stop);
     delete r;
@@ -895,6 +912,116 @@ int drt_renderer_occluded(drt_renderer *r, const drt_scene *scene, const drt_ray
     return ray_query_impl(r, scene, rays, occluded, n, hip_stream, true);
 }
 
+// ------------------------------------------------------------------ guide buffers and the a-trous denoiser (kernel_denoise.hip)
+static bool on_renderer_device(const drt_renderer *r, const void *p) {
+    hipPointerAttribute_t at;
+    std::memset(&at, 0, sizeof at);
+    const hipError_t e = hipPointerGetAttributes(&at, p);
+    (void)hipGetLastError();
+    return e == hipSuccess && (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged) && at.device == r->device;
+}
+
+// The guide pass on stream `s`, ordered with the ray queries (it shares their HBM stack); the caller has checked the arguments.
+static int enqueue_guides(drt_renderer *r, const drt_camera *cam, const drt_scene *scene, uint32_t frame_index, void *guides, hipStream_t s) {
+    if (r->world > 1) return fail(DRT_ERR_UNSUPPORTED, "guides and the denoiser need the whole frame: a sharded renderer (world > 1) holds only its stripes");
+    int rc = upload_scene(r, scene);
+    if (rc != DRT_OK) return rc;
+    if (r->bvh_depth > 64) return fail(DRT_ERR_UNSUPPORTED, "BVH deeper than 64 levels (the reference's traversal stack, BVHTraversal.cuh:17)");
+    if (r->query_recorded && r->query_stream != s) HIP_TRY(hipStreamWaitEvent(s, r->ev_query, 0));
+    const size_t stack_bytes = ray_query_stack_bytes(r->num_cus, r->bvh_depth, false);
+    if (stack_bytes > r->rq_stack_bytes) {
+        if (r->query_recorded) HIP_TRY(hipEventSynchronize(r->ev_query));
+        if (r->rq_stack) { (void)hipFree(r->rq_stack); r->rq_stack = nullptr; r->rq_stack_bytes = 0; }
+        HIP_TRY(hipMalloc(&r->rq_stack, stack_bytes));
+        r->rq_stack_bytes = stack_bytes;
+    }
+    FrameParams fp;
+    std::memset(&fp, 0, sizeof fp);
+    fill_frame_params(r, cam, fp);
+    GuideArgs a;
+    a.out = guides;
+    a.frame = frame_index;
+    a.stack_levels = (uint32_t)std::max(1, r->bvh_depth);
+    a.stack_hbm = (uint32_t *)r->rq_stack;
+    HIP_TRY(launch_guides(r->view, fp, a, r->num_cus, s));
+    HIP_TRY(hipEventRecord(r->ev_query, s));
+    r->query_stream = s;
+    r->query_recorded = true;
+    return DRT_OK;
+}
+
+int drt_renderer_render_guides(drt_renderer *r, const drt_camera *cam, const drt_scene *scene, uint32_t frame_index,
+                               drt_guide *guides, void *hip_stream) {
+    if (!r || !cam || !scene || !guides) return fail(DRT_ERR_INVALID, "null argument");
+    if (frame_index == 0) return fail(DRT_ERR_INVALID, "frame indices start at 1");
+    if (r->width == 0 || r->height == 0) return fail(DRT_ERR_INVALID, "ResizeBuffer has not been called");
+    if (((uintptr_t)guides & 15u) != 0) return fail(DRT_ERR_INVALID, "guides must be 16-byte aligned");
+    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
+    HIP_TRY(hipSetDevice(r->device));
+    (void)hipGetLastError();                   // (see render_batch_impl: only this call's own errors count)
+    if (!on_renderer_device(r, guides)) return fail(DRT_ERR_INVALID, "guides must be device memory on the renderer's device");
+    return enqueue_guides(r, cam, scene, frame_index, guides, hip_stream ? (hipStream_t)hip_stream : r->stream);
+}
+
+void drt_default_denoise_params(drt_denoise_params *out) {
+    if (!out) return;
+    out->iterations = 5;
+    out->sigma_color = 0.5f; out->sigma_normal = 0.1f; out->sigma_albedo = 0.1f;
+}
+
+int drt_renderer_denoise(drt_renderer *r, const drt_camera *cam, const drt_scene *scene, const drt_denoise_params *p, float *delta_ms) {
+    if (delta_ms) *delta_ms = 0.f;
+    if (!r || !cam || !scene || !p) return fail(DRT_ERR_INVALID, "null argument");
+    if (p->iterations < 0 || p->iterations > 10) return fail(DRT_ERR_INVALID, "iterations must lie in [0, 10]");
+    for (float sigma : { p->sigma_color, p->sigma_normal, p->sigma_albedo })
+        if (!std::isfinite(sigma) || !(sigma > 0.f)) return fail(DRT_ERR_INVALID, "every sigma must be finite and > 0");
+    if (r->width == 0 || r->height == 0) return fail(DRT_ERR_INVALID, "ResizeBuffer has not been called");
+    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
+    if (r->world > 1) return fail(DRT_ERR_UNSUPPORTED, "the denoiser needs the whole frame: a sharded renderer (world > 1) holds only its stripes");
+    HIP_TRY(hipSetDevice(r->device));
+    (void)hipGetLastError();
+    const size_t px = (size_t)r->width * r->height;
+    if (!r->dn_guides) {
+        HIP_TRY(hipMalloc(&r->dn_guides, px * sizeof(drt_guide)));
+        HIP_TRY(hipMalloc((void **)&r->dn_buf[0], px * sizeof(float4)));
+        HIP_TRY(hipMalloc((void **)&r->dn_buf[1], px * sizeof(float4)));
+    }
+    if (!r->ev_dn_start) HIP_TRY(hipEventCreate(&r->ev_dn_start));
+    if (!r->ev_dn_stop) HIP_TRY(hipEventCreate(&r->ev_dn_stop));
+    r->denoised = -1;
+    HIP_TRY(hipEventRecord(r->ev_dn_start, r->stream));
+    int rc = enqueue_guides(r, cam, scene, 1, r->dn_guides, r->stream);
+    if (rc != DRT_OK) return rc;
+    const float4 *in = reinterpret_cast<const float4 *>(r->cur_rgba());
+    int out = 0;
+    if (p->iterations == 0) {
+        HIP_TRY(hipMemcpyAsync(r->dn_buf[0], in, px * sizeof(float4), hipMemcpyDeviceToDevice, r->stream));
+    } else {
+        const float inv_sc2 = 1.0f / (p->sigma_color * p->sigma_color);
+        for (int i = 0; i < p->iterations; i++, out ^= 1) {
+            AtrousPass ps;
+            ps.in = i == 0 ? in : r->dn_buf[out ^ 1];
+            ps.out = r->dn_buf[out];
+            ps.guides = r->dn_guides;
+            ps.width = r->width; ps.height = r->height; ps.step = 1u << i;
+            ps.k_color = (float)(1 << i) * inv_sc2;
+            ps.k_normal = 1.0f / (p->sigma_normal * p->sigma_normal);
+            ps.k_albedo = 1.0f / (p->sigma_albedo * p->sigma_albedo);
+            HIP_TRY(launch_atrous(ps, r->stream));
+        }
+        out ^= 1;
+    }
+    HIP_TRY(hipEventRecord(r->ev_dn_stop, r->stream));
+    HIP_TRY(hipEventSynchronize(r->ev_dn_stop));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, r->ev_dn_start, r->ev_dn_stop));
+    if (delta_ms) *delta_ms = ms;
+    r->denoised = out;
+    return DRT_OK;
+}
+
+void *drt_renderer_device_denoised(drt_renderer *r) { return r && r->denoised >= 0 ? (void *)r->dn_buf[r->denoised] : nullptr; }
+
 int drt_renderer_render(drt_renderer *r, const drt_camera *cam, const drt_scene *scene, float *delta_ms) {
     return drt_renderer_render_batch(r, cam, scene, 1, delta_ms);
 }
@@ -915,6 +1042,10 @@ int drt_renderer_read_rgba32f(drt_renderer *r, float *dst, size_t dst_floats) {
 }
 int drt_renderer_read_accum(drt_renderer *r, float *dst, size_t dst_floats) {
     return read_back(r, r ? r->cur_accum() : nullptr, 3, dst, dst_floats);
+}
+int drt_renderer_read_denoised_rgba32f(drt_renderer *r, float *dst, size_t dst_floats) {
+    if (r && r->denoised < 0) return fail(DRT_ERR_INVALID, "no denoised image yet: drt_renderer_denoise first");
+    return read_back(r, r ? (const float *)r->dn_buf[r->denoised] : nullptr, 4, dst, dst_floats);
 }
 
 static int debug_check_exact(int32_t device, int which, uint64_t *mismatches, uint64_t *fast_path_count) {

@@ -2,6 +2,7 @@
 // (.png output reproduces the editor's "save png": 8-bit clamp of the GL read-back + vertical flip, EditorLayer.cpp:23-31,85-96)
 //   g++ -std=c++17 -Iinclude examples/drt_render.cpp -Ldustraytracer_amd -ldrt_hip -Wl,-rpath,$PWD/dustraytracer_amd -o drt_render
 //   ./drt_render models/cornell_box.glb out.pfm 1920 1080 8 8  3.6 1.25 0  -1 0 0
+//   ./drt_render models/cornell_box.glb out.png 1920 1080 4 8  3.6 1.25 0  -1 0 0  --denoise     (writes the a-trous denoised frame)
 //   DRT_DEVICES=0,1,2,3,4,5,6,7 ./drt_render models/room.glb out.pfm 3840 2160 64 16  0 1.4 2  0 0 -1     (all GPUs of the node: stripes + RCCL gather)
 #include <DustRayTracer.hpp>
 #include <DustRayTracerGL.hpp>
@@ -16,8 +17,10 @@
 using drtgl::write_png_rgba8;      // the minimal PNG writer lives in DustRayTracerGL.hpp (the editor shim's "save png")
 
 int main(int argc, char **argv) {
+    const bool denoise = argc > 1 && std::strcmp(argv[argc - 1], "--denoise") == 0;     // optional, always last
+    if (denoise) argc--;
     if (argc < 7) {
-        std::fprintf(stderr, "usage: %s scene.glb out.pfm width height spp depth [px py pz fx fy fz]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s scene.glb out.pfm width height spp depth [px py pz fx fy fz] [--denoise]\n", argv[0]);
         return 2;
     }
     try {
@@ -47,6 +50,14 @@ int main(int argc, char **argv) {
         renderer.ReadRenderTarget(rgba.data());
         std::printf("%zu triangles, %u x %u, %u spp on %d GPU%s: %.3f ms (%.1f Msamples/s)\n", scene.trianglesCount(), W, H, spp,
                     renderer.deviceCount(), renderer.deviceCount() > 1 ? "s" : "", ms, (double)W * H * spp / ms / 1e3);
+        if (denoise) {                                    // the a-trous filter of the frame, default parameters (drt_default_denoise_params)
+            drt_denoise_params p;
+            drt_default_denoise_params(&p);
+            float dms = 0;
+            renderer.Denoise(&cam, scene, &dms, p.iterations, p.sigma_color, p.sigma_normal, p.sigma_albedo);
+            renderer.ReadDenoisedTarget(rgba.data());
+            std::printf("denoised: %d passes, %.3f ms\n", p.iterations, dms);
+        }
         const std::string out(argv[2]);
         if (out.size() > 4 && out.compare(out.size() - 4, 4, ".png") == 0) {
             // glGetTexImage(GL_RGBA, GL_UNSIGNED_BYTE) clamps to [0,1] and rounds to 8 bits; stbi_flip_vertically_on_write(true)

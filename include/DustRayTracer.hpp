@@ -281,6 +281,28 @@ public:
     void Occluded(const Scene &scene, const drt_ray *rays, uint8_t *occluded, uint32_t n, void *stream = nullptr) {
         drt::check(drt_renderer_occluded(handle, scene.handle, rays, occluded, n, stream));
     }
+    // First-hit guide buffers of frame `frame_index` (drt_renderer_render_guides): a device drt_guide[width*height], enqueued on `stream`
+    void RenderGuides(Camera *cam, const Scene &scene, uint32_t frame_index, drt_guide *guides, void *stream = nullptr) {
+        drt_settings s = m_RendererSettings.pod();
+        drt_camera c = cam->pod();
+        drt::check(drt_renderer_set_settings(handle, &s));
+        drt::check(drt_renderer_render_guides(handle, &c, scene.handle, frame_index, guides, stream));
+    }
+    // Edge-avoiding a-trous filter of the current frame, guided by frame 1's albedo and normal (drt_renderer_denoise; blocking).
+    // A multi-device renderer is refused (DRT_ERR_UNSUPPORTED): the filter needs the whole frame on one device.
+    void Denoise(Camera *cam, const Scene &scene, float *delta, int iterations = 5, float sigma_color = 0.5f, float sigma_normal = 0.1f,
+                 float sigma_albedo = 0.1f) {
+        drt_denoise_params p = { iterations, sigma_color, sigma_normal, sigma_albedo };
+        drt_settings s = m_RendererSettings.pod();
+        drt_camera c = cam->pod();
+        drt::check(drt_renderer_set_settings(handle, &s));
+        drt::check(drt_renderer_denoise(handle, &c, scene.handle, &p, delta));
+    }
+    // the last Denoise result: RGBA32F, row 0 = bottom, width*height*4 floats (what a "denoise" toggle shows instead of ReadRenderTarget)
+    void ReadDenoisedTarget(float *dst) {
+        drt::check(drt_renderer_read_denoised_rgba32f(handle, dst, (size_t)getBufferWidth() * getBufferHeight() * 4));
+    }
+    void *DeviceDenoisedTarget() { return drt_renderer_device_denoised(handle); }
 
     RendererSettings m_RendererSettings;
     drt_renderer *handle = nullptr;       // the (first) device's renderer

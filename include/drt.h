@@ -26,7 +26,7 @@ extern "C" {
 #endif
 
 /* 2: drt_counters grew by sampler_tries; drt_group_* and drt_material_model entry points (round 2) are part of it; the ray-query
- * entry points (drt_renderer_trace_rays / _occluded) are additions to it */
+ * entry points (drt_renderer_trace_rays / _occluded) and the guide / denoise entry points are additions to it */
 #define DRT_ABI_VERSION 2
 
 typedef enum {
@@ -244,6 +244,38 @@ typedef struct drt_ray { float org[3]; float tmin; float dir[3]; float tmax; } d
 typedef struct drt_hit { float t; int32_t prim; float u, v; } drt_hit;                      /* 16 B */
 int           drt_renderer_trace_rays(drt_renderer *r, const drt_scene *scene, const drt_ray *rays, drt_hit *hits, uint32_t n, void *hip_stream);
 int           drt_renderer_occluded(drt_renderer *r, const drt_scene *scene, const drt_ray *rays, uint8_t *occluded, uint32_t n, void *hip_stream);
+
+/* ---- first-hit guide buffers and the a-trous denoiser (new; the reference's TODO list, RayGen.cuh:13-21, starts with "DLSS 3.5
+ * like features") ----
+ * drt_renderer_render_guides writes one drt_guide per pixel x + y * width (row 0 = bottom, as the framebuffer) for frame
+ * `frame_index` (>= 1): the renderer's primary ray of that pixel and frame (uv = ((float)x / width) * 2 - 1, ((float)y / height)
+ * * 2 - 1, seed = (x + y * width) * frame_index, Camera::GetRay with jitter and defocus), traced as drt_renderer_trace_rays
+ * traces it with tmin 0 and tmax FLT_MAX (TraceRay, bit for bit).  On a hit: albedo = the first hit's material albedo or texel
+ * (the ALBEDO debug view), normal = the face normal turned against the ray (the NORMAL debug view), t and prim as
+ * drt_renderer_trace_rays returns them.  On a miss: albedo = the sky term the ALBEDO debug view shows (settings' sky colour and
+ * intensity), normal = 0, t = FLT_MAX, prim = -1.  A component is stored as the views store it, added to a zeroed sum (-0 reads +0).
+ * `guides` is a 16-byte aligned device pointer on the renderer's device; hip_stream NULL = the renderer's stream; the call only
+ * enqueues, in order with the renderer's ray queries, and uploads the scene as rendering does.
+ * drt_renderer_denoise filters the current framebuffer c_0 (RGB; display-referred: every sample is tone-mapped) with the guides of
+ * frame 1: passes i = 0 .. iterations-1, step s = 2^i, h = {1/16, 1/4, 3/8, 1/4, 1/16}; for each pixel p, over b then a in 0..4,
+ * q = (clamp(x + (a-2)s, 0, W-1), clamp(y + (b-2)s, 0, H-1)),
+ *   e = |c_i(p)-c_i(q)|^2 * 2^i / sigma_color^2 + |n(p)-n(q)|^2 / sigma_normal^2 + |alb(p)-alb(q)|^2 / sigma_albedo^2,
+ *   w = h[a] h[b] expf(-e),  c_{i+1}(p) = sum w c_i(q) / sum w  (squared distances summed over x, y, z in that order).
+ * The result (c_K, the input's alpha; iterations 0 = a copy of the framebuffer) lands in a renderer-owned float4[width*height]
+ * buffer, allocated by the first call and freed by resize and destroy.  Blocking; *delta_ms = device time of guides + filter.
+ * Neither call touches the accumulation buffer, the framebuffer, the sample count, the counters, kernel info or kernel span.
+ * DRT_ERR_INVALID: a NULL argument, frame_index 0, no frame size, a misaligned / host / other-device `guides`, iterations outside
+ * [0, 10], a sigma not finite or not > 0, a pending drt_renderer_render_batch_async batch.  DRT_ERR_UNSUPPORTED: a sharded
+ * renderer (world > 1: the filter needs its neighbours' rows), a tree deeper than 64 levels. */
+typedef struct drt_guide { float albedo[3]; float t; float normal[3]; int32_t prim; } drt_guide;                  /* 32 B */
+int           drt_renderer_render_guides(drt_renderer *r, const drt_camera *cam, const drt_scene *scene, uint32_t frame_index,
+                                         drt_guide *guides, void *hip_stream);
+typedef struct drt_denoise_params { int32_t iterations; float sigma_color, sigma_normal, sigma_albedo; } drt_denoise_params;
+void          drt_default_denoise_params(drt_denoise_params *out);                                           /* 5, 0.5, 0.1, 0.1 */
+int           drt_renderer_denoise(drt_renderer *r, const drt_camera *cam, const drt_scene *scene, const drt_denoise_params *p,
+                                   float *delta_ms);
+int           drt_renderer_read_denoised_rgba32f(drt_renderer *r, float *dst, size_t dst_floats);        /* width*height*4 */
+void         *drt_renderer_device_denoised(drt_renderer *r);              /* device float4[width*height], NULL before the first denoise */
 
 /* ---- multi-GPU sharding (new; the reference is single-device) ---- */
 /* This renderer owns the rows y with (y / stripe_rows) % world == rank, stored compactly in stripe order.
