@@ -277,6 +277,11 @@ _sig("drt_default_denoise_params", None, C.POINTER(DenoiseParams))
 _sig("drt_renderer_denoise", C.c_int, _P, C.POINTER(_CameraPOD), _P, C.POINTER(DenoiseParams), C.POINTER(C.c_float))
 _sig("drt_renderer_read_denoised_rgba32f", C.c_int, _P, _P, C.c_size_t)
 _sig("drt_renderer_device_denoised", _P, _P)
+_sig("drt_scene_get_triangle_order", C.c_int, _P, _P, C.c_int32)
+_sig("drt_scene_refit", C.c_int, _P, _P, _P)
+_sig("drt_renderer_refit", C.c_int, _P, _P, _P, _P, C.POINTER(C.c_float), _P)
+_sig("drt_debug_pack_scene", C.c_int, _P, _P, C.c_size_t, _P, C.c_size_t, _P)
+_sig("drt_debug_read_device_scene", C.c_int, _P, _P, C.c_size_t, _P, C.c_size_t, _P)
 
 EXPORTED_SYMBOLS = [n for n in dir(_lib) if n.startswith("drt_")]
 
@@ -388,6 +393,38 @@ class Scene:
     @property
     def bvh_depth(self):
         return _lib.drt_scene_bvh_depth(self._h)
+
+    def triangleOrder(self):
+        """int32 [n]: the load index (setGeometry / file order) of each triangle of m_PrimitivesBuffer (drt_scene_get_triangle_order)."""
+        return self._copy(_lib.drt_scene_get_triangle_order, _lib.drt_scene_triangle_count(self._h), np.int32)
+
+    def _refit_arrays(self, positions, normals):
+        n = _lib.drt_scene_triangle_count(self._h)
+        out = []
+        for what, a in (("positions", positions), ("normals", normals)):
+            if a is None:
+                out.append(None)
+                continue
+            a = np.ascontiguousarray(a, np.float32)
+            if a.size != 9 * n:
+                raise DrtError(ERR_INVALID, "%s: %d values, [%d, 3, 3] expected" % (what, a.size, n))
+            out.append(a)
+        return out
+
+    def refit(self, positions, normals=None):
+        """Refit the BVH to new vertex positions [n, 3, 3] in load order (and normals, None = keep them): drt_scene_refit.
+        Tree topology and triangle order stay; renderers upload the scene again."""
+        pos, nrm = self._refit_arrays(positions, normals)
+        _check(_lib.drt_scene_refit(self._h, pos.ctypes.data, nrm.ctypes.data if nrm is not None else None))
+
+    def debugPack(self):
+        """(InnerNode records uint8 [n_inner, 64], TriHot records uint8 [n, 48], root box float32 [6]) of the host pack (drt_debug_pack_scene)."""
+        nodes = self.m_BVHNodes
+        inner = np.zeros((int((nodes["is_leaf"] == 0).sum()), 64), np.uint8)
+        hot = np.zeros((_lib.drt_scene_triangle_count(self._h), 48), np.uint8)
+        root = np.zeros(6, np.float32)
+        _check(_lib.drt_debug_pack_scene(self._h, inner.ctypes.data, inner.size, hot.ctypes.data, hot.size, root.ctypes.data))
+        return inner, hot, root
 
 
 class BVHBuilder:
@@ -617,6 +654,40 @@ class Renderer:
             h = g.cpu().numpy()
             return Guides(h[..., 0:3].copy(), h[..., 4:7].copy(), h[..., 3].copy(), h.view(np.int32)[..., 7].copy())
         return Guides(g[..., 0:3], g[..., 4:7], g[..., 3], g.view(torch.int32)[..., 7])
+
+    def refit(self, scene, positions, normals=None):
+        """Refit this renderer's device copy of `scene` to new vertex positions [n, 3, 3] float32 in load order (normals the same,
+        None = the last ones given, else the scene's): drt_renderer_refit.  Device tensors stay on the device and order with the
+        current torch stream; numpy arrays are uploaded.  Blocking; returns the device ms.  The host scene is not changed."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        n = _lib.drt_scene_triangle_count(scene._h)
+        args = []
+        for what, a in (("positions", positions), ("normals", normals)):
+            if a is None:
+                args.append(None)
+                continue
+            if isinstance(a, np.ndarray):
+                a = torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev)
+            elif not torch.is_tensor(a):
+                raise DrtError(ERR_INVALID, "%s: a numpy array or a torch tensor expected" % what)
+            if a.dtype != torch.float32 or a.device != dev or a.numel() != 9 * n:
+                raise DrtError(ERR_INVALID, "%s: %s %s with %d values, float32 [%d, 3, 3] on %s expected" % (what, a.dtype, a.device, a.numel(), n, dev))
+            args.append(a.contiguous())
+        ms = C.c_float(0)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _check(_lib.drt_renderer_refit(self._h, scene._h, args[0].data_ptr(), args[1].data_ptr() if args[1] is not None else None,
+                                       C.byref(ms), stream))
+        return ms.value
+
+    def debugReadDeviceScene(self, scene):
+        """The renderer's current device records, shaped as Scene.debugPack() (drt_debug_read_device_scene)."""
+        nodes = scene.m_BVHNodes
+        inner = np.zeros((int((nodes["is_leaf"] == 0).sum()), 64), np.uint8)
+        hot = np.zeros((_lib.drt_scene_triangle_count(scene._h), 48), np.uint8)
+        root = np.zeros(6, np.float32)
+        _check(_lib.drt_debug_read_device_scene(self._h, inner.ctypes.data, inner.size, hot.ctypes.data, hot.size, root.ctypes.data))
+        return inner, hot, root
 
     def Denoise(self, cam, scene, iterations=5, sigma_color=0.5, sigma_normal=0.1, sigma_albedo=0.1):
         """Edge-avoiding a-trous filter of the current framebuffer, guided by frame 1's albedo and normal (drt_renderer_denoise):

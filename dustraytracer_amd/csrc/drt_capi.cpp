@@ -20,6 +20,7 @@
 #include "render_kernels.hpp"
 #include "ray_query.hpp"
 #include "denoise.hpp"
+#include "refit.hpp"
 #include "scene_host.hpp"
 #include "bvh_build_device.hpp"
 #include "png_decode.hpp"
@@ -149,12 +150,29 @@ struct drt_renderer {
     float4 *dn_buf[2] = { nullptr, nullptr };
     int denoised = -1;
     hipEvent_t ev_dn_start = nullptr, ev_dn_stop = nullptr;
+    // drt_renderer_refit: the uploaded scene's refit metadata (refit.hpp), built by the first refit after an upload and freed
+    // with the scene copy; out = the root box and the error word the kernels leave
+    bool rf_built = false;
+    DeviceArray<int32_t> rf_order;
+    DeviceArray<float4> rf_avg;
+    DeviceArray<float> rf_ext;
+    DeviceArray<RefitLeaf> rf_leaves;
+    DeviceArray<RefitInner> rf_levels;
+    DeviceArray<uint32_t> rf_height_begin;
+    DeviceArray<float> rf_out;
+    std::vector<uint32_t> rf_heights;
+    int rf_top_nodes = kRefitTopNodes;         // DRT_REFIT_TOP: 0 = one launch per height up to the root
+    int rf_launches = 0;
+    hipEvent_t ev_rf_start = nullptr, ev_rf_stop = nullptr, ev_rf_dep = nullptr;
 
     float *cur_accum() const { return ext_accum ? ext_accum : accum; }
     float *cur_rgba() const { return ext_rgba ? ext_rgba : rgba; }
     void free_scene() {
         d_inner.release(); d_leaves.release(); d_hot.release(); d_cold.release();
         d_mats.release(); d_mats_ext.release(); d_texs.release(); d_texels.release();
+        rf_order.release(); rf_avg.release(); rf_ext.release(); rf_leaves.release(); rf_levels.release();
+        rf_height_begin.release(); rf_out.release();
+        rf_built = false;
         uploaded_scene = nullptr;
     }
     void free_denoise() {
@@ -320,6 +338,12 @@ int drt_scene_get_triangles(const drt_scene *s, drt_triangle *out, int32_t cap) 
 int drt_scene_get_nodes(const drt_scene *s, drt_bvh_node *out, int32_t cap) { DRT_COPY_OUT(nodes) }
 int drt_scene_get_materials(const drt_scene *s, drt_material *out, int32_t cap) { DRT_COPY_OUT(materials) }
 int drt_scene_get_meshes(const drt_scene *s, drt_mesh *out, int32_t cap) { DRT_COPY_OUT(meshes) }
+int drt_scene_get_triangle_order(const drt_scene *s, int32_t *out, int32_t cap) { DRT_COPY_OUT(load_index) }
+
+int drt_scene_refit(drt_scene *s, const float *positions, const float *normals) {
+    if (!s) return fail(DRT_ERR_INVALID, "null scene");
+    try { s->host.refit(positions, normals); return DRT_OK; } catch (...) { return from_exception(); }
+}
 
 int drt_scene_get_texture_info(const drt_scene *s, int32_t index, drt_texture_info *out) {
     if (!s || !out || index < 0 || (size_t)index >= s->host.textures.size()) return fail(DRT_ERR_INVALID, "bad texture index");
@@ -410,6 +434,7 @@ drt_renderer *drt_renderer_create(int32_t device) {
     int khz = 0;
     if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) == hipSuccess && khz > 0) r->wall_clock_khz = khz;
     r->rq_refill_min = std::min(64, std::max(1, env_int("DRT_RQ_REFILL", r->rq_refill_min)));
+    r->rf_top_nodes = std::max(0, env_int("DRT_REFIT_TOP", r->rf_top_nodes));
     if (hipEventCreate(&r->ev_start) != hipSuccess || hipEventCreate(&r->ev_stop) != hipSuccess ||
         hipEventCreateWithFlags(&r->ev_query, hipEventDisableTiming) != hipSuccess ||
         hipMalloc((void **)&r->counters, sizeof(drt_counters)) != hipSuccess ||
@@ -448,6 +473,8 @@ void drt_renderer_destroy(drt_renderer *r) {
     r->free_denoise();
     if (r->ev_dn_start) (void)hipEventDestroy(r->ev_dn_start);
     if (r->ev_dn_stop) (void)hipEventDestroy(r->ev_dn_stop);
+    for (hipEvent_t ev : { r->ev_rf_start, r->ev_rf_stop, r->ev_rf_dep })
+        if (ev) (void)hipEventDestroy(ev);
     if (r->ev_start) (void)hipEventDestroy(r->ev_start);
     if (r->ev_stop) (void)hipEventDestroy(r->ev_stop);
     delete r;
@@ -1017,6 +1044,164 @@ int drt_renderer_denoise(drt_renderer *r, const drt_camera *cam, const drt_scene
     HIP_TRY(hipEventElapsedTime(&ms, r->ev_dn_start, r->ev_dn_stop));
     if (delta_ms) *delta_ms = ms;
     r->denoised = out;
+    return DRT_OK;
+}
+
+// ------------------------------------------------------------------ refit of the device copy (kernel_refit.hip)
+// The metadata of the uploaded scene: load order, stored normals' averages, the leaves and the interior nodes by height, every
+// node's destination box in pack()'s numbering of the records.
+static RefitPlan refit_plan(const HostScene &h) {
+    RefitPlan p;
+    const size_t n_nodes = h.nodes.size();
+    p.n_nodes = (uint32_t)n_nodes;
+    p.order = h.load_index;
+    p.avg_normal.resize(h.triangles.size());
+    for (size_t k = 0; k < h.triangles.size(); k++) {
+        const drt_vertex *v = h.triangles[k].vertex;
+        const V3 avg = (V3{ v[0].normal[0], v[0].normal[1], v[0].normal[2] } + V3{ v[1].normal[0], v[1].normal[1], v[1].normal[2] } +
+                        V3{ v[2].normal[0], v[2].normal[1], v[2].normal[2] }) / 3;        // make_triangle (Scene.cu:279)
+        p.avg_normal[k] = make_float4(avg.x, avg.y, avg.z, 0.f);
+    }
+    std::vector<uint32_t> rec(n_nodes, 0), dest(n_nodes, kRefitRootDest);
+    uint32_t n_inner = 0;
+    for (size_t i = 0; i < n_nodes; i++)
+        if (!h.nodes[i].is_leaf) rec[i] = n_inner++;
+    for (size_t i = 0; i < n_nodes; i++) {
+        const drt_bvh_node &nd = h.nodes[i];
+        if (nd.is_leaf) continue;
+        dest[(size_t)nd.child1] = rec[i] << 1;
+        dest[(size_t)nd.child2] = rec[i] << 1 | 1u;
+    }
+    std::vector<int32_t> pre, todo{ (int32_t)n_nodes - 1 }, height(n_nodes, 0);
+    pre.reserve(n_nodes);
+    while (!todo.empty()) {
+        const int32_t i = todo.back();
+        todo.pop_back();
+        pre.push_back(i);
+        const drt_bvh_node &nd = h.nodes[(size_t)i];
+        if (!nd.is_leaf) { todo.push_back(nd.child1); todo.push_back(nd.child2); }
+    }
+    int32_t heights = 0;
+    for (size_t j = pre.size(); j-- > 0;) {            // children before their parent
+        const int32_t i = pre[j];
+        const drt_bvh_node &nd = h.nodes[(size_t)i];
+        if (nd.is_leaf) {
+            p.leaves.push_back(RefitLeaf{ nd.prim_start, nd.prim_count, i, dest[(size_t)i] });
+        } else {
+            height[(size_t)i] = 1 + std::max(height[(size_t)nd.child1], height[(size_t)nd.child2]);
+            heights = std::max(heights, height[(size_t)i]);
+        }
+    }
+    p.height_begin.assign((size_t)heights + 1, 0);
+    for (int32_t i : pre)
+        if (height[(size_t)i] > 0) p.height_begin[(size_t)height[(size_t)i]]++;
+    for (int32_t hh = 1; hh <= heights; hh++) p.height_begin[(size_t)hh] += p.height_begin[(size_t)hh - 1];
+    std::vector<uint32_t> fill(p.height_begin.begin(), p.height_begin.end());
+    p.inner.resize(n_inner);
+    for (size_t i = 0; i < n_nodes; i++) {
+        const drt_bvh_node &nd = h.nodes[i];
+        if (!nd.is_leaf) p.inner[fill[(size_t)height[i] - 1]++] = RefitInner{ nd.child1, nd.child2, (int32_t)i, dest[i] };
+    }
+    return p;
+}
+
+// device memory of the renderer's device that holds `bytes` bytes from p on (as far as the runtime can tell)
+static bool device_range_on_renderer(const drt_renderer *r, const void *p, size_t bytes) {
+    if (((uintptr_t)p & 3u) != 0 || !on_renderer_device(r, p)) return false;
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return true; }
+    return (const char *)p >= (const char *)base && bytes <= size - (size_t)((const char *)p - (const char *)base);
+}
+
+int drt_renderer_refit(drt_renderer *r, const drt_scene *scene, const float *positions, const float *normals, float *delta_ms,
+                       void *hip_stream) {
+    if (delta_ms) *delta_ms = 0.f;
+    if (!r || !scene || !positions) return fail(DRT_ERR_INVALID, "null argument");
+    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
+    if (scene->host.nodes.empty()) return fail(DRT_ERR_INVALID, "scene has no BVH: refit keeps a tree, build one first");
+    HIP_TRY(hipSetDevice(r->device));
+    (void)hipGetLastError();
+    const size_t bytes = 9 * sizeof(float) * scene->host.triangles.size();
+    for (const float *p : { positions, normals })
+        if (p && !device_range_on_renderer(r, p, bytes))
+            return fail(DRT_ERR_INVALID, "positions and normals must be float[n][3][3] in device memory on the renderer's device");
+    int rc = upload_scene(r, scene);
+    if (rc != DRT_OK) return rc;
+    if (r->bvh_depth > 64) return fail(DRT_ERR_UNSUPPORTED, "BVH deeper than 64 levels (the reference's traversal stack, BVHTraversal.cuh:17)");
+    if (!r->rf_built) {
+        RefitPlan plan;
+        try { plan = refit_plan(scene->host); } catch (...) { return from_exception(); }
+        HIP_TRY(r->rf_order.upload(plan.order));
+        HIP_TRY(r->rf_avg.upload(plan.avg_normal));
+        HIP_TRY(r->rf_ext.upload(std::vector<float>(6 * (size_t)plan.n_nodes, 0.f)));
+        HIP_TRY(r->rf_leaves.upload(plan.leaves));
+        HIP_TRY(r->rf_levels.upload(plan.inner));
+        HIP_TRY(r->rf_height_begin.upload(plan.height_begin));
+        HIP_TRY(r->rf_out.upload(std::vector<float>(8, 0.f)));
+        r->rf_heights = plan.height_begin;
+        r->rf_built = true;
+    }
+    if (!r->ev_rf_start) HIP_TRY(hipEventCreate(&r->ev_rf_start));
+    if (!r->ev_rf_stop) HIP_TRY(hipEventCreate(&r->ev_rf_stop));
+    if (!r->ev_rf_dep) HIP_TRY(hipEventCreateWithFlags(&r->ev_rf_dep, hipEventDisableTiming));
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : r->stream;
+    // nothing is written before the renderer's queries / guide passes in flight and the work on its stream are done
+    if (r->query_recorded && r->query_stream != s) HIP_TRY(hipStreamWaitEvent(s, r->ev_query, 0));
+    if (s != r->stream) {
+        HIP_TRY(hipEventRecord(r->ev_rf_dep, r->stream));
+        HIP_TRY(hipStreamWaitEvent(s, r->ev_rf_dep, 0));
+    }
+    HIP_TRY(hipEventRecord(r->ev_rf_start, s));
+    HIP_TRY(hipMemsetAsync(r->rf_out.ptr + 6, 0, sizeof(unsigned int), s));
+    RefitArgs a;
+    a.pos = positions; a.nrm = normals;
+    a.order = r->rf_order.ptr; a.avg_normal = r->rf_avg.ptr;
+    a.hot = r->d_hot.ptr; a.inner = r->d_inner.ptr; a.ext = r->rf_ext.ptr;
+    a.leaves = r->rf_leaves.ptr; a.n_leaves = (uint32_t)r->rf_leaves.count;
+    a.levels = r->rf_levels.ptr; a.height_begin = r->rf_height_begin.ptr;
+    a.root_box = r->rf_out.ptr; a.error = reinterpret_cast<unsigned int *>(r->rf_out.ptr + 6);
+    HIP_TRY(launch_refit(a, r->rf_heights, r->rf_top_nodes, s, &r->rf_launches));
+    HIP_TRY(hipEventRecord(r->ev_rf_stop, s));
+    float out[8];
+    HIP_TRY(hipMemcpyAsync(out, r->rf_out.ptr, sizeof out, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    unsigned int err;
+    std::memcpy(&err, out + 6, 4);
+    if (err) {
+        r->uploaded_scene = nullptr;             // the copy is half written: the next use uploads the host state again
+        return fail(DRT_ERR_INVALID, "non-finite coordinate in refit input");
+    }
+    std::memcpy(r->view.root_min, out, 12);
+    std::memcpy(r->view.root_max, out + 3, 12);
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, r->ev_rf_start, r->ev_rf_stop));
+    if (delta_ms) *delta_ms = ms;
+    return DRT_OK;
+}
+
+int drt_debug_pack_scene(const drt_scene *s, void *inner, size_t inner_bytes, void *tri_hot, size_t hot_bytes, float root_box[6]) {
+    if (!s) return fail(DRT_ERR_INVALID, "null scene");
+    PackedScene ps;
+    try { ps = s->host.pack(); } catch (...) { return from_exception(); }
+    if ((inner && inner_bytes < ps.inner.size() * sizeof(InnerNode)) || (tri_hot && hot_bytes < ps.tri_hot.size() * sizeof(TriHot)))
+        return fail(DRT_ERR_INVALID, "destination too small");
+    if (inner && !ps.inner.empty()) std::memcpy(inner, ps.inner.data(), ps.inner.size() * sizeof(InnerNode));
+    if (tri_hot && !ps.tri_hot.empty()) std::memcpy(tri_hot, ps.tri_hot.data(), ps.tri_hot.size() * sizeof(TriHot));
+    if (root_box) { std::memcpy(root_box, ps.root_min, 12); std::memcpy(root_box + 3, ps.root_max, 12); }
+    return DRT_OK;
+}
+
+int drt_debug_read_device_scene(drt_renderer *r, void *inner, size_t inner_bytes, void *tri_hot, size_t hot_bytes, float root_box[6]) {
+    if (!r) return fail(DRT_ERR_INVALID, "null renderer");
+    if (!r->uploaded_scene) return fail(DRT_ERR_INVALID, "the renderer holds no scene");
+    if ((inner && inner_bytes < r->d_inner.count * sizeof(InnerNode)) || (tri_hot && hot_bytes < r->d_hot.count * sizeof(TriHot)))
+        return fail(DRT_ERR_INVALID, "destination too small");
+    HIP_TRY(hipSetDevice(r->device));
+    HIP_TRY(hipDeviceSynchronize());
+    if (inner && r->d_inner.count) HIP_TRY(hipMemcpy(inner, r->d_inner.ptr, r->d_inner.count * sizeof(InnerNode), hipMemcpyDeviceToHost));
+    if (tri_hot && r->d_hot.count) HIP_TRY(hipMemcpy(tri_hot, r->d_hot.ptr, r->d_hot.count * sizeof(TriHot), hipMemcpyDeviceToHost));
+    if (root_box) { std::memcpy(root_box, r->view.root_min, 12); std::memcpy(root_box + 3, r->view.root_max, 12); }
     return DRT_OK;
 }
 

@@ -37,7 +37,7 @@ static inline V3 ld(const float *p) { return V3{ p[0], p[1], p[2] }; }
 static inline void st(float *p, V3 v) { p[0] = v.x; p[1] = v.y; p[2] = v.z; }
 
 void HostScene::clear() {
-    triangles.clear(); materials.clear(); textures.clear(); meshes.clear(); nodes.clear();
+    triangles.clear(); load_index.clear(); materials.clear(); textures.clear(); meshes.clear(); nodes.clear();
     revision = next_revision();
 }
 
@@ -69,8 +69,11 @@ static drt_triangle make_triangle(const float *pos, const float *nrm, const floa
 void HostScene::set_geometry(const float *pos, const float *nrm, const float *uv, const int32_t *mat, int32_t n_tris) {
     drt_mesh mesh;
     mesh.primitives_offset = (int32_t)triangles.size();
-    for (int32_t i = 0; i < n_tris; i++)
+    load_index.resize(triangles.size());
+    for (int32_t i = 0; i < n_tris; i++) {
         triangles.push_back(make_triangle(pos + 9 * (size_t)i, nrm + 9 * (size_t)i, uv + 6 * (size_t)i, mat[i]));
+        load_index.push_back(mesh.primitives_offset + i);
+    }
     mesh.tris_count = n_tris;
     meshes.push_back(mesh);
     nodes.clear();
@@ -509,6 +512,7 @@ void HostScene::load_gltf(const char *path, bool strict) {
             throw UnsupportedError("baseColorTexture.index beyond the image list (used as image index, Scene.cu:79)");
 
     triangles = std::move(fresh.triangles);
+    load_index = std::move(fresh.load_index);
     materials = std::move(fresh.materials);
     textures = std::move(fresh.textures);
     meshes = std::move(fresh.meshes);
@@ -644,6 +648,12 @@ void HostScene::build_bvh(int32_t target_leaf_prims, int32_t bin_count) {
         return;
     }
     std::vector<drt_triangle> work = triangles;          // reordered copy, committed on success
+    // every triangle carries its load index through the partitions in its padding word, which is restored afterwards
+    std::vector<float> pad_of_load(work.size());
+    for (size_t i = 0; i < work.size(); i++) {
+        pad_of_load[(size_t)load_index[i]] = work[i]._pad0;
+        std::memcpy(&work[i]._pad0, &load_index[i], 4);
+    }
     std::vector<drt_bvh_node> out;
     out.reserve((size_t)2 * (size_t)n + 2);
     Builder b{ work, bin_count, {}, {} };
@@ -671,6 +681,10 @@ void HostScene::build_bvh(int32_t target_leaf_prims, int32_t bin_count) {
         if (cur < 0) root = node; else out[(size_t)cur] = node;
     }
     out.push_back(root);
+    for (size_t i = 0; i < work.size(); i++) {
+        std::memcpy(&load_index[i], &work[i]._pad0, 4);
+        work[i]._pad0 = pad_of_load[(size_t)load_index[i]];
+    }
     triangles.swap(work);
     nodes.swap(out);
 }
@@ -683,8 +697,13 @@ float HostScene::build_bvh_on_device(int32_t target_leaf_prims, int32_t bin_coun
     }
     DeviceBuild built = drt::build_bvh_on_device(triangles, target_leaf_prims, bin_count, device);
     std::vector<drt_triangle> reordered(triangles.size());
-    for (size_t i = 0; i < reordered.size(); i++) reordered[i] = triangles[built.order[i]];
+    std::vector<int32_t> reordered_index(triangles.size());
+    for (size_t i = 0; i < reordered.size(); i++) {
+        reordered[i] = triangles[built.order[i]];
+        reordered_index[i] = load_index[built.order[i]];
+    }
     triangles.swap(reordered);
+    load_index.swap(reordered_index);
     nodes.swap(built.nodes);
     revision = next_revision();
     return built.device_ms;
@@ -702,6 +721,73 @@ int32_t HostScene::bvh_depth() const {
         if (!n.is_leaf) { todo.push_back({ n.child1, d + 1 }); todo.push_back({ n.child2, d + 1 }); }
     }
     return depth;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Refit (drt_scene_refit): the tree's topology and triangle order stay, the geometry moves
+// ---------------------------------------------------------------------------------------------
+void HostScene::refit(const float *pos, const float *nrm) {
+    if (nodes.empty()) throw std::invalid_argument("scene has no BVH: refit keeps a tree, build one first");
+    if (!pos) throw std::invalid_argument("null positions");
+    const size_t n = triangles.size();
+    for (size_t i = 0; i < 9 * n; i++)
+        if (!std::isfinite(pos[i]) || (nrm && !std::isfinite(nrm[i])))
+            throw std::invalid_argument("non-finite coordinate in refit input (value " + std::to_string(i) + ")");
+    // Every node's box from the exact extent of its subtree: lo / hi = min / max over its vertices (a parent takes the min /
+    // max of its children's lo / hi, not of their stored boxes), stored as set_bounds stores it: bmin = lo, bmax = lo + (hi - lo).
+    // Children are visited before their parent by walking a pre-order from the root backwards.
+    std::vector<int32_t> pre;
+    pre.reserve(nodes.size());
+    std::vector<int32_t> todo{ (int32_t)nodes.size() - 1 };
+    while (!todo.empty()) {
+        const int32_t i = todo.back();
+        todo.pop_back();
+        pre.push_back(i);
+        const drt_bvh_node &nd = nodes[(size_t)i];
+        if (nd.is_leaf ? nd.prim_start < 0 || nd.prim_count < 0 || (size_t)nd.prim_start + (size_t)nd.prim_count > n
+                       : nd.child1 < 0 || nd.child2 < 0 || (size_t)nd.child1 >= nodes.size() || (size_t)nd.child2 >= nodes.size() ||
+                             pre.size() + todo.size() + 2 > nodes.size())
+            throw std::invalid_argument("BVH node " + std::to_string(i) + " is not part of a binary tree over the triangles");
+        if (!nd.is_leaf) { todo.push_back(nd.child1); todo.push_back(nd.child2); }
+    }
+    for (size_t k = 0; k < n; k++) {            // make_triangle on the new vertices, in place: UVs and material stay
+        drt_triangle &t = triangles[k];
+        const size_t src = 9 * (size_t)load_index[k];
+        float p[9], q[9], uv[6];
+        for (int v = 0; v < 3; v++) {
+            for (int c = 0; c < 3; c++) {
+                p[3 * v + c] = pos[src + 3 * v + c];
+                q[3 * v + c] = nrm ? nrm[src + 3 * v + c] : t.vertex[v].normal[c];
+            }
+            uv[2 * v] = t.vertex[v].uv[0];
+            uv[2 * v + 1] = t.vertex[v].uv[1];
+        }
+        const float pad = t._pad0;
+        t = make_triangle(p, q, uv, t.material);
+        t._pad0 = pad;
+    }
+    std::vector<V3> lo(nodes.size()), hi(nodes.size());
+    for (size_t j = pre.size(); j-- > 0;) {
+        const size_t i = (size_t)pre[j];
+        drt_bvh_node &nd = nodes[i];
+        V3 l = v3(FLT_MAX, FLT_MAX, FLT_MAX), h = v3(-FLT_MAX, -FLT_MAX, -FLT_MAX);
+        auto take = [&](V3 a, V3 b) {
+            l = v3(min_zero_ordered(l.x, a.x), min_zero_ordered(l.y, a.y), min_zero_ordered(l.z, a.z));
+            h = v3(max_zero_ordered(h.x, b.x), max_zero_ordered(h.y, b.y), max_zero_ordered(h.z, b.z));
+        };
+        if (nd.is_leaf) {
+            for (int32_t k = nd.prim_start; k < nd.prim_start + nd.prim_count; k++)
+                for (int v = 0; v < 3; v++) take(ld(triangles[(size_t)k].vertex[v].position), ld(triangles[(size_t)k].vertex[v].position));
+        } else {
+            take(lo[(size_t)nd.child1], hi[(size_t)nd.child1]);
+            take(lo[(size_t)nd.child2], hi[(size_t)nd.child2]);
+        }
+        lo[i] = l;
+        hi[i] = h;
+        st(nd.bmin, l);
+        st(nd.bmax, l + (h - l));
+    }
+    revision = next_revision();
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 // scene_host.hpp -- host-side scene: glTF flattening, binned-SAH BVH build, packing for the device.
 // Replaces struct Scene (Core/Scene/Scene.cuh:41-57) and class BVHBuilder (Core/BVH/BVHBuilder.cuh:12-96).
 #pragma once
+#include <cmath>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -32,6 +33,7 @@ V3 normalize(V3 v);   // v * (1.0f / sqrtf(dot(v, v)))  (helper_math.cuh:1325-13
 class HostScene {
 public:
     std::vector<drt_triangle> triangles;     // m_PrimitivesBuffer (reordered in place by build_bvh)
+    std::vector<int32_t> load_index;         // per triangle: its index in load / set_geometry order, permuted with the triangles by every build
     std::vector<drt_material> materials;     // m_Material
     std::vector<HostTexture> textures;       // m_Textures
     std::vector<drt_mesh> meshes;            // m_Meshes
@@ -52,9 +54,18 @@ public:
     float build_bvh_on_device(int32_t target_leaf_prims, int32_t bin_count, int device);
     int32_t bvh_depth() const;
 
+    // Refit (drt_scene_refit): new vertex positions (and normals, or nullptr to keep the stored ones) in load order,
+    // float[n][3][3]; triangles recomputed as loaded, every node box from the exact extents of its subtree, topology and
+    // order kept.  Throws std::invalid_argument (no BVH, a non-finite value) before anything is written.
+    void refit(const float *pos, const float *nrm);
+
     // Device-layout image of the scene (see device_scene.hpp); throws when there is no BVH.
     PackedScene pack() const;
 };
+
+// Order-independent min / max of finite floats: -0 < +0 in both (the device builder's and the refits' rule for a zero bound).
+inline float min_zero_ordered(float a, float b) { return a < b ? a : b < a ? b : std::signbit(a) ? a : b; }
+inline float max_zero_ordered(float a, float b) { return a > b ? a : b > a ? b : std::signbit(a) ? b : a; }
 
 struct UnsupportedError : std::runtime_error { using std::runtime_error::runtime_error; };
 struct IoError : std::runtime_error { using std::runtime_error::runtime_error; };

@@ -146,6 +146,14 @@ struct Scene {
         if (!v.empty()) drt::check(drt_scene_get_nodes(handle, v.data(), (int32_t)v.size()));
         return v;
     }
+    // new: load index of every triangle of primitives() (drt_scene_get_triangle_order)
+    std::vector<int32_t> TriangleOrder() const {
+        std::vector<int32_t> v(trianglesCount());
+        if (!v.empty()) drt::check(drt_scene_get_triangle_order(handle, v.data(), (int32_t)v.size()));
+        return v;
+    }
+    // new: refit the BVH to moved vertices, float[n][3][3] in load order; normals nullptr = keep them (drt_scene_refit)
+    void Refit(const float *positions, const float *normals = nullptr) { drt::check(drt_scene_refit(handle, positions, normals)); }
     void refresh() {                                                      // after anything that changes the scene
         std::vector<drt_mesh> meshes(meshCount());
         if (!meshes.empty()) drt::check(drt_scene_get_meshes(handle, meshes.data(), (int32_t)meshes.size()));
@@ -282,6 +290,13 @@ public:
         drt::check(drt_renderer_occluded(handle, scene.handle, rays, occluded, n, stream));
     }
     // First-hit guide buffers of frame `frame_index` (drt_renderer_render_guides): a device drt_guide[width*height], enqueued on `stream`
+    // new: refit this renderer's device copy of the scene to moved vertices (device pointers, load order; drt_renderer_refit).
+    // Blocking; returns the device ms.  Reset the accumulation afterwards, as after a camera move.
+    float Refit(const Scene &scene, const float *positions, const float *normals = nullptr, void *stream = nullptr) {
+        float ms = 0.f;
+        drt::check(drt_renderer_refit(handle, scene.handle, positions, normals, &ms, stream));
+        return ms;
+    }
     void RenderGuides(Camera *cam, const Scene &scene, uint32_t frame_index, drt_guide *guides, void *stream = nullptr) {
         drt_settings s = m_RendererSettings.pod();
         drt_camera c = cam->pod();

@@ -26,7 +26,7 @@ extern "C" {
 #endif
 
 /* 2: drt_counters grew by sampler_tries; drt_group_* and drt_material_model entry points (round 2) are part of it; the ray-query
- * entry points (drt_renderer_trace_rays / _occluded) and the guide / denoise entry points are additions to it */
+ * entry points (drt_renderer_trace_rays / _occluded), the guide / denoise entry points and the refit entry points are additions to it */
 #define DRT_ABI_VERSION 2
 
 typedef enum {
@@ -276,6 +276,41 @@ int           drt_renderer_denoise(drt_renderer *r, const drt_camera *cam, const
                                    float *delta_ms);
 int           drt_renderer_read_denoised_rgba32f(drt_renderer *r, float *dst, size_t dst_floats);        /* width*height*4 */
 void         *drt_renderer_device_denoised(drt_renderer *r);              /* device float4[width*height], NULL before the first denoise */
+
+/* ---- BVH refit for moving geometry (new; the reference rebuilds) ----
+ * A refit keeps the tree's topology, node order and triangle order and recomputes the boxes bottom-up from new vertex positions.
+ * drt_scene_get_triangle_order: out[k] = the load index of triangle k in drt_scene_get_triangles order (= the prim of ray queries
+ * and guides): the index it had in load / drt_scene_set_geometry order (what a drt_mesh range addresses).  Identity after a load,
+ * permuted by every build exactly as the triangles are.  Returns the count written (at most cap).
+ * drt_scene_refit: positions = float[n_tris][3][3] in LOAD order (drt_scene_set_geometry's de-indexed layout); normals the same
+ * shape, or NULL to keep the stored vertex normals.  Every triangle is assembled again as the loader assembles it (positions,
+ * normals when given, face normal turned towards the averaged vertex normal, centroid; UVs and material stay).  Every node's box
+ * comes from the EXACT extent of its subtree: lo / hi = min / max over its vertices (an interior node's = min / max of its
+ * children's exact lo / hi, not of their stored boxes), stored as the builder stores it: bmin = lo, bmax = lo + (hi - lo) in fp32.
+ * A zero bound takes the order-independent sign (-0 < +0 in min and max), as drt_scene_build_bvh_device.  The revision moves, so
+ * renderers upload the scene again.  DRT_ERR_INVALID: no BVH, NULL positions, a non-finite value (checked before anything is
+ * written: the scene is unchanged).
+ * drt_renderer_refit: the same refit applied to THIS renderer's device copy of `scene` (uploaded first if it holds another):
+ * TriHot records, InnerNode child boxes and the root box equal, bit for bit, what the host refit with the same arguments packs
+ * (the NaN face normal of a zero-area triangle, which no traversal reads, may carry another payload).  positions / normals are
+ * device pointers on the renderer's device, in load order; normals NULL = those of this renderer's last refit that gave them since
+ * the upload, else the scene's.  Every later render, query and guide pass of this renderer uses the refitted copy until the scene's
+ * revision moves or another scene is uploaded (both upload the host state again and drop the refit); other renderers and the host
+ * scene are untouched.  hip_stream NULL = the renderer's stream; the refit waits on the device for the renderer's queries and
+ * guide passes in flight and its stream, then blocks until done (the root box travels back to the host); *delta_ms = device time.
+ * The accumulation buffer, framebuffer, sample count, counters, kernel info and kernel span are not touched: reset after moving
+ * geometry, as after a camera move.  DRT_ERR_INVALID: a NULL / host / other-device pointer or one whose allocation ends short of n_tris * 36 bytes, a pending
+ * drt_renderer_render_batch_async batch, no BVH, a non-finite value (the device copy is then dropped: the next use uploads the
+ * host state).  DRT_ERR_UNSUPPORTED: a tree deeper than 64 levels. */
+int           drt_scene_get_triangle_order(const drt_scene *s, int32_t *out, int32_t cap);
+int           drt_scene_refit(drt_scene *s, const float *positions, const float *normals);
+int           drt_renderer_refit(drt_renderer *r, const drt_scene *scene, const float *positions, const float *normals, float *delta_ms,
+                                 void *hip_stream);
+/* Read-backs for the tests: the host pack of the scene (InnerNode[] and TriHot[] records of csrc/device_scene.hpp, root bmin, bmax)
+ * and the renderer's current device copy of them (blocking; DRT_ERR_INVALID when it holds no scene).  A NULL destination is
+ * skipped; DRT_ERR_INVALID when one is too small. */
+int           drt_debug_pack_scene(const drt_scene *s, void *inner, size_t inner_bytes, void *tri_hot, size_t hot_bytes, float root_box[6]);
+int           drt_debug_read_device_scene(drt_renderer *r, void *inner, size_t inner_bytes, void *tri_hot, size_t hot_bytes, float root_box[6]);
 
 /* ---- multi-GPU sharding (new; the reference is single-device) ---- */
 /* This renderer owns the rows y with (y / stripe_rows) % world == rank, stored compactly in stripe order.
