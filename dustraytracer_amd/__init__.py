@@ -280,6 +280,8 @@ _sig("drt_renderer_device_denoised", _P, _P)
 _sig("drt_scene_get_triangle_order", C.c_int, _P, _P, C.c_int32)
 _sig("drt_scene_refit", C.c_int, _P, _P, _P)
 _sig("drt_renderer_refit", C.c_int, _P, _P, _P, _P, C.POINTER(C.c_float), _P)
+_sig("drt_renderer_camera_rays", C.c_int, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P)
+_sig("drt_renderer_radiance", C.c_int, _P, _P, _P, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_debug_pack_scene", C.c_int, _P, _P, C.c_size_t, _P, C.c_size_t, _P)
 _sig("drt_debug_read_device_scene", C.c_int, _P, _P, C.c_size_t, _P, C.c_size_t, _P)
 
@@ -679,6 +681,96 @@ class Renderer:
         _check(_lib.drt_renderer_refit(self._h, scene._h, args[0].data_ptr(), args[1].data_ptr() if args[1] is not None else None,
                                        C.byref(ms), stream))
         return ms.value
+
+    def cameraRays(self, cams, width, height, frame_index=1, as_torch=False):
+        """RayGen's primary rays of every camera and pixel in frame `frame_index` (drt_renderer_camera_rays): float32 [K, H, W, 8]
+        = org, seed (uint32 bits), dir, exposure; row 0 = bottom.  `cams`: a Camera or a list of K.  as_torch=True: a device tensor,
+        the work enqueued on the current torch stream; else a numpy array."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        cams = [cams] if isinstance(cams, Camera) else list(cams)
+        pods = (_CameraPOD * max(len(cams), 1))(*[c._pod() for c in cams])
+        rays = torch.empty((len(cams), int(height), int(width), 8), dtype=torch.float32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _check(_lib.drt_renderer_camera_rays(self._h, pods, len(cams), int(width), int(height), int(frame_index),
+                                             rays.data_ptr() if rays.numel() else None, stream))
+        return rays if as_torch else rays.cpu().numpy()
+
+    def radiance(self, scene, rays, out=None, accumulate=False):
+        """One path-traced sample of every ray with the current settings and material model (drt_renderer_radiance).  rays:
+        float32 [..., 8] (org, seed bits, dir, exposure), a numpy array or a device tensor; returns float32 [..., 4] = (c, 1).
+        out: an array / tensor of that shape (same kind as rays) to write into instead; accumulate=True adds c to its rgb and
+        keeps its alpha.  Device tensors order with the current torch stream; numpy in, numpy out."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        from_numpy = isinstance(rays, np.ndarray)
+        if from_numpy:
+            if rays.dtype != np.float32:
+                raise DrtError(ERR_INVALID, "rays: dtype %s, float32 expected" % rays.dtype)
+            r = torch.from_numpy(np.ascontiguousarray(rays)).to(dev)
+        elif torch.is_tensor(rays):
+            if rays.dtype != torch.float32 or rays.device != dev:
+                raise DrtError(ERR_INVALID, "rays: %s on %s, torch.float32 on %s expected" % (rays.dtype, rays.device, dev))
+            r = rays.contiguous()
+        else:
+            raise DrtError(ERR_INVALID, "rays: a numpy array or a torch tensor expected")
+        if r.dim() < 1 or r.shape[-1] != 8:
+            raise DrtError(ERR_INVALID, "rays: shape %s, [..., 8] expected" % (tuple(r.shape),))
+        shape = tuple(r.shape[:-1]) + (4,)
+        if accumulate and out is None:
+            raise DrtError(ERR_INVALID, "accumulate needs `out`")
+        if out is None:
+            o = torch.empty(shape, dtype=torch.float32, device=dev)
+        elif isinstance(out, np.ndarray) != from_numpy or (not from_numpy and not torch.is_tensor(out)):
+            raise DrtError(ERR_INVALID, "out: the same kind as rays (numpy array or device tensor) expected")
+        elif tuple(out.shape) != shape:
+            raise DrtError(ERR_INVALID, "out: shape %s, %s expected" % (tuple(out.shape), shape))
+        elif from_numpy:
+            if out.dtype != np.float32:
+                raise DrtError(ERR_INVALID, "out: dtype %s, float32 expected" % out.dtype)
+            o = torch.from_numpy(np.ascontiguousarray(out)).to(dev)
+        else:
+            if out.dtype != torch.float32 or out.device != dev or not out.is_contiguous() or out.data_ptr() % 16:
+                raise DrtError(ERR_INVALID, "out: a contiguous, 16-byte aligned torch.float32 tensor on %s expected" % dev)
+            o = out
+        n = r.numel() // 8
+        if r.data_ptr() % 16:
+            r = r.clone()
+        self._push_settings()
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if n:
+            _check(_lib.drt_renderer_radiance(self._h, scene._h, r.data_ptr(), o.data_ptr(), n, 1 if accumulate else 0, stream))
+        if not from_numpy:
+            return o
+        h = o.cpu().numpy()
+        if out is None:
+            return h
+        out[...] = h
+        return out
+
+    def renderViews(self, cams, scene, width, height, spp, as_torch=False):
+        """`spp` frames of K cameras at width x height (frames 1..spp): per frame one camera_rays launch for all cameras and one
+        accumulating radiance launch over K*H*W rays; returns accum / spp with alpha 1, float32 [K, H, W, 4], row 0 = bottom.
+        Each view equals what a renderer that rendered that camera alone (ResizeBuffer, reset, spp frames) shows."""
+        import torch                             # (only here: importing the package does not import torch)
+        if int(spp) < 1:
+            raise DrtError(ERR_INVALID, "spp >= 1 expected")
+        dev = torch.device("cuda", self._device)
+        cams = [cams] if isinstance(cams, Camera) else list(cams)
+        acc = torch.zeros((len(cams), int(height), int(width), 4), dtype=torch.float32, device=dev)
+        for f in range(1, int(spp) + 1):
+            rays = self.cameraRays(cams, width, height, f, as_torch=True)
+            self.radiance(scene, rays, out=acc, accumulate=True)
+        if as_torch:
+            # RenderKernel.cu:30, one correctly rounded fp32 division: torch's fp32 division on the device is not, the fp64 quotient
+            # of two floats rounded once to fp32 is (53 >= 2 * 24 + 2 bits)
+            img = (acc.double() / float(spp)).float()
+            img[..., 3] = 1.0
+            return img
+        img = acc.cpu().numpy()
+        img[..., :3] = img[..., :3] / np.float32(spp)
+        img[..., 3] = 1.0
+        return img
 
     def debugReadDeviceScene(self, scene):
         """The renderer's current device records, shaped as Scene.debugPack() (drt_debug_read_device_scene)."""

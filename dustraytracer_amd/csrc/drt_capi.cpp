@@ -21,6 +21,7 @@
 #include "ray_query.hpp"
 #include "denoise.hpp"
 #include "refit.hpp"
+#include "radiance.hpp"
 #include "scene_host.hpp"
 #include "bvh_build_device.hpp"
 #include "png_decode.hpp"
@@ -673,11 +674,9 @@ static int upload_scene(drt_renderer *r, const drt_scene *scene) {
     return DRT_OK;
 }
 
-// Per-frame constants of Camera::GetRay (Camera.cu:84-103) and RayGen (RayGen.cuh:68-72), computed on the
-// host with the same fp32 operations in the same order (host libm for tan/sin/cos).
-static void fill_frame_params(const drt_renderer *r, const drt_camera *cam, FrameParams &fp) {
-    const drt_settings &s = r->settings;
-    const float width = (float)r->width, height = (float)r->height;       // Camera.cu:82 takes floats
+// Camera::GetRay's per-frame constants (Camera.cu:84-103) for a width x height image, computed on the host with the same fp32
+// operations in the same order (host libm for tan).
+static CamConst camera_const(const drt_camera *cam, float width, float height) {      // Camera.cu:82 takes floats
     float theta = cam->vfov_rad / 2;
     float fov_factor = tanf(theta / 2.0f);
     float aspect_ratio = width / height;
@@ -692,11 +691,28 @@ static void fill_frame_params(const drt_renderer *r, const drt_camera *cam, Fram
     V3 disk_u = defocus_radius * right_dir, disk_v = defocus_radius * up_dir;
     V3 fwd_focus = forward_dir * cam->focus_dist;
     auto put = [](float *dst, V3 v) { dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; };
-    std::memcpy(fp.cam_pos, cam->position, 12);
-    put(fp.fwd_focus, fwd_focus); put(fp.horizontal, horizontal); put(fp.vertical, vertical);
-    put(fp.disk_u, disk_u); put(fp.disk_v, disk_v);
-    fp.defocus = !(cam->defocus_angle <= 0);
-    fp.exposure = cam->exposure;
+    CamConst c;
+    std::memcpy(c.cam_pos, cam->position, 12);
+    put(c.fwd_focus, fwd_focus); put(c.horizontal, horizontal); put(c.vertical, vertical);
+    put(c.disk_u, disk_u); put(c.disk_v, disk_v);
+    c.defocus = !(cam->defocus_angle <= 0);
+    c.exposure = cam->exposure;
+    return c;
+}
+
+// Per-frame constants of Camera::GetRay (Camera.cu:84-103) and RayGen (RayGen.cuh:68-72), computed on the
+// host with the same fp32 operations in the same order (host libm for tan/sin/cos).
+static void fill_frame_params(const drt_renderer *r, const drt_camera *cam, FrameParams &fp) {
+    const drt_settings &s = r->settings;
+    auto put = [](float *dst, V3 v) { dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; };
+    if (cam) {                                 // (radiance queries have no camera: their rays carry what it would give)
+        const CamConst c = camera_const(cam, (float)r->width, (float)r->height);
+        std::memcpy(fp.cam_pos, c.cam_pos, 12);
+        std::memcpy(fp.fwd_focus, c.fwd_focus, 12); std::memcpy(fp.horizontal, c.horizontal, 12); std::memcpy(fp.vertical, c.vertical, 12);
+        std::memcpy(fp.disk_u, c.disk_u, 12); std::memcpy(fp.disk_v, c.disk_v, 12);
+        fp.defocus = c.defocus;
+        fp.exposure = c.exposure;
+    }
 
     float sx = sinf(s.sunlight_dir[0]), sy = sinf(s.sunlight_dir[1]), cx = cosf(s.sunlight_dir[0]);
     put(fp.sunpos, V3{ sx * (1 - sy), sy, cx * (1 - sy) } * 100.0f);
@@ -988,6 +1004,88 @@ int drt_renderer_render_guides(drt_renderer *r, const drt_camera *cam, const drt
     (void)hipGetLastError();                   // (see render_batch_impl: only this call's own errors count)
     if (!on_renderer_device(r, guides)) return fail(DRT_ERR_INVALID, "guides must be device memory on the renderer's device");
     return enqueue_guides(r, cam, scene, frame_index, guides, hip_stream ? (hipStream_t)hip_stream : r->stream);
+}
+
+// ------------------------------------------------------------------ camera rays and radiance queries (kernel_radiance.hip)
+// Both share the ray queries' claim heads and HBM stack: they wait for the last query / guide pass of this renderer on another stream,
+// and record the event the next one waits for.
+static int query_order(drt_renderer *r, hipStream_t s) {
+    if (r->query_recorded && r->query_stream != s) HIP_TRY(hipStreamWaitEvent(s, r->ev_query, 0));
+    return DRT_OK;
+}
+static int query_recorded(drt_renderer *r, hipStream_t s) {
+    HIP_TRY(hipEventRecord(r->ev_query, s));
+    r->query_stream = s;
+    r->query_recorded = true;
+    return DRT_OK;
+}
+
+int drt_renderer_camera_rays(drt_renderer *r, const drt_camera *cams, uint32_t n_cams, uint32_t width, uint32_t height,
+                             uint32_t frame_index, drt_path_ray *rays, void *hip_stream) {
+    if (!r || !cams || !rays) return fail(DRT_ERR_INVALID, "null argument");
+    if (frame_index == 0) return fail(DRT_ERR_INVALID, "frame indices start at 1");
+    if (n_cams == 0 || width == 0 || height == 0) return fail(DRT_ERR_INVALID, "zero cameras, width or height");
+    if ((uint64_t)n_cams * width * height > 0x7fffffffull) return fail(DRT_ERR_INVALID, "at most 2^31 - 1 rays per call");
+    if (((uintptr_t)rays & 15u) != 0) return fail(DRT_ERR_INVALID, "rays must be 16-byte aligned");
+    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
+    HIP_TRY(hipSetDevice(r->device));
+    (void)hipGetLastError();                   // (see render_batch_impl: only this call's own errors count)
+    if (!on_renderer_device(r, rays)) return fail(DRT_ERR_INVALID, "rays must be device memory on the renderer's device");
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : r->stream;
+    int rc = query_order(r, s);
+    if (rc != DRT_OK) return rc;
+    const size_t per_cam = (size_t)width * height;
+    for (uint32_t c0 = 0; c0 < n_cams; c0 += kCamsPerLaunch) {     // (one launch up to kCamsPerLaunch cameras)
+        CameraRaysArgs a;
+        a.n_cams = std::min<uint32_t>(kCamsPerLaunch, n_cams - c0);
+        a.rays = rays + c0 * per_cam;
+        a.width = width; a.height = height; a.frame = frame_index;
+        for (uint32_t c = 0; c < a.n_cams; c++) a.cams[c] = camera_const(&cams[c0 + c], (float)width, (float)height);
+        HIP_TRY(launch_camera_rays(a, s));
+    }
+    return query_recorded(r, s);
+}
+
+int drt_renderer_radiance(drt_renderer *r, const drt_scene *scene, const drt_path_ray *rays, float *out, uint32_t n, int32_t accumulate,
+                          void *hip_stream) {
+    if (!r || !scene) return fail(DRT_ERR_INVALID, "null argument");
+    if (n == 0) return DRT_OK;
+    if (!rays || !out) return fail(DRT_ERR_INVALID, "null ray or result pointer");
+    if (((uintptr_t)rays & 15u) != 0 || ((uintptr_t)out & 15u) != 0) return fail(DRT_ERR_INVALID, "rays and results must be 16-byte aligned");
+    if (n > 0x7fffffffu) return fail(DRT_ERR_INVALID, "at most 2^31 - 1 rays per call");
+    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
+    if (r->settings.render_mode == 1) return fail(DRT_ERR_UNSUPPORTED, "debug views are the framebuffer's: radiance needs render_mode 0");
+    HIP_TRY(hipSetDevice(r->device));
+    (void)hipGetLastError();                   // (see render_batch_impl: only this call's own errors count)
+    if (!on_renderer_device(r, rays) || !on_renderer_device(r, out))
+        return fail(DRT_ERR_INVALID, "rays and results must be device memory on the renderer's device");
+    int rc = upload_scene(r, scene);
+    if (rc != DRT_OK) return rc;
+    if (r->bvh_depth > 64) return fail(DRT_ERR_UNSUPPORTED, "BVH deeper than 64 levels (the reference's traversal stack, BVHTraversal.cuh:17)");
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : r->stream;
+    rc = query_order(r, s);
+    if (rc != DRT_OK) return rc;
+    if (!r->rq_heads) HIP_TRY(hipMalloc((void **)&r->rq_heads, sizeof(unsigned int) * kRqHeadWords));
+    const size_t stack_bytes = ray_query_stack_bytes(r->num_cus, r->bvh_depth, false);
+    if (stack_bytes > r->rq_stack_bytes) {
+        if (r->query_recorded) HIP_TRY(hipEventSynchronize(r->ev_query));
+        if (r->rq_stack) { (void)hipFree(r->rq_stack); r->rq_stack = nullptr; r->rq_stack_bytes = 0; }
+        HIP_TRY(hipMalloc(&r->rq_stack, stack_bytes));
+        r->rq_stack_bytes = stack_bytes;
+    }
+    HIP_TRY(hipMemsetAsync(r->rq_heads, 0, sizeof(unsigned int) * kRqHeadWords, s));
+    FrameParams fp;
+    std::memset(&fp, 0, sizeof fp);
+    fill_frame_params(r, nullptr, fp);
+    RadianceArgs a;
+    a.rays = rays; a.out = reinterpret_cast<float4 *>(out); a.n = n;
+    a.stack_levels = (uint32_t)std::max(1, r->bvh_depth);
+    a.refill_min = (uint32_t)r->rq_refill_min;
+    a.accumulate = accumulate != 0;
+    a.heads = r->rq_heads;
+    a.stack_hbm = (uint32_t *)r->rq_stack;
+    HIP_TRY(launch_radiance(r->view, fp, r->scene_has_alpha, a, r->num_cus, s));
+    return query_recorded(r, s);
 }
 
 void drt_default_denoise_params(drt_denoise_params *out) {

@@ -289,6 +289,18 @@ public:
     void Occluded(const Scene &scene, const drt_ray *rays, uint8_t *occluded, uint32_t n, void *stream = nullptr) {
         drt::check(drt_renderer_occluded(handle, scene.handle, rays, occluded, n, stream));
     }
+    // new: RayGen's primary rays of n_cams cameras for a width x height image, frame `frame_index` (drt_renderer_camera_rays): a device
+    // drt_path_ray[n_cams * width * height], enqueued on `stream`
+    void CameraRays(const drt_camera *cams, uint32_t n_cams, uint32_t width, uint32_t height, uint32_t frame_index, drt_path_ray *rays,
+                    void *stream = nullptr) {
+        drt::check(drt_renderer_camera_rays(handle, cams, n_cams, width, height, frame_index, rays, stream));
+    }
+    // new: one path-traced sample per ray with the current settings (drt_renderer_radiance): device float4 out[n], (c, 1) or rgb += c
+    void Radiance(const Scene &scene, const drt_path_ray *rays, float *out, uint32_t n, bool accumulate = false, void *stream = nullptr) {
+        drt_settings s = m_RendererSettings.pod();
+        drt::check(drt_renderer_set_settings(handle, &s));
+        drt::check(drt_renderer_radiance(handle, scene.handle, rays, out, n, accumulate ? 1 : 0, stream));
+    }
     // First-hit guide buffers of frame `frame_index` (drt_renderer_render_guides): a device drt_guide[width*height], enqueued on `stream`
     // new: refit this renderer's device copy of the scene to moved vertices (device pointers, load order; drt_renderer_refit).
     // Blocking; returns the device ms.  Reset the accumulation afterwards, as after a camera move.

@@ -26,7 +26,8 @@ extern "C" {
 #endif
 
 /* 2: drt_counters grew by sampler_tries; drt_group_* and drt_material_model entry points (round 2) are part of it; the ray-query
- * entry points (drt_renderer_trace_rays / _occluded), the guide / denoise entry points and the refit entry points are additions to it */
+ * entry points (drt_renderer_trace_rays / _occluded), the guide / denoise entry points, the refit entry points and the camera-ray /
+ * radiance entry points are additions to it */
 #define DRT_ABI_VERSION 2
 
 typedef enum {
@@ -276,6 +277,31 @@ int           drt_renderer_denoise(drt_renderer *r, const drt_camera *cam, const
                                    float *delta_ms);
 int           drt_renderer_read_denoised_rgba32f(drt_renderer *r, float *dst, size_t dst_floats);        /* width*height*4 */
 void         *drt_renderer_device_denoised(drt_renderer *r);              /* device float4[width*height], NULL before the first denoise */
+
+/* ---- path-traced radiance of arbitrary rays (new; the reference shades only its one camera's pixels) ----
+ * drt_renderer_camera_rays writes rays[c * width * height + x + y * width] (row 0 = bottom) for every camera c < n_cams and pixel:
+ * RayGen's primary ray of that pixel in frame `frame_index`, the rule of the guides (uv = ((float)x / width) * 2 - 1, ((float)y /
+ * height) * 2 - 1, seed0 = (x + y * width) * frame_index in uint32, Camera::GetRay with jitter and defocus, the camera's constants
+ * for a width x height image); `seed` is the seed state AFTER GetRay, `exposure` the camera's.  The renderer's frame size is not
+ * used: any width x height works.  One launch per 32 cameras.
+ * drt_renderer_radiance runs RayGen's path loop (RayGen.cuh:88-169) for one sample per ray, started from make_ray(org, dir) and
+ * seed `seed`: the renderer's current settings (bounce limit, sunlight, sky, tone mapping, gamma) and material model (emissive,
+ * specular, transmission, as the renderer renders them), the tone curve with the ray's `exposure`.  accumulate == 0: out[i] =
+ * (c, 1); else out[i].rgb += c (one fp32 add per component, the renderer's accum += c), alpha untouched.  So
+ * radiance(camera_rays(cam, W, H, f)) is the renderer's frame-f sample of every pixel, and their sum over frames 1..n divided by n
+ * is what ResizeBuffer(W, H), a reset and n renders leave in the framebuffer.  out is float4[n].
+ * Both calls take device pointers on the renderer's device (16-byte aligned); hip_stream NULL = the renderer's stream; they only
+ * enqueue, in order with the renderer's ray queries and guide passes (the same event).  radiance uploads the scene as rendering
+ * does and uses the renderer's refitted copy if there is one.  Neither touches the framebuffer, the accumulation, the sample
+ * count, the counters, kernel info or kernel span, so a sharded renderer may call them.  n == 0 is a successful no-op.
+ * DRT_ERR_INVALID: a NULL, misaligned, host or other-device pointer, frame_index 0, a zero width, height or n_cams, 2^31 rays or
+ * more, a pending drt_renderer_render_batch_async batch.  DRT_ERR_UNSUPPORTED: render_mode DEBUGMODE (debug views stay the
+ * framebuffer's), a tree deeper than 64 levels. */
+typedef struct drt_path_ray { float org[3]; uint32_t seed; float dir[3]; float exposure; } drt_path_ray;   /* 32 B */
+int           drt_renderer_camera_rays(drt_renderer *r, const drt_camera *cams, uint32_t n_cams, uint32_t width, uint32_t height,
+                                       uint32_t frame_index, drt_path_ray *rays, void *hip_stream);
+int           drt_renderer_radiance(drt_renderer *r, const drt_scene *scene, const drt_path_ray *rays, float *out, uint32_t n,
+                                    int32_t accumulate, void *hip_stream);
 
 /* ---- BVH refit for moving geometry (new; the reference rebuilds) ----
  * A refit keeps the tree's topology, node order and triangle order and recomputes the boxes bottom-up from new vertex positions.
