@@ -9,8 +9,11 @@
 // has no data-path collective.  (Round 2 received every 8-row stripe at its rows of the image: no assemble pass, but 118
 // send / receive pairs per 1080p frame on the critical path of a 0.4 ms step; DRT_GROUP_GATHER=stripes still does that, for
 // timing the two against each other.)
-// MORE THAN ONE DEVICE HAS NEVER RUN HERE (one-GPU boxes): what is tested is the address arithmetic (CPU), a group of one, and
-// the RCCL plumbing with the one device sending to itself (DRT_GROUP_FORCE_RCCL).
+// MORE THAN ONE REAL DEVICE HAS NEVER RUN HERE (one-GPU boxes).  What is tested: the address arithmetic (CPU), a group of one, the
+// RCCL plumbing with the one device sending to itself (DRT_GROUP_FORCE_RCCL), and this file's whole N > 1 path on one GPU against
+// a stand-in transport -- DRT_RCCL_LIB=<path> binds the RCCL entry points from that library instead, and DRT_GROUP_SHARE_DEVICE=1
+// (honoured only together with it) lets a device appear more than once, so that groups of 2, 3 and 8 renderers, each on its own
+// stream, share device 0 (tests/cpp/mock_rccl.cpp, tests/test_gpu_group.py).  Real RCCL across devices is what remains.
 // RCCL is loaded at run time (dlopen "librccl.so.1") when a group of more than one device is created: the library
 // has no link-time dependency on it, and a process that already carries another copy (PyTorch ships its own) is not
 // handed a second one unless it asks for a group.
@@ -22,6 +25,9 @@
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -42,12 +48,15 @@ struct Rccl {
     int (*Recv)(void *buf, size_t count, int datatype, int peer, void *comm, hipStream_t stream) = nullptr;
     const char *(*GetErrorString)(int) = nullptr;
     static constexpr int kFloat = 7;               // ncclFloat32 (rccl.h ncclDataType_t)
-    std::string load() {
-        if (lib) return "";
-        for (const char *name : { "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1" }) {
-            lib = dlopen(name, RTLD_NOW | RTLD_LOCAL);
-            if (lib) break;
-        }
+    // `path` empty: RCCL itself; else exactly that library (DRT_RCCL_LIB)
+    std::string load(const std::string &path) {
+        if (lib) return bound() ? "" : "RCCL library lacks an expected symbol";
+        if (!path.empty()) lib = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
+        else
+            for (const char *name : { "librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1" }) {
+                lib = dlopen(name, RTLD_NOW | RTLD_LOCAL);
+                if (lib) break;
+            }
         if (!lib) return std::string("cannot load RCCL: ") + dlerror();
         auto sym = [&](const char *n) { return dlsym(lib, n); };
         CommInitAll = reinterpret_cast<decltype(CommInitAll)>(sym("ncclCommInitAll"));
@@ -57,11 +66,24 @@ struct Rccl {
         Send = reinterpret_cast<decltype(Send)>(sym("ncclSend"));
         Recv = reinterpret_cast<decltype(Recv)>(sym("ncclRecv"));
         GetErrorString = reinterpret_cast<decltype(GetErrorString)>(sym("ncclGetErrorString"));
-        if (!CommInitAll || !CommDestroy || !GroupStart || !GroupEnd || !Send || !Recv) return "RCCL library lacks an expected symbol";
-        return "";
+        return bound() ? "" : "RCCL library lacks an expected symbol";
     }
+    bool bound() const { return CommInitAll && CommDestroy && GroupStart && GroupEnd && Send && Recv; }
 };
-Rccl g_rccl;
+
+// The bound tables, one per library path ("" = RCCL), loaded once and kept for the life of the process: a group keeps a pointer to
+// the one it was created with, so a group on DRT_RCCL_LIB never reaches the RCCL that an earlier group bound, nor the reverse.
+const Rccl *rccl_for(const std::string &path, std::string &err) {
+    static std::mutex mu;
+    static std::map<std::string, std::unique_ptr<Rccl>> tables;
+    std::lock_guard<std::mutex> lock(mu);
+    std::unique_ptr<Rccl> &t = tables[path];
+    if (!t) t.reset(new Rccl());
+    err = t->load(path);
+    return err.empty() ? t.get() : nullptr;
+}
+
+const char *rccl_error_string(const Rccl *rccl, int e) { return rccl && rccl->GetErrorString ? rccl->GetErrorString(e) : "RCCL error"; }
 
 }  // namespace
 
@@ -70,6 +92,7 @@ struct drt_group {
     std::vector<drt_renderer *> renderers;
     std::vector<hipStream_t> streams;
     std::vector<void *> comms;                // RCCL communicators, one per device (empty for a group of one)
+    const Rccl *rccl = nullptr;               // the entry points the communicators came from (null while there are none)
     float *image = nullptr;                   // device 0: the full RGBA32F frame, rows in place
     float *staging = nullptr;                 // device 0: [rank][padded_rows][width] RGBA32F -- the shards as the ranks hold them (slot 0 = device 0's own render target)
     float *accum0 = nullptr;                  // device 0: its renderer's accumulation buffer (bound together with staging slot 0)
@@ -85,11 +108,6 @@ struct drt_group {
     do {                                                                                                    \
         hipError_t e_ = (expr);                                                                             \
         if (e_ != hipSuccess) return drt_internal_fail(DRT_ERR_DEVICE, (std::string(#expr) + ": " + hipGetErrorString(e_)).c_str()); \
-    } while (0)
-#define GROUP_NCCL(expr)                                                                                    \
-    do {                                                                                                    \
-        int e_ = (expr);                                                                                    \
-        if (e_ != 0) return drt_internal_fail(DRT_ERR_DEVICE, (std::string(#expr) + ": " + (g_rccl.GetErrorString ? g_rccl.GetErrorString(e_) : "RCCL error")).c_str()); \
     } while (0)
 
 extern "C" {
@@ -111,9 +129,16 @@ int drt_shard_stripe(uint32_t width, uint32_t height, uint32_t stripe_rows, uint
 
 drt_group *drt_group_create(const int32_t *devices, int32_t n_devices) {
     if (!devices || n_devices < 1 || n_devices > 64) { drt_internal_fail(DRT_ERR_INVALID, "bad device list"); return nullptr; }
-    for (int i = 0; i < n_devices; i++)
-        for (int j = 0; j < i; j++)
-            if (devices[i] == devices[j]) { drt_internal_fail(DRT_ERR_INVALID, "a device appears twice in the group"); return nullptr; }
+    // test hooks: DRT_RCCL_LIB=<path> binds the transport from that library; DRT_GROUP_SHARE_DEVICE=1 then lets a device appear more
+    // than once (several renderers, each on its own stream, on one GPU).  RCCL itself is never handed a repeated device.
+    const char *lib_env = std::getenv("DRT_RCCL_LIB");
+    const std::string rccl_path = lib_env ? lib_env : "";
+    const char *share_env = std::getenv("DRT_GROUP_SHARE_DEVICE");
+    const bool share_device = !rccl_path.empty() && share_env && std::atoi(share_env) != 0;
+    if (!share_device)
+        for (int i = 0; i < n_devices; i++)
+            for (int j = 0; j < i; j++)
+                if (devices[i] == devices[j]) { drt_internal_fail(DRT_ERR_INVALID, "a device appears twice in the group"); return nullptr; }
     drt_group *g = new (std::nothrow) drt_group();
     if (!g) { drt_internal_fail(DRT_ERR_INVALID, "out of host memory"); return nullptr; }
     g->devices.assign(devices, devices + n_devices);
@@ -136,13 +161,14 @@ drt_group *drt_group_create(const int32_t *devices, int32_t n_devices) {
     g->self_gather = n_devices == 1 && std::getenv("DRT_GROUP_FORCE_RCCL") && std::atoi(std::getenv("DRT_GROUP_FORCE_RCCL")) != 0;
     g->per_stripe = std::getenv("DRT_GROUP_GATHER") && std::strcmp(std::getenv("DRT_GROUP_GATHER"), "stripes") == 0;
     if (n_devices > 1 || g->self_gather) {
-        const std::string err = g_rccl.load();
-        if (!err.empty()) { drt_internal_fail(DRT_ERR_DEVICE, err.c_str()); drt_group_destroy(g); return nullptr; }
+        std::string err;
+        g->rccl = rccl_for(rccl_path, err);
+        if (!g->rccl) { drt_internal_fail(DRT_ERR_DEVICE, err.c_str()); drt_group_destroy(g); return nullptr; }
         g->comms.assign((size_t)n_devices, nullptr);
-        const int rc = g_rccl.CommInitAll(g->comms.data(), n_devices, g->devices.data());
+        const int rc = g->rccl->CommInitAll(g->comms.data(), n_devices, g->devices.data());
         if (rc != 0) {
             g->comms.clear();
-            drt_internal_fail(DRT_ERR_DEVICE, (std::string("ncclCommInitAll: ") + (g_rccl.GetErrorString ? g_rccl.GetErrorString(rc) : "error")).c_str());
+            drt_internal_fail(DRT_ERR_DEVICE, (std::string("ncclCommInitAll: ") + rccl_error_string(g->rccl, rc)).c_str());
             drt_group_destroy(g);
             return nullptr;
         }
@@ -154,7 +180,7 @@ void drt_group_destroy(drt_group *g) {
     if (!g) return;
     if (g->pending) (void)drt_group_wait(g, nullptr);      // sends / receives may still target what is freed below
     for (size_t i = 0; i < g->streams.size(); i++) if (hipSetDevice(g->devices[i]) == hipSuccess) (void)hipStreamSynchronize(g->streams[i]);
-    for (void *c : g->comms) if (c && g_rccl.CommDestroy) g_rccl.CommDestroy(c);
+    for (void *c : g->comms) if (c && g->rccl) g->rccl->CommDestroy(c);
     for (size_t i = 0; i < g->renderers.size(); i++) drt_renderer_destroy(g->renderers[i]);
     for (size_t i = 0; i < g->streams.size(); i++) { (void)hipSetDevice(g->devices[i]); (void)hipStreamDestroy(g->streams[i]); }
     if (!g->devices.empty()) (void)hipSetDevice(g->devices[0]);
@@ -226,7 +252,7 @@ int drt_group_render_batch_async(drt_group *g, const drt_camera *cam, const drt_
     int rc = DRT_OK;
     bool in_rccl_group = false;
     auto hip_ok = [&](hipError_t e, const char *what) { if (e != hipSuccess && rc == DRT_OK) rc = drt_internal_fail(DRT_ERR_DEVICE, (std::string(what) + ": " + hipGetErrorString(e)).c_str()); return e == hipSuccess; };
-    auto nccl_ok = [&](int e, const char *what) { if (e != 0 && rc == DRT_OK) rc = drt_internal_fail(DRT_ERR_DEVICE, (std::string(what) + ": " + (g_rccl.GetErrorString ? g_rccl.GetErrorString(e) : "RCCL error")).c_str()); return e == 0; };
+    auto nccl_ok = [&](int e, const char *what) { if (e != 0 && rc == DRT_OK) rc = drt_internal_fail(DRT_ERR_DEVICE, (std::string(what) + ": " + rccl_error_string(g->rccl, e)).c_str()); return e == 0; };
     for (drt_renderer *r : g->renderers) {                 // every device starts tracing before anything is gathered
         rc = drt_renderer_render_batch_async(r, cam, scene, n_frames);
         if (rc != DRT_OK) break;
@@ -245,21 +271,21 @@ int drt_group_render_batch_async(drt_group *g, const drt_camera *cam, const drt_
             if (rest && drt_shard_stripe(g->width, g->height, kStripeRows, 0, world, full, &so, &dof, &cnt))
                 hip_ok(hipMemcpyAsync(g->image + dof, src + so, cnt * sizeof(float), hipMemcpyDeviceToDevice, g->streams[0]), "hipMemcpyAsync");
         }
-        if (rc == DRT_OK && (world > 1 || g->self_gather) && nccl_ok(g_rccl.GroupStart(), "ncclGroupStart")) {
+        if (rc == DRT_OK && (world > 1 || g->self_gather) && nccl_ok(g->rccl->GroupStart(), "ncclGroupStart")) {
             in_rccl_group = true;
             for (uint32_t rank = g->self_gather ? 0 : 1; rank < world && rc == DRT_OK; rank++) {
                 const float *src = static_cast<const float *>(drt_renderer_device_rgba(g->renderers[rank]));
                 for (uint32_t k = 0; rc == DRT_OK; k++) {
                     uint64_t so, dof, cnt;
                     if (!drt_shard_stripe(g->width, g->height, kStripeRows, rank, world, k, &so, &dof, &cnt)) break;
-                    if (nccl_ok(g_rccl.Send(src + so, (size_t)cnt, Rccl::kFloat, 0, g->comms[rank], g->streams[rank]), "ncclSend"))
-                        nccl_ok(g_rccl.Recv(g->image + dof, (size_t)cnt, Rccl::kFloat, (int)rank, g->comms[0], g->streams[0]), "ncclRecv");
+                    if (nccl_ok(g->rccl->Send(src + so, (size_t)cnt, Rccl::kFloat, 0, g->comms[rank], g->streams[rank]), "ncclSend"))
+                        nccl_ok(g->rccl->Recv(g->image + dof, (size_t)cnt, Rccl::kFloat, (int)rank, g->comms[0], g->streams[0]), "ncclRecv");
                 }
             }
         }
     } else if (rc == DRT_OK) {
         // ---- one transfer per peer: its whole shard (contiguous where it was rendered) into its slot of the staging buffer ----
-        if ((world > 1 || g->self_gather) && nccl_ok(g_rccl.GroupStart(), "ncclGroupStart")) {
+        if ((world > 1 || g->self_gather) && nccl_ok(g->rccl->GroupStart(), "ncclGroupStart")) {
             in_rccl_group = true;
             for (uint32_t rank = g->self_gather ? 0 : 1; rank < world && rc == DRT_OK; rank++) {
                 const float *src = static_cast<const float *>(drt_renderer_device_rgba(g->renderers[rank]));
@@ -268,12 +294,12 @@ int drt_group_render_batch_async(drt_group *g, const drt_camera *cam, const drt_
                 // below reads slot 1 -- the image then really is what RCCL moved)
                 float *dst = g->staging + (size_t)(g->self_gather ? 1u : rank) * shard_floats;
                 if (count == 0) continue;
-                if (nccl_ok(g_rccl.Send(src, count, Rccl::kFloat, 0, g->comms[rank], g->streams[rank]), "ncclSend"))
-                    nccl_ok(g_rccl.Recv(dst, count, Rccl::kFloat, (int)rank, g->comms[0], g->streams[0]), "ncclRecv");
+                if (nccl_ok(g->rccl->Send(src, count, Rccl::kFloat, 0, g->comms[rank], g->streams[rank]), "ncclSend"))
+                    nccl_ok(g->rccl->Recv(dst, count, Rccl::kFloat, (int)rank, g->comms[0], g->streams[0]), "ncclRecv");
             }
         }
     }
-    if (in_rccl_group) nccl_ok(g_rccl.GroupEnd(), "ncclGroupEnd");          // (also on the error path: never leave the thread inside an open group)
+    if (in_rccl_group) nccl_ok(g->rccl->GroupEnd(), "ncclGroupEnd");          // (also on the error path: never leave the thread inside an open group)
     if (rc == DRT_OK && !g->per_stripe) {
         // the stripes of every shard to their rows of the image: one kernel on device 0's stream, behind its render and the receives
         if (hip_ok(hipSetDevice(g->devices[0]), "hipSetDevice"))

@@ -366,9 +366,18 @@ int           drt_assemble_shards(const void *gathered, void *image, uint32_t wi
 /* ---- several GPUs of one node behind one object (one process, N devices) ------------------------------
  * Each device renders its 8-row stripes of the frame (drt_renderer_set_shard; seeds use the global pixel index, so the image
  * is bit-identical to the one-GPU image) on its own stream; the stripes are then gathered into device `devices[0]`'s full
- * RGBA32F image over RCCL -- grouped ncclSend / ncclRecv, every stripe received at its rows of the image (no assemble
- * pass), one xGMI link per peer.  RCCL is loaded (dlopen) only when a group of more than one device is created.
- * Same contract as the renderer otherwise: frame index from 1, no-op at max_samples, blocking render returns wall ms. */
+ * RGBA32F image over RCCL -- grouped ncclSend / ncclRecv, one pair per peer moving its whole shard into a staging buffer on
+ * devices[0], then one assemble pass; one xGMI link per peer.  RCCL is loaded (dlopen) only when a group of more than one
+ * device is created.
+ * Same contract as the renderer otherwise: frame index from 1, no-op at max_samples, blocking render returns wall ms.
+ * Environment, read by drt_group_create (defaults: unset):
+ *   DRT_GROUP_GATHER=stripes   one send / receive pair per 8-row stripe, received at its rows of the image (no assemble pass).
+ *   DRT_GROUP_FORCE_RCCL=1     a group of ONE device also gathers through RCCL, sending its shard to itself.
+ *   DRT_RCCL_LIB=<path>        test hook: the RCCL entry points are bound from that library instead of librccl.so.1 (one
+ *                              table per path; a group keeps the one it was created with).
+ *   DRT_GROUP_SHARE_DEVICE=1   test hook, honoured only with DRT_RCCL_LIB: a device may appear more than once (a renderer and
+ *                              a stream per entry, all on that GPU).  Otherwise a repeated device is refused (NULL,
+ *                              drt_last_error "a device appears twice in the group"): RCCL itself never sees one. */
 typedef struct drt_group drt_group;
 drt_group    *drt_group_create(const int32_t *devices, int32_t n_devices);     /* NULL on failure (drt_last_error) */
 void          drt_group_destroy(drt_group *g);

@@ -185,3 +185,28 @@ def test_group_gather_through_rccl_on_one_device(monkeypatch, gather):
         assert np.array_equal(bits(g.GetRenderTargetImage()), bits(r.GetRenderTargetImage()))
         g.RenderBatchAsync(cam, sc, 1); r.RenderBatch(cam, sc, 1)        # left in flight: the next resize (or the destructor) drains it
     del g
+
+
+def test_mock_rccl_builds_and_exports_what_the_group_binds(tmp_path):
+    """tests/cpp/mock_rccl.cpp (the transport of tests/test_gpu_group.py) compiles, and exports the seven entry points that
+    csrc/drt_group.cpp binds by name."""
+    import subprocess
+    from tests.test_gpu_group import NCCL_NAMES, build_mock_rccl
+    lib = build_mock_rccl(tmp_path)
+    out = subprocess.run(["nm", "-D", "--defined-only", lib], capture_output=True, text=True, check=True).stdout
+    exported = {line.split()[-1] for line in out.splitlines() if line.split()[1:2] == ["T"]}
+    assert set(NCCL_NAMES) <= exported, set(NCCL_NAMES) - exported
+
+
+@pytest.mark.parametrize("env", [{}, {"DRT_GROUP_SHARE_DEVICE": "1"}, {"DRT_RCCL_LIB": "libmock_rccl.so"},
+                                 {"DRT_RCCL_LIB": "", "DRT_GROUP_SHARE_DEVICE": "1"}])
+def test_group_refuses_a_repeated_device_without_both_test_hooks(monkeypatch, env):
+    """A device twice in a group is refused before anything touches a GPU -- unless the transport is a test library
+    (DRT_RCCL_LIB) AND DRT_GROUP_SHARE_DEVICE=1: RCCL itself never sees a repeated device."""
+    for k in ("DRT_GROUP_SHARE_DEVICE", "DRT_RCCL_LIB"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    with pytest.raises(drt.DrtError) as e:
+        drt.RendererGroup([0, 1, 0])
+    assert "a device appears twice" in str(e.value)
