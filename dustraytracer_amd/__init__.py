@@ -163,6 +163,21 @@ class DenoiseParams(C.Structure):
             setattr(self, k, v)
 
 
+class TemporalParams(C.Structure):
+    """include/drt.h drt_temporal_params: a-trous passes, history cap, blend floor, the reprojection's normal test and the
+    three edge-stopping sigmas (defaults 5, 32, 0, 0.9, 4, 0.1, 0.1)."""
+    _fields_ = [("iterations", C.c_int32), ("max_history", C.c_int32), ("alpha_min", C.c_float), ("normal_cos_min", C.c_float),
+                ("sigma_luma", C.c_float), ("sigma_normal", C.c_float), ("sigma_albedo", C.c_float)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        _lib.drt_default_temporal_params(C.byref(self))
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError("TemporalParams has no field %r" % k)
+            setattr(self, k, v)
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("samples", "rays", "node_visits", "inner_visits", "tri_tests",
                                            "hits_textured", "hits_flat", "shadow_rays", "inner_visits_shadow",
@@ -277,6 +292,11 @@ _sig("drt_default_denoise_params", None, C.POINTER(DenoiseParams))
 _sig("drt_renderer_denoise", C.c_int, _P, C.POINTER(_CameraPOD), _P, C.POINTER(DenoiseParams), C.POINTER(C.c_float))
 _sig("drt_renderer_read_denoised_rgba32f", C.c_int, _P, _P, C.c_size_t)
 _sig("drt_renderer_device_denoised", _P, _P)
+_sig("drt_default_temporal_params", None, C.POINTER(TemporalParams))
+_sig("drt_renderer_temporal_denoise", C.c_int, _P, C.POINTER(_CameraPOD), _P, C.POINTER(TemporalParams), C.POINTER(C.c_float))
+_sig("drt_renderer_temporal_reset", C.c_int, _P)
+_sig("drt_renderer_read_temporal", C.c_int, _P, C.c_int32, _P, C.c_size_t)
+_sig("drt_renderer_device_temporal", _P, _P, C.c_int32)
 _sig("drt_scene_get_triangle_order", C.c_int, _P, _P, C.c_int32)
 _sig("drt_scene_refit", C.c_int, _P, _P, _P)
 _sig("drt_renderer_refit", C.c_int, _P, _P, _P, _P, C.POINTER(C.c_float), _P)
@@ -526,6 +546,7 @@ class RendererGroup:
 
 FLT_MAX = float(np.finfo(np.float32).max)
 RayHits = collections.namedtuple("RayHits", "t prim u v")     # closest-hit query results (Renderer.traceRays)
+TemporalHistory = collections.namedtuple("TemporalHistory", "color length moments variance weight")  # Renderer.GetTemporalHistory
 Guides = collections.namedtuple("Guides", "albedo normal t prim")  # first-hit guide buffers (Renderer.renderGuides)
 
 
@@ -603,6 +624,7 @@ class Renderer:
         self._device = device
         self.m_RendererSettings = RendererSettings()
         self.m_LastDenoiseMs = 0.0               # device time of the last Denoise (guides + filter)
+        self.m_LastTemporalMs = 0.0              # device time of the last TemporalDenoise (guides + reprojection + filter)
 
     def _ray_query(self, scene, origins, directions, tmin, tmax, occluded):
         import torch                             # (only here: importing the package does not import torch)
@@ -802,6 +824,36 @@ class Renderer:
     def DeviceDenoisedTarget(self):
         """Device address of the last Denoise result (float4 [H * W]), None before the first Denoise."""
         return _lib.drt_renderer_device_denoised(self._h)
+
+    def TemporalDenoise(self, cam, scene, **params):
+        """Temporal reprojection, moment accumulation and the variance-guided a-trous filter of the current framebuffer
+        (drt_renderer_temporal_denoise; `params` = TemporalParams fields): float32 [H, W, 4], row 0 = bottom.  Call once per
+        rendered pose; the per-pixel history travels from call to call through the first-hit geometry."""
+        self._push_settings()
+        p = TemporalParams(**params)
+        ms = C.c_float(0)
+        pod = cam._pod()
+        _check(_lib.drt_renderer_temporal_denoise(self._h, C.byref(pod), scene._h, C.byref(p), C.byref(ms)))
+        self.m_LastTemporalMs = ms.value
+        return self.GetDenoisedImage()
+
+    def resetTemporalHistory(self):
+        """Drop the temporal history (drt_renderer_temporal_reset): the next TemporalDenoise starts at N = 1."""
+        _check(_lib.drt_renderer_temporal_reset(self._h))
+
+    def GetTemporalHistory(self):
+        """The history the last TemporalDenoise stored: TemporalHistory(color [H, W, 3], length [H, W], moments [H, W, 2],
+        variance [H, W], weight [H, W]) -- the unfiltered integrated colour, N, (m1, m2), the variance and the sum of the
+        valid taps' weights (drt_renderer_read_temporal)."""
+        H, W = self.getBufferHeight(), self.getBufferWidth()
+        c, m = np.zeros((H, W, 4), np.float32), np.zeros((H, W, 4), np.float32)
+        _check(_lib.drt_renderer_read_temporal(self._h, 0, c.ctypes.data, c.size))
+        _check(_lib.drt_renderer_read_temporal(self._h, 1, m.ctypes.data, m.size))
+        return TemporalHistory(c[..., :3].copy(), c[..., 3].copy(), m[..., :2].copy(), m[..., 2].copy(), m[..., 3].copy())
+
+    def DeviceTemporalHistory(self, which=0):
+        """Device address of the history's colour (which 0) or moments (1) records, None before the first TemporalDenoise."""
+        return _lib.drt_renderer_device_temporal(self._h, int(which))
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None

@@ -20,6 +20,7 @@
 #include "render_kernels.hpp"
 #include "ray_query.hpp"
 #include "denoise.hpp"
+#include "temporal.hpp"
 #include "refit.hpp"
 #include "radiance.hpp"
 #include "scene_host.hpp"
@@ -151,6 +152,12 @@ struct drt_renderer {
     float4 *dn_buf[2] = { nullptr, nullptr };
     int denoised = -1;
     hipEvent_t ev_dn_start = nullptr, ev_dn_stop = nullptr;
+    // drt_renderer_temporal_denoise: the ping-pong history (three float4 records per pixel and half), allocated by the first call,
+    // freed by resize, destroy and drt_renderer_temporal_reset; tp_cur = the half the last call wrote (-1: no history), tp_cam =
+    // that call's camera as a pinhole.  The filtered result lands in dn_buf.
+    float4 *tp_hist[2][3] = { { nullptr, nullptr, nullptr }, { nullptr, nullptr, nullptr } };
+    int tp_cur = -1;
+    PrevCamera tp_cam;
     // drt_renderer_refit: the uploaded scene's refit metadata (refit.hpp), built by the first refit after an upload and freed
     // with the scene copy; out = the root box and the error word the kernels leave
     bool rf_built = false;
@@ -181,6 +188,11 @@ struct drt_renderer {
         for (float4 *&b : dn_buf) { if (b) (void)hipFree(b); b = nullptr; }
         dn_guides = nullptr;
         denoised = -1;
+    }
+    void free_temporal() {
+        for (auto &half : tp_hist)
+            for (float4 *&b : half) { if (b) (void)hipFree(b); b = nullptr; }
+        tp_cur = -1;
     }
 };
 
@@ -375,6 +387,7 @@ static int realloc_buffers(drt_renderer *r) {
     if (r->accum) { (void)hipFree(r->accum); r->accum = nullptr; }
     if (r->rgba) { (void)hipFree(r->rgba); r->rgba = nullptr; }
     r->free_denoise();
+    r->free_temporal();
     r->local_rows = drt_shard_rows(r->height, r->stripe_rows, r->rank, r->world);
     size_t px = std::max<size_t>((size_t)r->width * r->local_rows, 1);
     HIP_TRY(hipMalloc((void **)&r->accum, px * 3 * sizeof(float)));
@@ -472,6 +485,7 @@ void drt_renderer_destroy(drt_renderer *r) {
     if (r->rq_stack) (void)hipFree(r->rq_stack);
     if (r->ev_query) (void)hipEventDestroy(r->ev_query);
     r->free_denoise();
+    r->free_temporal();
     if (r->ev_dn_start) (void)hipEventDestroy(r->ev_dn_start);
     if (r->ev_dn_stop) (void)hipEventDestroy(r->ev_dn_stop);
     for (hipEvent_t ev : { r->ev_rf_start, r->ev_rf_stop, r->ev_rf_dep })
@@ -1145,6 +1159,125 @@ int drt_renderer_denoise(drt_renderer *r, const drt_camera *cam, const drt_scene
     return DRT_OK;
 }
 
+// ------------------------------------------------------------------ temporal reprojection and the variance-guided filter (kernel_temporal.hip)
+void drt_default_temporal_params(drt_temporal_params *out) {
+    if (!out) return;
+    out->iterations = 5;
+    out->max_history = 32;
+    out->alpha_min = 0.f;
+    out->normal_cos_min = 0.9f;
+    out->sigma_luma = 4.f; out->sigma_normal = 0.1f; out->sigma_albedo = 0.1f;
+}
+
+// The camera as the next call's reprojection sees it: Camera.cu:82's basis and image plane, without jitter and defocus
+static PrevCamera pinhole_of(const drt_camera *cam, float width, float height) {
+    PrevCamera pc;
+    const float fov_factor = tanf((cam->vfov_rad / 2) / 2.0f);
+    pc.plane_h = 2.0f * fov_factor * cam->focus_dist;
+    pc.plane_w = pc.plane_h * (width / height);
+    pc.focus = cam->focus_dist;
+    const V3 f = normalize(V3{ cam->forward[0], cam->forward[1], cam->forward[2] });
+    const V3 right = normalize(cross(f, V3{ 0, 1, 0 })), up = cross(right, f);
+    auto put = [](float *dst, V3 v) { dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; };
+    std::memcpy(pc.pos, cam->position, 12);
+    put(pc.forward, f); put(pc.right, right); put(pc.up, up);
+    return pc;
+}
+
+int drt_renderer_temporal_denoise(drt_renderer *r, const drt_camera *cam, const drt_scene *scene, const drt_temporal_params *p, float *delta_ms) {
+    if (delta_ms) *delta_ms = 0.f;
+    if (!r || !cam || !scene || !p) return fail(DRT_ERR_INVALID, "null argument");
+    if (p->iterations < 0 || p->iterations > 10) return fail(DRT_ERR_INVALID, "iterations must lie in [0, 10]");
+    if (p->max_history < 1) return fail(DRT_ERR_INVALID, "max_history must be at least 1");
+    if (!(p->alpha_min >= 0.f && p->alpha_min <= 1.f)) return fail(DRT_ERR_INVALID, "alpha_min must lie in [0, 1]");
+    if (!std::isfinite(p->normal_cos_min)) return fail(DRT_ERR_INVALID, "normal_cos_min must be finite");
+    for (float sigma : { p->sigma_luma, p->sigma_normal, p->sigma_albedo })
+        if (!std::isfinite(sigma) || !(sigma > 0.f)) return fail(DRT_ERR_INVALID, "every sigma must be finite and > 0");
+    if (r->width == 0 || r->height == 0) return fail(DRT_ERR_INVALID, "ResizeBuffer has not been called");
+    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
+    if (r->world > 1) return fail(DRT_ERR_UNSUPPORTED, "the temporal filter needs the whole frame: a sharded renderer (world > 1) holds only its stripes");
+    HIP_TRY(hipSetDevice(r->device));
+    (void)hipGetLastError();
+    const size_t px = (size_t)r->width * r->height;
+    if (!r->dn_guides) {
+        HIP_TRY(hipMalloc(&r->dn_guides, px * sizeof(drt_guide)));
+        HIP_TRY(hipMalloc((void **)&r->dn_buf[0], px * sizeof(float4)));
+        HIP_TRY(hipMalloc((void **)&r->dn_buf[1], px * sizeof(float4)));
+    }
+    if (!r->tp_hist[0][0]) {
+        r->tp_cur = -1;
+        for (auto &half : r->tp_hist)
+            for (float4 *&b : half) HIP_TRY(hipMalloc((void **)&b, px * sizeof(float4)));
+    }
+    if (!r->ev_dn_start) HIP_TRY(hipEventCreate(&r->ev_dn_start));
+    if (!r->ev_dn_stop) HIP_TRY(hipEventCreate(&r->ev_dn_stop));
+    r->denoised = -1;
+    HIP_TRY(hipEventRecord(r->ev_dn_start, r->stream));
+    int rc = enqueue_guides(r, cam, scene, 1, r->dn_guides, r->stream);
+    if (rc != DRT_OK) return rc;
+
+    const int half = r->tp_cur < 0 ? 0 : r->tp_cur ^ 1;
+    const CamConst cc = camera_const(cam, (float)r->width, (float)r->height);
+    ReprojectArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.frame = reinterpret_cast<const float4 *>(r->cur_rgba());
+    a.guides = r->dn_guides;
+    a.cur = TemporalHistory{ r->tp_hist[half][0], r->tp_hist[half][1], r->tp_hist[half][2] };
+    a.prev = TemporalHistory{ r->tp_hist[half ^ 1][0], r->tp_hist[half ^ 1][1], r->tp_hist[half ^ 1][2] };
+    a.width = r->width; a.height = r->height;
+    a.has_prev = r->tp_cur >= 0;
+    std::memcpy(a.cam_pos, cc.cam_pos, 12); std::memcpy(a.fwd_focus, cc.fwd_focus, 12);
+    std::memcpy(a.horizontal, cc.horizontal, 12); std::memcpy(a.vertical, cc.vertical, 12);
+    if (a.has_prev) a.pc = r->tp_cam;
+    a.max_history = (float)p->max_history; a.alpha_min = p->alpha_min; a.normal_cos_min = p->normal_cos_min;
+    r->tp_cur = -1;                            // (a failure below leaves no history)
+    HIP_TRY(launch_temporal_reproject(a, r->num_cus, r->stream));
+
+    int out = 0;
+    if (p->iterations == 0) {
+        HIP_TRY(launch_temporal_copy(a.cur.color, r->dn_buf[0], (uint32_t)px, r->stream));
+    } else {
+        for (int i = 0; i < p->iterations; i++, out ^= 1) {
+            AtrousVarPass ps;
+            ps.in = i == 0 ? a.cur.color : r->dn_buf[out ^ 1];
+            ps.var_src = i == 0 ? a.cur.moments : nullptr;
+            ps.out = r->dn_buf[out];
+            ps.guides = r->dn_guides;
+            ps.width = r->width; ps.height = r->height; ps.step = 1u << i;
+            ps.last = i == p->iterations - 1;
+            ps.sigma_luma = p->sigma_luma;
+            ps.k_normal = 1.0f / (p->sigma_normal * p->sigma_normal);
+            ps.k_albedo = 1.0f / (p->sigma_albedo * p->sigma_albedo);
+            HIP_TRY(launch_atrous_var(ps, r->stream));
+        }
+        out ^= 1;
+    }
+    HIP_TRY(hipEventRecord(r->ev_dn_stop, r->stream));
+    HIP_TRY(hipEventSynchronize(r->ev_dn_stop));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, r->ev_dn_start, r->ev_dn_stop));
+    if (delta_ms) *delta_ms = ms;
+    r->tp_cam = pinhole_of(cam, (float)r->width, (float)r->height);
+    r->tp_cur = half;
+    r->denoised = out;
+    return DRT_OK;
+}
+
+int drt_renderer_temporal_reset(drt_renderer *r) {
+    if (!r) return fail(DRT_ERR_INVALID, "null argument");
+    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
+    if (r->tp_hist[0][0]) {
+        HIP_TRY(hipSetDevice(r->device));
+        HIP_TRY(hipStreamSynchronize(r->stream));
+    }
+    r->free_temporal();
+    return DRT_OK;
+}
+
+void *drt_renderer_device_temporal(drt_renderer *r, int32_t which) {
+    return r && r->tp_cur >= 0 && (which == 0 || which == 1) ? (void *)r->tp_hist[r->tp_cur][which == 0 ? 0 : 2] : nullptr;
+}
+
 // ------------------------------------------------------------------ refit of the device copy (kernel_refit.hip)
 // The metadata of the uploaded scene: load order, stored normals' averages, the leaves and the interior nodes by height, every
 // node's destination box in pack()'s numbering of the records.
@@ -1329,6 +1462,13 @@ int drt_renderer_read_accum(drt_renderer *r, float *dst, size_t dst_floats) {
 int drt_renderer_read_denoised_rgba32f(drt_renderer *r, float *dst, size_t dst_floats) {
     if (r && r->denoised < 0) return fail(DRT_ERR_INVALID, "no denoised image yet: drt_renderer_denoise first");
     return read_back(r, r ? (const float *)r->dn_buf[r->denoised] : nullptr, 4, dst, dst_floats);
+}
+
+int drt_renderer_read_temporal(drt_renderer *r, int32_t which, float *dst, size_t dst_floats) {
+    if (!r || !dst) return fail(DRT_ERR_INVALID, "null argument");
+    if (which < 0 || which > 1) return fail(DRT_ERR_INVALID, "which must be 0 (colour, N) or 1 (moments, variance, weight)");
+    if (r->tp_cur < 0) return fail(DRT_ERR_INVALID, "no temporal history yet: drt_renderer_temporal_denoise first");
+    return read_back(r, (const float *)r->tp_hist[r->tp_cur][which == 0 ? 0 : 2], 4, dst, dst_floats);
 }
 
 static int debug_check_exact(int32_t device, int which, uint64_t *mismatches, uint64_t *fast_path_count) {

@@ -3,11 +3,14 @@
 //   g++ -std=c++17 -Iinclude examples/drt_render.cpp -Ldustraytracer_amd -ldrt_hip -Wl,-rpath,$PWD/dustraytracer_amd -o drt_render
 //   ./drt_render models/cornell_box.glb out.pfm 1920 1080 8 8  3.6 1.25 0  -1 0 0
 //   ./drt_render models/cornell_box.glb out.png 1920 1080 4 8  3.6 1.25 0  -1 0 0  --denoise     (writes the a-trous denoised frame)
+//   ./drt_render models/cornell_box.glb out.png 1920 1080 1 8  3.6 1.25 0  -1 0 0  --temporal 12  (12 poses of a small orbit ending at the
+//                                                  given pose, 1 spp each, temporally accumulated and filtered: writes the last pose)
 //   DRT_DEVICES=0,1,2,3,4,5,6,7 ./drt_render models/room.glb out.pfm 3840 2160 64 16  0 1.4 2  0 0 -1     (all GPUs of the node: stripes + RCCL gather)
 #include <DustRayTracer.hpp>
 #include <DustRayTracerGL.hpp>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -19,8 +22,13 @@ using drtgl::write_png_rgba8;      // the minimal PNG writer lives in DustRayTra
 int main(int argc, char **argv) {
     const bool denoise = argc > 1 && std::strcmp(argv[argc - 1], "--denoise") == 0;     // optional, always last
     if (denoise) argc--;
-    if (argc < 7) {
-        std::fprintf(stderr, "usage: %s scene.glb out.pfm width height spp depth [px py pz fx fy fz] [--denoise]\n", argv[0]);
+    int temporal = 0;                                     // --temporal K: optional, last (before --denoise)
+    if (argc > 2 && std::strcmp(argv[argc - 2], "--temporal") == 0) {
+        temporal = std::atoi(argv[argc - 1]);
+        argc -= 2;
+    }
+    if (argc < 7 || temporal < 0) {
+        std::fprintf(stderr, "usage: %s scene.glb out.pfm width height spp depth [px py pz fx fy fz] [--temporal K] [--denoise]\n", argv[0]);
         return 2;
     }
     try {
@@ -57,6 +65,28 @@ int main(int argc, char **argv) {
             renderer.Denoise(&cam, scene, &dms, p.iterations, p.sigma_color, p.sigma_normal, p.sigma_albedo);
             renderer.ReadDenoisedTarget(rgba.data());
             std::printf("denoised: %d passes, %.3f ms\n", p.iterations, dms);
+        }
+        if (temporal > 0) {
+            // K poses at 1 spp each on an orbit (0.01 rad per pose about the vertical through the point 3 units ahead) that ends
+            // at the given pose; every pose is reset, rendered and handed to the temporal filter, which carries the history
+            const float px = cam.m_Position.x, pz = cam.m_Position.z, fx = cam.m_Forward_dir.x, fz = cam.m_Forward_dir.z;
+            const float fl = std::sqrt(fx * fx + cam.m_Forward_dir.y * cam.m_Forward_dir.y + fz * fz);
+            const float cx = px + fx / fl * 3.0f, cz = pz + fz / fl * 3.0f;
+            float tms = 0, total = 0;
+            for (int k = 0; k < temporal; k++) {
+                const float ang = 0.01f * (float)(k - (temporal - 1)), co = std::cos(ang), si = std::sin(ang);
+                Camera pose = cam;
+                pose.m_Position.x = cx + (px - cx) * co - (pz - cz) * si;
+                pose.m_Position.z = cz + (px - cx) * si + (pz - cz) * co;
+                pose.m_Forward_dir.x = fx * co - fz * si;
+                pose.m_Forward_dir.z = fx * si + fz * co;
+                renderer.resetAccumulationBuffer();
+                renderer.RenderBatch(&pose, scene, 1, &ms);
+                renderer.TemporalDenoise(&pose, scene, &tms);
+                total += tms;
+            }
+            renderer.ReadDenoisedTarget(rgba.data());
+            std::printf("temporal: %d poses, %.3f ms per pose\n", temporal, total / (float)temporal);
         }
         const std::string out(argv[2]);
         if (out.size() > 4 && out.compare(out.size() - 4, 4, ".png") == 0) {

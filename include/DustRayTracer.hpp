@@ -330,6 +330,23 @@ public:
         drt::check(drt_renderer_read_denoised_rgba32f(handle, dst, (size_t)getBufferWidth() * getBufferHeight() * 4));
     }
     void *DeviceDenoisedTarget() { return drt_renderer_device_denoised(handle); }
+    // Temporal reprojection + variance-guided a-trous filter of the current frame (drt_renderer_temporal_denoise; blocking): call
+    // once per rendered pose, the history travels from call to call.  params NULL = drt_default_temporal_params.  The result is
+    // read with ReadDenoisedTarget / DeviceDenoisedTarget.  A multi-device renderer is refused (DRT_ERR_UNSUPPORTED).
+    void TemporalDenoise(Camera *cam, const Scene &scene, float *delta, const drt_temporal_params *params = nullptr) {
+        drt_temporal_params p;
+        drt_default_temporal_params(&p);
+        if (params) p = *params;
+        drt_settings s = m_RendererSettings.pod();
+        drt_camera c = cam->pod();
+        drt::check(drt_renderer_set_settings(handle, &s));
+        drt::check(drt_renderer_temporal_denoise(handle, &c, scene.handle, &p, delta));
+    }
+    void ResetTemporalHistory() { drt::check(drt_renderer_temporal_reset(handle)); }      // after a cut or moved geometry: N = 1 again
+    // the history of the last TemporalDenoise, width*height*4 floats: which 0 = (colour rgb, N), 1 = (m1, m2, variance, weight sum)
+    void ReadTemporal(int which, float *dst) {
+        drt::check(drt_renderer_read_temporal(handle, which, dst, (size_t)getBufferWidth() * getBufferHeight() * 4));
+    }
 
     RendererSettings m_RendererSettings;
     drt_renderer *handle = nullptr;       // the (first) device's renderer

@@ -278,6 +278,67 @@ int           drt_renderer_denoise(drt_renderer *r, const drt_camera *cam, const
 int           drt_renderer_read_denoised_rgba32f(drt_renderer *r, float *dst, size_t dst_floats);        /* width*height*4 */
 void         *drt_renderer_device_denoised(drt_renderer *r);              /* device float4[width*height], NULL before the first denoise */
 
+/* ---- temporal reprojection and the variance-guided a-trous filter (new; SVGF, Schied et al. 2017, on the guides above) ----
+ * drt_renderer_temporal_denoise carries a per-pixel history from call to call.  One call, for the current framebuffer c (RGB,
+ * display-referred, whatever has been rendered since the last reset) and camera `cam`, W x H pixels p = (x, y), row 0 = bottom.
+ * All arithmetic is fp32, one rounding per operation, in the order written (sums left to right); dot(a, b) = a.x b.x + a.y b.y +
+ * a.z b.z, normalize(v) = v * (1 / sqrtf(dot(v, v))), lum(c) = 0.2126f c.r + 0.7152f c.g + 0.0722f c.b.
+ * (a) g = the guides of frame 1 for `cam` (drt_renderer_render_guides: what drt_renderer_denoise uses).
+ * (b) Reproject and accumulate.  l = lum(c(p)).  The pixel has NO history on the first call after a reset and where g.prim < 0.
+ *   Otherwise u = ((float)x / W) * 2 - 1, v = ((float)y / H) * 2 - 1, d0 = normalize(fwd_focus + u * horizontal + v * vertical)
+ *   (Camera::GetRay's direction without jitter and defocus: the jitter is +-0.00175 in uv, +-1.7 pixels at 1080p, and reprojecting
+ *   the jittered hit would blur a still camera's image), P = cam_pos + d0 * g.t(p).  With the PREVIOUS call's camera (position
+ *   pos', forward f' = normalize(forward), right' = normalize(cross(f', (0,1,0))), up' = cross(right', f'), focus' = focus_dist,
+ *   plane_h' = 2 * tanf((vfov_rad / 2) / 2) * focus', plane_w' = plane_h' * ((float)W / (float)H): Camera.cu:82's, the tan(vfov/4)
+ *   quirk included): pv = P - pos', z = dot(pv, f'); no history unless z > 0;
+ *     su = (dot(pv, right') * focus') / (z * plane_w'),  sv = (dot(pv, up') * focus') / (z * plane_h'),
+ *     fx = ((su + 1) * 0.5f) * W,  fy = ((sv + 1) * 0.5f) * H;  no history unless -1 < fx < W and -1 < fy < H.
+ *   Taps j = 0, 1 (outer), i = 0, 1 (inner) at q = (floorf(fx) + i, floorf(fy) + j), weight w = wx_i * wy_j with wx_1 = fx -
+ *   floorf(fx), wx_0 = 1 - wx_1 (wy alike).  A tap is valid iff q is inside the image, its stored N >= 1 (every record a call stores
+ *   has: the test is "a previous call exists"), its stored prim == g.prim(p) and dot(n_stored(q), g.normal(p)) >= normal_cos_min.
+ *   On a planar triangle the same prim through nearly the same pixel is the same surface point: prim equality is the
+ *   disocclusion test, and it holds across refits, which keep the triangle order.  Over the valid taps in tap order, from 0:
+ *   S += w, hc += colour(q) * w, hN += N(q) * w, h1 += m1(q) * w, h2 += m2(q) * w.
+ *     S >= 0.01f: N = fminf(floorf(hN / S + 0.5f) + 1, (float)max_history), a = fmaxf(1 / N, alpha_min),
+ *                 colour = (hc / S) * (1 - a) + c * a,  m1 = (h1 / S) * (1 - a) + l * a,  m2 = (h2 / S) * (1 - a) + (l * l) * a.
+ *     else:       N = 1, colour = c, m1 = l, m2 = l * l.
+ *   Variance: N >= 4: fmaxf(0, m2 - m1 * m1).  N < 4: over the 7x7 window (dy = -3..3 outer, dx inner, coordinates clamped to the
+ *   image) of THIS call's integrated colour, the pixels q with g.prim(q) == g.prim(p): s1 += lum(colour(q)), s2 += lum * lum, n += 1;
+ *   variance = fmaxf(0, s2 / n - (s1 / n) * (s1 / n)) * (4 / N).
+ *   Stored in the other half of a ping-pong history: (colour, N), (g.normal, g.prim), (m1, m2, variance, S); the camera on the host.
+ *   No transcendental: with -ffp-contract=off and correctly rounded / and sqrtf this stage is reproducible bit for bit.
+ * (c) Variance-guided a-trous: c_0 = the integrated colour, var_0 = the variance of (b); passes i = 0 .. iterations-1 with the
+ *   taps, h, clamping, normal and albedo terms of drt_renderer_denoise.  gv_i(p) = the 3x3 Gaussian of var_i (dy = -1..1 outer,
+ *   dx inner, clamped, weights {0.25, 0.5, 0.25}[dy] * {0.25, 0.5, 0.25}[dx], summed from 0), r = 1 / (sigma_luma * sqrtf(gv_i(p))
+ *   + 1e-4f),
+ *     e = fabsf(lum(c_i(p)) - lum(c_i(q))) * r + |n(p)-n(q)|^2 * (1 / sigma_normal^2) + |alb(p)-alb(q)|^2 * (1 / sigma_albedo^2),
+ *     w = h[a] h[b] expf(-e),  c_{i+1}(p) = sum w c_i(q) / sum w,  var_{i+1}(p) = sum (w * w) var_i(q) / ((sum w) * (sum w)).
+ *   The result (c_K, alpha 1; iterations 0 = the integrated colour itself) lands in the renderer's denoised target:
+ *   drt_renderer_read_denoised_rgba32f and drt_renderer_device_denoised read it.  The history keeps the UNFILTERED colour.
+ * Side effects: none beyond the history and the denoised target (accumulation buffer, framebuffer, sample count, counters, kernel
+ * info and span untouched).  The history is allocated by the first call and freed by resize, destroy and
+ * drt_renderer_temporal_reset (the next call then starts at N = 1).  Blocking; *delta_ms = device time of all stages.
+ * drt_renderer_read_temporal / drt_renderer_device_temporal: which 0 = (colour rgb, N), 1 = (m1, m2, variance, S) of the last call,
+ * float4[width * height].
+ * DRT_ERR_INVALID: a NULL argument, no frame size, a pending drt_renderer_render_batch_async batch, iterations outside [0, 10],
+ * max_history < 1, alpha_min outside [0, 1], a normal_cos_min or sigma that is not finite, a sigma not > 0, `which` outside 0..1, a
+ * too short dst, a read before the first call.  DRT_ERR_UNSUPPORTED: a sharded renderer (world > 1), a tree deeper than 64 levels.
+ * Out of scope: motion vectors for geometry that moves between calls (after a refit the caller resets the history or accepts that
+ * moved triangles reproject as if they were static); feeding the filtered colour back into the history; drt_group. */
+typedef struct drt_temporal_params {
+    int32_t iterations;      /* a-trous passes, 0..10, default 5 */
+    int32_t max_history;     /* history length cap, >= 1, default 32 */
+    float   alpha_min;       /* floor of the blend weight, [0, 1], default 0 */
+    float   normal_cos_min;  /* a tap is valid only if dot(n_prev, n_cur) >= this, default 0.9 */
+    float   sigma_luma, sigma_normal, sigma_albedo;   /* default 4, 0.1, 0.1 */
+} drt_temporal_params;
+void          drt_default_temporal_params(drt_temporal_params *out);
+int           drt_renderer_temporal_denoise(drt_renderer *r, const drt_camera *cam, const drt_scene *scene,
+                                            const drt_temporal_params *p, float *delta_ms);
+int           drt_renderer_temporal_reset(drt_renderer *r);               /* drop the history; the next call starts at N = 1 */
+int           drt_renderer_read_temporal(drt_renderer *r, int32_t which, float *dst, size_t dst_floats);
+void         *drt_renderer_device_temporal(drt_renderer *r, int32_t which);     /* device float4[width*height], NULL before the first call */
+
 /* ---- path-traced radiance of arbitrary rays (new; the reference shades only its one camera's pixels) ----
  * drt_renderer_camera_rays writes rays[c * width * height + x + y * width] (row 0 = bottom) for every camera c < n_cams and pixel:
  * RayGen's primary ray of that pixel in frame `frame_index`, the rule of the guides (uv = ((float)x / width) * 2 - 1, ((float)y /
