@@ -297,6 +297,9 @@ _sig("drt_renderer_temporal_denoise", C.c_int, _P, C.POINTER(_CameraPOD), _P, C.
 _sig("drt_renderer_temporal_reset", C.c_int, _P)
 _sig("drt_renderer_read_temporal", C.c_int, _P, C.c_int32, _P, C.c_size_t)
 _sig("drt_renderer_device_temporal", _P, _P, C.c_int32)
+_sig("drt_renderer_track_motion", C.c_int, _P, C.c_int32)
+_sig("drt_renderer_motion_advance", C.c_int, _P)
+_sig("drt_renderer_motion_vectors", C.c_int, _P, C.POINTER(_CameraPOD), C.POINTER(_CameraPOD), _P, _P, _P)
 _sig("drt_scene_get_triangle_order", C.c_int, _P, _P, C.c_int32)
 _sig("drt_scene_refit", C.c_int, _P, _P, _P)
 _sig("drt_renderer_refit", C.c_int, _P, _P, _P, _P, C.POINTER(C.c_float), _P)
@@ -854,6 +857,34 @@ class Renderer:
     def DeviceTemporalHistory(self, which=0):
         """Device address of the history's colour (which 0) or moments (1) records, None before the first TemporalDenoise."""
         return _lib.drt_renderer_device_temporal(self._h, int(which))
+
+    def trackMotion(self, enable=True):
+        """Follow geometry that Renderer.refit moves (drt_renderer_track_motion): the first refit after a TemporalDenoise keeps
+        the triangles as they were, and the next TemporalDenoise reprojects every moved triangle's pixels through that state.
+        False frees the snapshot."""
+        _check(_lib.drt_renderer_track_motion(self._h, 1 if enable else 0))
+
+    def advanceMotion(self):
+        """The geometry as it is now is the previous geometry from here on (drt_renderer_motion_advance): what TemporalDenoise
+        does by itself, for callers that use motionVectors with a filter of their own."""
+        _check(_lib.drt_renderer_motion_advance(self._h))
+
+    def motionVectors(self, cam, scene, prev_cam=None, as_torch=False):
+        """Screen-space motion of every pixel's first hit (drt_renderer_motion_vectors): float32 [H, W, 4] = (fx - x, fy - y, z,
+        flag), where (fx, fy) is the pixel position and z the depth in `prev_cam` (None = the camera of the last TemporalDenoise)
+        of the point the pixel shows, carried back onto the geometry of the previous call; flag 0 = none (miss, or behind
+        prev_cam), 1 = static, 2 = moved.  Row 0 = bottom.  as_torch=True: a device tensor, the work enqueued on the current
+        torch stream; else a numpy array."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        self._push_settings()
+        out = torch.empty((self.getBufferHeight(), self.getBufferWidth(), 4), dtype=torch.float32, device=dev)
+        pod = cam._pod()
+        prev = prev_cam._pod() if prev_cam is not None else None
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _check(_lib.drt_renderer_motion_vectors(self._h, C.byref(pod), C.byref(prev) if prev is not None else None, scene._h,
+                                                out.data_ptr() if out.numel() else None, stream))
+        return out if as_torch else out.cpu().numpy()
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None

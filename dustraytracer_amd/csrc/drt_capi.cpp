@@ -22,6 +22,7 @@
 #include "denoise.hpp"
 #include "temporal.hpp"
 #include "refit.hpp"
+#include "motion.hpp"
 #include "radiance.hpp"
 #include "scene_host.hpp"
 #include "bvh_build_device.hpp"
@@ -69,6 +70,13 @@ struct DeviceArray {
         hipError_t e = hipMalloc((void **)&ptr, bytes);
         if (e != hipSuccess) { ptr = nullptr; return e; }
         if (!host.empty()) e = hipMemcpy(ptr, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice);
+        return e;
+    }
+    hipError_t alloc(size_t n) {                 // uninitialised
+        release();
+        hipError_t e = hipMalloc((void **)&ptr, std::max<size_t>(n, 1) * sizeof(T));
+        if (e != hipSuccess) { ptr = nullptr; return e; }
+        count = n;
         return e;
     }
     void release() { if (ptr) (void)hipFree(ptr); ptr = nullptr; count = 0; }
@@ -172,6 +180,12 @@ struct drt_renderer {
     int rf_top_nodes = kRefitTopNodes;         // DRT_REFIT_TOP: 0 = one launch per height up to the root
     int rf_launches = 0;
     hipEvent_t ev_rf_start = nullptr, ev_rf_stop = nullptr, ev_rf_dep = nullptr;
+    // drt_renderer_track_motion: mv_snap = the TriHot records as they were before the first refit since the last temporal call /
+    // drt_renderer_motion_advance (valid while mv_armed; the buffer is kept for reuse, dropped with the scene copy),
+    // mv_guides = drt_renderer_motion_vectors' guide buffer
+    bool mv_track = false, mv_armed = false;
+    DeviceArray<TriHot> mv_snap;
+    void *mv_guides = nullptr;
 
     float *cur_accum() const { return ext_accum ? ext_accum : accum; }
     float *cur_rgba() const { return ext_rgba ? ext_rgba : rgba; }
@@ -181,7 +195,13 @@ struct drt_renderer {
         rf_order.release(); rf_avg.release(); rf_ext.release(); rf_leaves.release(); rf_levels.release();
         rf_height_begin.release(); rf_out.release();
         rf_built = false;
+        mv_snap.release();
+        mv_armed = false;
         uploaded_scene = nullptr;
+    }
+    void free_motion_guides() {
+        if (mv_guides) (void)hipFree(mv_guides);
+        mv_guides = nullptr;
     }
     void free_denoise() {
         if (dn_guides) (void)hipFree(dn_guides);
@@ -388,6 +408,7 @@ static int realloc_buffers(drt_renderer *r) {
     if (r->rgba) { (void)hipFree(r->rgba); r->rgba = nullptr; }
     r->free_denoise();
     r->free_temporal();
+    r->free_motion_guides();
     r->local_rows = drt_shard_rows(r->height, r->stripe_rows, r->rank, r->world);
     size_t px = std::max<size_t>((size_t)r->width * r->local_rows, 1);
     HIP_TRY(hipMalloc((void **)&r->accum, px * 3 * sizeof(float)));
@@ -486,6 +507,7 @@ void drt_renderer_destroy(drt_renderer *r) {
     if (r->ev_query) (void)hipEventDestroy(r->ev_query);
     r->free_denoise();
     r->free_temporal();
+    r->free_motion_guides();
     if (r->ev_dn_start) (void)hipEventDestroy(r->ev_dn_start);
     if (r->ev_dn_stop) (void)hipEventDestroy(r->ev_dn_stop);
     for (hipEvent_t ev : { r->ev_rf_start, r->ev_rf_stop, r->ev_rf_dep })
@@ -1184,6 +1206,16 @@ static PrevCamera pinhole_of(const drt_camera *cam, float width, float height) {
     return pc;
 }
 
+// The current records and the armed snapshot as the kernels of kernel_motion.hip read them (snapshot NULL = nothing armed: every
+// pixel static)
+static MotionGeometry motion_geometry(const drt_renderer *r) {
+    MotionGeometry geo;
+    geo.hot = reinterpret_cast<const float4 *>(r->d_hot.ptr);
+    geo.snapshot = nullptr;
+    if (r->mv_armed && r->mv_snap.count == r->d_hot.count && r->d_hot.count != 0) geo.snapshot = reinterpret_cast<const float4 *>(r->mv_snap.ptr);
+    return geo;
+}
+
 int drt_renderer_temporal_denoise(drt_renderer *r, const drt_camera *cam, const drt_scene *scene, const drt_temporal_params *p, float *delta_ms) {
     if (delta_ms) *delta_ms = 0.f;
     if (!r || !cam || !scene || !p) return fail(DRT_ERR_INVALID, "null argument");
@@ -1231,7 +1263,12 @@ int drt_renderer_temporal_denoise(drt_renderer *r, const drt_camera *cam, const 
     if (a.has_prev) a.pc = r->tp_cam;
     a.max_history = (float)p->max_history; a.alpha_min = p->alpha_min; a.normal_cos_min = p->normal_cos_min;
     r->tp_cur = -1;                            // (a failure below leaves no history)
-    HIP_TRY(launch_temporal_reproject(a, r->num_cus, r->stream));
+    if (r->mv_armed) {                         // geometry moved since the last call: P' and n' of the moved rule (kernel_motion.hip)
+        HIP_TRY(launch_motion_reproject(a, motion_geometry(r), r->stream));
+        r->mv_armed = false;                   // the geometry as it is now is the previous geometry of the next call
+    } else {
+        HIP_TRY(launch_temporal_reproject(a, r->num_cus, r->stream));
+    }
 
     int out = 0;
     if (p->iterations == 0) {
@@ -1276,6 +1313,58 @@ int drt_renderer_temporal_reset(drt_renderer *r) {
 
 void *drt_renderer_device_temporal(drt_renderer *r, int32_t which) {
     return r && r->tp_cur >= 0 && (which == 0 || which == 1) ? (void *)r->tp_hist[r->tp_cur][which == 0 ? 0 : 2] : nullptr;
+}
+
+// ------------------------------------------------------------------ motion tracking and motion vectors (kernel_motion.hip)
+int drt_renderer_track_motion(drt_renderer *r, int32_t enable) {
+    if (!r) return fail(DRT_ERR_INVALID, "null argument");
+    r->mv_track = enable != 0;
+    if (!r->mv_track) {
+        if (r->mv_snap.ptr) {
+            HIP_TRY(hipSetDevice(r->device));
+            HIP_TRY(hipDeviceSynchronize());     // (a motion-vector pass on a caller's stream may still read them)
+        }
+        r->mv_snap.release();
+        r->mv_armed = false;
+    }
+    return DRT_OK;
+}
+
+int drt_renderer_motion_advance(drt_renderer *r) {
+    if (!r) return fail(DRT_ERR_INVALID, "null argument");
+    r->mv_armed = false;
+    return DRT_OK;
+}
+
+int drt_renderer_motion_vectors(drt_renderer *r, const drt_camera *cam, const drt_camera *prev_cam, const drt_scene *scene, float *out,
+                                void *hip_stream) {
+    if (!r || !cam || !scene || !out) return fail(DRT_ERR_INVALID, "null argument");
+    if (r->width == 0 || r->height == 0) return fail(DRT_ERR_INVALID, "ResizeBuffer has not been called");
+    if (((uintptr_t)out & 15u) != 0) return fail(DRT_ERR_INVALID, "out must be 16-byte aligned");
+    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
+    if (!prev_cam && r->tp_cur < 0) return fail(DRT_ERR_INVALID, "no previous camera: pass prev_cam or call drt_renderer_temporal_denoise first");
+    HIP_TRY(hipSetDevice(r->device));
+    (void)hipGetLastError();
+    if (!on_renderer_device(r, out)) return fail(DRT_ERR_INVALID, "out must be device memory on the renderer's device");
+    if (r->world > 1) return fail(DRT_ERR_UNSUPPORTED, "motion vectors need the whole frame: a sharded renderer (world > 1) holds only its stripes");
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : r->stream;
+    int rc = upload_scene(r, scene);             // (nothing is allocated for a scene the guide pass refuses)
+    if (rc != DRT_OK) return rc;
+    if (r->bvh_depth > 64) return fail(DRT_ERR_UNSUPPORTED, "BVH deeper than 64 levels (the reference's traversal stack, BVHTraversal.cuh:17)");
+    if (!r->mv_guides) HIP_TRY(hipMalloc(&r->mv_guides, (size_t)r->width * r->height * sizeof(drt_guide)));
+    rc = enqueue_guides(r, cam, scene, 1, r->mv_guides, s);
+    if (rc != DRT_OK) return rc;
+    const CamConst cc = camera_const(cam, (float)r->width, (float)r->height);
+    ReprojectArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.guides = r->mv_guides;
+    a.width = r->width; a.height = r->height;
+    a.has_prev = 1;
+    std::memcpy(a.cam_pos, cc.cam_pos, 12); std::memcpy(a.fwd_focus, cc.fwd_focus, 12);
+    std::memcpy(a.horizontal, cc.horizontal, 12); std::memcpy(a.vertical, cc.vertical, 12);
+    a.pc = prev_cam ? pinhole_of(prev_cam, (float)r->width, (float)r->height) : r->tp_cam;
+    HIP_TRY(launch_motion_vectors(a, motion_geometry(r), reinterpret_cast<float4 *>(out), s));
+    return query_recorded(r, s);                 // (the next guide pass, on whatever stream, overwrites mv_guides only after this one)
 }
 
 // ------------------------------------------------------------------ refit of the device copy (kernel_refit.hip)
@@ -1383,7 +1472,13 @@ int drt_renderer_refit(drt_renderer *r, const drt_scene *scene, const float *pos
         HIP_TRY(hipEventRecord(r->ev_rf_dep, r->stream));
         HIP_TRY(hipStreamWaitEvent(s, r->ev_rf_dep, 0));
     }
+    const bool take_snapshot = r->mv_track && !r->mv_armed && r->d_hot.count;      // the oldest state since the last temporal call / motion_advance is kept
+    if (take_snapshot && r->mv_snap.count != r->d_hot.count) HIP_TRY(r->mv_snap.alloc(r->d_hot.count));       // (host time: not in *delta_ms)
     HIP_TRY(hipEventRecord(r->ev_rf_start, s));
+    if (take_snapshot) {
+        HIP_TRY(hipMemcpyAsync(r->mv_snap.ptr, r->d_hot.ptr, r->d_hot.count * sizeof(TriHot), hipMemcpyDeviceToDevice, s));
+        r->mv_armed = true;
+    }
     HIP_TRY(hipMemsetAsync(r->rf_out.ptr + 6, 0, sizeof(unsigned int), s));
     RefitArgs a;
     a.pos = positions; a.nrm = normals;
@@ -1401,6 +1496,7 @@ int drt_renderer_refit(drt_renderer *r, const drt_scene *scene, const float *pos
     std::memcpy(&err, out + 6, 4);
     if (err) {
         r->uploaded_scene = nullptr;             // the copy is half written: the next use uploads the host state again
+        r->mv_armed = false;                     // ... and with it goes the snapshot
         return fail(DRT_ERR_INVALID, "non-finite coordinate in refit input");
     }
     std::memcpy(r->view.root_min, out, 12);

@@ -263,6 +263,13 @@ hipError_t launch_temporal_reproject(const ReprojectArgs &args, int num_cus, hip
     return hipGetLastError();
 }
 
+hipError_t launch_temporal_variance(const ReprojectArgs &args, hipStream_t stream) {
+    const uint32_t tiles = ((args.width + 7) / 8) * ((args.height + 7) / 8);
+    if (tiles == 0) return hipSuccess;
+    hipLaunchKernelGGL(temporal_variance_kernel, dim3((tiles + kTpThreads / 64 - 1) / (kTpThreads / 64)), dim3(kTpThreads), 0, stream, args);
+    return hipGetLastError();
+}
+
 hipError_t launch_atrous_var(const AtrousVarPass &ps, hipStream_t stream) {
     if (ps.width == 0 || ps.height == 0) return hipSuccess;
     const dim3 block(kAtrousTile * kAtrousTile);

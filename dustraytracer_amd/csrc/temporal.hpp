@@ -33,6 +33,8 @@ struct ReprojectArgs {
 // Stage (b): reprojection, accumulation and the temporal variance (temporal_reproject_kernel), then the spatial variance of the
 // pixels whose history is shorter than 4 (temporal_variance_kernel) -- two launches on `stream`.
 hipError_t launch_temporal_reproject(const ReprojectArgs &args, int num_cus, hipStream_t stream);
+// The second of those launches alone, for a caller that has written args.cur with a reprojection of its own (kernel_motion.hip)
+hipError_t launch_temporal_variance(const ReprojectArgs &args, hipStream_t stream);
 
 // One variance-guided a-trous pass, step 2^pass.  in = (rgb, variance) per pixel; when `var_src` is given the variance comes
 // from its .z instead (pass 0 reads the history's colour and moments records as they are).  out = (rgb, variance'), or

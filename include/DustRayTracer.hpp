@@ -342,7 +342,20 @@ public:
         drt::check(drt_renderer_set_settings(handle, &s));
         drt::check(drt_renderer_temporal_denoise(handle, &c, scene.handle, &p, delta));
     }
-    void ResetTemporalHistory() { drt::check(drt_renderer_temporal_reset(handle)); }      // after a cut or moved geometry: N = 1 again
+    void ResetTemporalHistory() { drt::check(drt_renderer_temporal_reset(handle)); }      // after a cut or untracked moved geometry: N = 1 again
+    // Follow geometry that Refit moves: TemporalDenoise then reprojects every moved triangle through the state it had at the last
+    // call (drt_renderer_track_motion).  AdvanceMotion makes the current geometry the previous one without a TemporalDenoise.
+    void TrackMotion(bool enable = true) { drt::check(drt_renderer_track_motion(handle, enable ? 1 : 0)); }
+    void AdvanceMotion() { drt::check(drt_renderer_motion_advance(handle)); }
+    // (fx - x, fy - y, z, flag) per pixel into the device buffer out (float4[width*height]); prev_cam NULL = the camera of the
+    // last TemporalDenoise (drt_renderer_motion_vectors; enqueues only)
+    void MotionVectors(Camera *cam, const Scene &scene, float *out, Camera *prev_cam = nullptr, void *stream = nullptr) {
+        drt_settings s = m_RendererSettings.pod();
+        drt_camera c = cam->pod(), pc;
+        if (prev_cam) pc = prev_cam->pod();
+        drt::check(drt_renderer_set_settings(handle, &s));
+        drt::check(drt_renderer_motion_vectors(handle, &c, prev_cam ? &pc : nullptr, scene.handle, out, stream));
+    }
     // the history of the last TemporalDenoise, width*height*4 floats: which 0 = (colour rgb, N), 1 = (m1, m2, variance, weight sum)
     void ReadTemporal(int which, float *dst) {
         drt::check(drt_renderer_read_temporal(handle, which, dst, (size_t)getBufferWidth() * getBufferHeight() * 4));

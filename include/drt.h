@@ -323,8 +323,10 @@ void         *drt_renderer_device_denoised(drt_renderer *r);              /* dev
  * DRT_ERR_INVALID: a NULL argument, no frame size, a pending drt_renderer_render_batch_async batch, iterations outside [0, 10],
  * max_history < 1, alpha_min outside [0, 1], a normal_cos_min or sigma that is not finite, a sigma not > 0, `which` outside 0..1, a
  * too short dst, a read before the first call.  DRT_ERR_UNSUPPORTED: a sharded renderer (world > 1), a tree deeper than 64 levels.
- * Out of scope: motion vectors for geometry that moves between calls (after a refit the caller resets the history or accepts that
- * moved triangles reproject as if they were static); feeding the filtered colour back into the history; drt_group. */
+ * Geometry that a drt_renderer_refit moved between two calls is followed when drt_renderer_track_motion is on (the section
+ * below: P and the normal test of (b) are replaced per pixel, everything else stays).  Out of scope: motion through a host-side
+ * drt_scene_refit and re-upload (such triangles reproject as if they were static: reset the history or accept it); feeding the
+ * filtered colour back into the history; drt_group. */
 typedef struct drt_temporal_params {
     int32_t iterations;      /* a-trous passes, 0..10, default 5 */
     int32_t max_history;     /* history length cap, >= 1, default 32 */
@@ -338,6 +340,47 @@ int           drt_renderer_temporal_denoise(drt_renderer *r, const drt_camera *c
 int           drt_renderer_temporal_reset(drt_renderer *r);               /* drop the history; the next call starts at N = 1 */
 int           drt_renderer_read_temporal(drt_renderer *r, int32_t which, float *dst, size_t dst_floats);
 void         *drt_renderer_device_temporal(drt_renderer *r, int32_t which);     /* device float4[width*height], NULL before the first call */
+
+/* ---- motion vectors: the temporal filter follows refitted geometry (new; opt-in, the reference has neither) ----
+ * drt_renderer_track_motion(r, 1): from now on drt_renderer_refit copies this renderer's device TriHot records (csrc/device_scene.hpp:
+ * v0, e1 = v1 - v0, e2 = v2 - v0, face normal fn; 48 B per triangle) into a renderer-owned SNAPSHOT before its kernels run, on
+ * the refit's stream, but only if the snapshot is not ARMED; the copy arms it.  Several refits between two temporal calls thus
+ * keep the oldest state.  drt_renderer_temporal_denoise disarms it at the end of its stage (b), drt_renderer_motion_advance
+ * disarms it at once ("the geometry as it is now is the PREVIOUS geometry from here on": for callers that feed the motion buffer
+ * to a filter of their own); the buffer is kept for reuse.  It is dropped whenever the renderer's device copy of the scene is
+ * uploaded again (the scene's revision moved, another scene, a failed refit), by drt_renderer_track_motion(r, 0) and by destroy.
+ * A host-side drt_scene_refit moves the revision: the re-upload drops the snapshot and every pixel reprojects as static.
+ * Default 0: every call launches exactly the kernels it launches without this section, and no memory is added.
+ * The rule.  fp32, one rounding per operation, in the order written; dot and normalize as above.  For a pixel with k = g.prim >= 0
+ * and P = cam_pos + d0 * g.t of stage (b), (v0, e1, e2, fn) = the current record k, (v0', e1', e2', fn') = the snapshot's record k:
+ *   STATIC rule -- no armed snapshot, or the nine words v0, e1, e2 are bitwise equal to v0', e1', e2':  P' = P, and a tap is tested
+ *     with dot(n_stored(q), g.normal(p)) >= normal_cos_min.  Stage (b) exactly as written above.
+ *   MOVED rule -- otherwise:  w = P - v0, d11 = dot(e1, e1), d12 = dot(e1, e2), d22 = dot(e2, e2), w1 = dot(w, e1), w2 = dot(w, e2),
+ *     den = d11 * d22 - d12 * d12.  If not den > 0 (zero area, NaN): the static rule.  Else
+ *     b1 = (d22 * w1 - d12 * w2) / den,  b2 = (d11 * w2 - d12 * w1) / den,  P' = (v0' + e1' * b1) + e2' * b2,
+ *     n' = dot(fn, g.normal(p)) < 0 ? -fn' : fn'  (the previous face normal on the side the guide's normal is on), and a tap is
+ *     tested with dot(n_stored(q), n') >= normal_cos_min.
+ *   P' replaces P in pv = P' - pos'; projection, taps, prim equality, sums, blend, variance and what is stored are unchanged (the
+ *   key stores the CURRENT g.normal and g.prim).  The barycentric form carries deformation as well as rigid motion.  No
+ *   transcendental: stage (b) stays reproducible bit for bit.  A snapshot record that is itself degenerate needs no case of its
+ *   own: a NaN in it makes z or the normal test fail (no history), never a stored NaN.
+ * drt_renderer_motion_vectors writes, for the guides of frame 1 for `cam` and the previous camera `prev_cam` (NULL = the camera of
+ * the last drt_renderer_temporal_denoise call), per pixel x + y * width: (fx - (float)x, fy - (float)y, z, flag) with fx, fy, z of
+ * stage (b) for P' and NO bounds test on fx, fy; flag 1 = static rule, 2 = moved rule, 0 = no vector (g.prim < 0 or not z > 0:
+ * then all four words are 0).  It works with tracking off (every flag then 0 or 1) and does not disarm the snapshot.  `out` is a
+ * 16-byte aligned device pointer on the renderer's device, float4[width * height]; hip_stream NULL = the renderer's stream; the
+ * call only enqueues, in order with the renderer's ray queries and guide passes (the same event), and uploads the scene as
+ * rendering does.  The guides it traces live in a renderer-owned buffer allocated by the first call, freed by resize and destroy.
+ * None of the three calls touches the accumulation buffer, the framebuffer, the sample count, the counters, kernel info, kernel
+ * span, the temporal history or the denoised target.  track_motion and motion_advance only manage the snapshot and are legal on a
+ * sharded renderer.
+ * DRT_ERR_INVALID: a NULL argument (prev_cam excepted), prev_cam NULL before the first temporal call (or after a reset / resize), no
+ * frame size, a misaligned / host / other-device `out`, a pending drt_renderer_render_batch_async batch.  DRT_ERR_UNSUPPORTED
+ * (motion_vectors): a sharded renderer (world > 1), a tree deeper than 64 levels. */
+int           drt_renderer_track_motion(drt_renderer *r, int32_t enable);
+int           drt_renderer_motion_advance(drt_renderer *r);
+int           drt_renderer_motion_vectors(drt_renderer *r, const drt_camera *cam, const drt_camera *prev_cam, const drt_scene *scene,
+                                          float *out /* float4[width*height] */, void *hip_stream);
 
 /* ---- path-traced radiance of arbitrary rays (new; the reference shades only its one camera's pixels) ----
  * drt_renderer_camera_rays writes rays[c * width * height + x + y * width] (row 0 = bottom) for every camera c < n_cams and pixel:
