@@ -31,6 +31,10 @@ struct AtrousPass {
     uint32_t width, height, step;
     float k_color, k_normal, k_albedo;
 };
-hipError_t launch_atrous(const AtrousPass &pass, hipStream_t stream);
+// Which of the two filter kernels a pass runs: the rule of launch_atrous (lattice tiles in LDS when width >= 8 * step and height >=
+// 8 * step, cache-read taps otherwise), or one of them whatever the size (DRT_FILTER_KERNEL=lds|taps: both kernels clamp every tap,
+// so both are valid at every size and step; for the tests, which compare the two bit for bit)
+enum class FilterKernel : int32_t { automatic = 0, lds, taps };
+hipError_t launch_atrous(const AtrousPass &pass, FilterKernel which, hipStream_t stream);
 
 }  // namespace drt

@@ -153,6 +153,7 @@ struct drt_renderer {
     unsigned int *rq_heads = nullptr;
     void *rq_stack = nullptr;
     size_t rq_stack_bytes = 0;
+    FilterKernel filter_kernel = FilterKernel::automatic;      // DRT_FILTER_KERNEL=lds / taps: one a-trous kernel for every pass (unset, or any other value: launch_atrous's rule)
     int rq_refill_min = 16;                    // DRT_RQ_REFILL: idle lanes that make a wave claim new rays (64 = only when all are)
     // drt_renderer_denoise: frame 1's guides and the two float4 buffers the passes ping-pong between, allocated by the first call,
     // freed by resize; denoised = the one that holds the last result (-1: none yet)
@@ -439,6 +440,9 @@ drt_renderer *drt_renderer_create(int32_t device) {
         delete r;
         return nullptr;
     }
+    const char *filter = std::getenv("DRT_FILTER_KERNEL");
+    if (filter && std::strcmp(filter, "lds") == 0) r->filter_kernel = FilterKernel::lds;
+    if (filter && std::strcmp(filter, "taps") == 0) r->filter_kernel = FilterKernel::taps;
     auto env_int = [](const char *name, int dflt) { const char *v = std::getenv(name); return (v && *v) ? std::atoi(v) : dflt; };
     r->vote_node = std::max(1, env_int("DRT_VOTE_N", r->vote_node));
     r->vote_shade = std::max(1, env_int("DRT_VOTE_S", r->vote_shade));
@@ -1168,7 +1172,7 @@ int drt_renderer_denoise(drt_renderer *r, const drt_camera *cam, const drt_scene
             ps.k_color = (float)(1 << i) * inv_sc2;
             ps.k_normal = 1.0f / (p->sigma_normal * p->sigma_normal);
             ps.k_albedo = 1.0f / (p->sigma_albedo * p->sigma_albedo);
-            HIP_TRY(launch_atrous(ps, r->stream));
+            HIP_TRY(launch_atrous(ps, r->filter_kernel, r->stream));
         }
         out ^= 1;
     }
@@ -1285,7 +1289,7 @@ int drt_renderer_temporal_denoise(drt_renderer *r, const drt_camera *cam, const 
             ps.sigma_luma = p->sigma_luma;
             ps.k_normal = 1.0f / (p->sigma_normal * p->sigma_normal);
             ps.k_albedo = 1.0f / (p->sigma_albedo * p->sigma_albedo);
-            HIP_TRY(launch_atrous_var(ps, r->stream));
+            HIP_TRY(launch_atrous_var(ps, r->filter_kernel, r->stream));
         }
         out ^= 1;
     }

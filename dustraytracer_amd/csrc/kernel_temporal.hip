@@ -270,10 +270,11 @@ hipError_t launch_temporal_variance(const ReprojectArgs &args, hipStream_t strea
     return hipGetLastError();
 }
 
-hipError_t launch_atrous_var(const AtrousVarPass &ps, hipStream_t stream) {
+hipError_t launch_atrous_var(const AtrousVarPass &ps, FilterKernel which, hipStream_t stream) {
     if (ps.width == 0 || ps.height == 0) return hipSuccess;
     const dim3 block(kAtrousTile * kAtrousTile);
-    if (ps.width >= 8 * ps.step && ps.height >= 8 * ps.step) {          // launch_atrous's switch-over: at least half a lattice tile each way inside the image
+    const bool fits = ps.width >= 8 * ps.step && ps.height >= 8 * ps.step;      // launch_atrous's switch-over: at least half a lattice tile each way inside the image
+    if (which == FilterKernel::automatic ? fits : which == FilterKernel::lds) {
         const uint32_t tiles_x = ((ps.width + ps.step - 1) / ps.step + kAtrousTile - 1) / kAtrousTile;
         const uint32_t tiles_y = ((ps.height + ps.step - 1) / ps.step + kAtrousTile - 1) / kAtrousTile;
         const uint32_t n = tiles_x * ps.step * tiles_y * ps.step;

@@ -5,6 +5,8 @@
 
 #include <cstdint>
 
+#include "denoise.hpp"
+
 namespace drt {
 
 // One half of the ping-pong history: three 16-byte records per pixel x + y * width (row 0 = bottom)
@@ -48,7 +50,7 @@ struct AtrousVarPass {
     int32_t last;
     float sigma_luma, k_normal, k_albedo;
 };
-hipError_t launch_atrous_var(const AtrousVarPass &pass, hipStream_t stream);
+hipError_t launch_atrous_var(const AtrousVarPass &pass, FilterKernel which, hipStream_t stream);
 
 // out = (in.rgb, 1): the result of zero passes
 hipError_t launch_temporal_copy(const float4 *in, float4 *out, uint32_t n, hipStream_t stream);

@@ -48,32 +48,45 @@ def _sq(d):
     return (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
 
 
-def atrous(rgba, albedo, normal, iterations=5, sigma_color=0.5, sigma_normal=0.1, sigma_albedo=0.1):
-    """The filter of drt_renderer_denoise on rgba [H, W, 4] with guides albedo / normal [H, W, 3]: (c_K, the input's alpha)."""
-    rgba = np.ascontiguousarray(rgba, np.float32)
-    alb, nrm = np.ascontiguousarray(albedo, np.float32), np.ascontiguousarray(normal, np.float32)
+def atrous_passes(rgba, albedo, normal, iterations=5, sigma_color=0.5, sigma_normal=0.1, sigma_albedo=0.1, dtype=np.float32):
+    """The colour [H, W, 3] after each pass of the filter of drt_renderer_denoise in turn (a generator: c_1, c_2, ... c_K).  dtype =
+    np.float32: the kernel's own operations and order, one float32 rounding each.  dtype = np.float64: the same formulas of drt.h
+    with every array and constant in float64 and np.exp in float64 -- the filter evaluated (to float32's eyes) exactly."""
+    f = dtype
+    rgba = np.ascontiguousarray(rgba, f)
+    alb, nrm = np.ascontiguousarray(albedo, f), np.ascontiguousarray(normal, f)
     H, W = rgba.shape[:2]
     c = rgba[..., :3].copy()
-    f = np.float32
-    inv_sc2 = f(1) / (f(sigma_color) * f(sigma_color))
-    k_normal = f(1) / (f(sigma_normal) * f(sigma_normal))
-    k_albedo = f(1) / (f(sigma_albedo) * f(sigma_albedo))
+    # (the sigmas are the float parameters of drt_denoise_params in either dtype)
+    inv_sc2 = f(1) / (f(np.float32(sigma_color)) * f(np.float32(sigma_color)))
+    k_normal = f(1) / (f(np.float32(sigma_normal)) * f(np.float32(sigma_normal)))
+    k_albedo = f(1) / (f(np.float32(sigma_albedo)) * f(np.float32(sigma_albedo)))
     ys, xs = np.arange(H), np.arange(W)
     for i in range(iterations):
         s = 1 << i
         k_color = f(s) * inv_sc2
-        wsum = np.zeros((H, W), np.float32)
-        csum = np.zeros((H, W, 3), np.float32)
+        wsum = np.zeros((H, W), f)
+        csum = np.zeros((H, W, 3), f)
         for b in range(5):
             qy = np.clip(ys + (b - 2) * s, 0, H - 1)
             for a in range(5):
                 qx = np.clip(xs + (a - 2) * s, 0, W - 1)
                 cq, nq, aq = c[qy][:, qx], nrm[qy][:, qx], alb[qy][:, qx]
                 e = (_sq(c - cq) * k_color + _sq(nrm - nq) * k_normal) + _sq(alb - aq) * k_albedo
-                w = (B3[a] * B3[b]) * np.exp(-e).astype(np.float32)
+                w = (f(B3[a]) * f(B3[b])) * np.exp(-e).astype(f)
                 wsum = wsum + w
                 csum = csum + cq * w[..., None]
-        c = (csum / wsum[..., None]).astype(np.float32)
+        c = (csum / wsum[..., None]).astype(f)
+        yield c
+
+
+def atrous(rgba, albedo, normal, iterations=5, sigma_color=0.5, sigma_normal=0.1, sigma_albedo=0.1, dtype=np.float32):
+    """The filter of drt_renderer_denoise on rgba [H, W, 4] with guides albedo / normal [H, W, 3]: (c_K, the input's alpha), in
+    `dtype` (atrous_passes)."""
+    rgba = np.ascontiguousarray(rgba, dtype)
+    c = rgba[..., :3]
+    for c in atrous_passes(rgba, albedo, normal, iterations, sigma_color, sigma_normal, sigma_albedo, dtype):
+        pass
     return np.concatenate([c, rgba[..., 3:4]], axis=-1)
 
 

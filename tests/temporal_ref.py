@@ -75,8 +75,8 @@ def project(ph, P, W, H):
     return fx, fy, ok
 
 
-def luminance(c):
-    return ((F(0.2126) * c[..., 0] + F(0.7152) * c[..., 1]) + F(0.0722) * c[..., 2]).astype(F)
+def luminance(c, T=F):
+    return ((T(0.2126) * c[..., 0] + T(0.7152) * c[..., 1]) + T(0.0722) * c[..., 2]).astype(T)
 
 
 def reproject(prev, rgba, guides, ph, max_history=32, alpha_min=0.0, normal_cos_min=0.9, **_):
@@ -144,39 +144,51 @@ def reproject(prev, rgba, guides, ph, max_history=32, alpha_min=0.0, normal_cos_
     return History(color, N, normal.copy(), prim.copy(), m1, m2, variance, S, ph)
 
 
-def atrous_var(color, variance, albedo, normal, iterations=5, sigma_luma=4.0, sigma_normal=0.1, sigma_albedo=0.1, **_):
-    """Stage (c): (c_K, 1) [H, W, 4] from the integrated colour [H, W, 3] and its variance [H, W]."""
-    c, var = np.ascontiguousarray(color, F).copy(), np.ascontiguousarray(variance, F).copy()
-    alb, nrm = np.ascontiguousarray(albedo, F), np.ascontiguousarray(normal, F)
+def atrous_var_passes(color, variance, albedo, normal, iterations=5, sigma_luma=4.0, sigma_normal=0.1, sigma_albedo=0.1, dtype=F, **_):
+    """Stage (c), pass by pass (a generator): the colour [H, W, 3] after passes 1, 2, ... K.  dtype = float32: the kernel's own
+    operations and order, one float32 rounding each.  dtype = float64: the same formulas of drt.h with every array and constant in
+    float64 and np.exp in float64 -- the filter evaluated (to float32's eyes) exactly."""
+    T = dtype
+    c, var = np.ascontiguousarray(color, T).copy(), np.ascontiguousarray(variance, T).copy()
+    alb, nrm = np.ascontiguousarray(albedo, T), np.ascontiguousarray(normal, T)
     H, W = var.shape
-    k_normal = F(1) / (F(sigma_normal) * F(sigma_normal))
-    k_albedo = F(1) / (F(sigma_albedo) * F(sigma_albedo))
+    # (the sigmas are the float parameters of drt_temporal_params in either dtype)
+    k_normal = T(1) / (T(F(sigma_normal)) * T(F(sigma_normal)))
+    k_albedo = T(1) / (T(F(sigma_albedo)) * T(F(sigma_albedo)))
     ys, xs = np.arange(H), np.arange(W)
-    g3 = F([0.25, 0.5, 0.25])
+    g3 = np.array([0.25, 0.5, 0.25], T)
     for i in range(iterations):
         s = 1 << i
-        gv = np.zeros((H, W), F)
+        gv = np.zeros((H, W), T)
         for dy in range(-1, 2):
             qy = np.clip(ys + dy, 0, H - 1)
             for dx in range(-1, 2):
                 qx = np.clip(xs + dx, 0, W - 1)
-                gv = (gv + (g3[dy + 1] * g3[dx + 1]) * var[qy][:, qx]).astype(F)
-        r = (F(1) / ((F(sigma_luma) * np.sqrt(gv)).astype(F) + F(1e-4)).astype(F)).astype(F)
-        lum = luminance(c)
-        wsum, vsum, csum = np.zeros((H, W), F), np.zeros((H, W), F), np.zeros((H, W, 3), F)
+                gv = (gv + (g3[dy + 1] * g3[dx + 1]) * var[qy][:, qx]).astype(T)
+        r = (T(1) / ((T(F(sigma_luma)) * np.sqrt(gv)).astype(T) + T(1e-4)).astype(T)).astype(T)
+        lum = luminance(c, T)
+        wsum, vsum, csum = np.zeros((H, W), T), np.zeros((H, W), T), np.zeros((H, W, 3), T)
         for b in range(5):
             qy = np.clip(ys + (b - 2) * s, 0, H - 1)
             for a in range(5):
                 qx = np.clip(xs + (a - 2) * s, 0, W - 1)
                 cq, nq, aq = c[qy][:, qx], nrm[qy][:, qx], alb[qy][:, qx]
-                e = ((np.abs(lum - lum[qy][:, qx]) * r).astype(F) + _sq(nrm - nq) * k_normal).astype(F) + (_sq(alb - aq) * k_albedo).astype(F)
-                w = ((B3[a] * B3[b]) * np.exp(-e).astype(F)).astype(F)
-                wsum = (wsum + w).astype(F)
-                csum = (csum + cq * w[..., None]).astype(F)
-                vsum = (vsum + (w * w).astype(F) * var[qy][:, qx]).astype(F)
-        c = (csum / wsum[..., None]).astype(F)
-        var = (vsum / (wsum * wsum).astype(F)).astype(F)
-    return np.concatenate([c, np.ones((H, W, 1), F)], axis=-1)
+                e = ((np.abs(lum - lum[qy][:, qx]) * r).astype(T) + _sq(nrm - nq) * k_normal).astype(T) + (_sq(alb - aq) * k_albedo).astype(T)
+                w = ((T(B3[a]) * T(B3[b])) * np.exp(-e).astype(T)).astype(T)
+                wsum = (wsum + w).astype(T)
+                csum = (csum + cq * w[..., None]).astype(T)
+                vsum = (vsum + (w * w).astype(T) * var[qy][:, qx]).astype(T)
+        c = (csum / wsum[..., None]).astype(T)
+        var = (vsum / (wsum * wsum).astype(T)).astype(T)
+        yield c
+
+
+def atrous_var(color, variance, albedo, normal, iterations=5, sigma_luma=4.0, sigma_normal=0.1, sigma_albedo=0.1, dtype=F, **_):
+    """Stage (c): (c_K, 1) [H, W, 4] from the integrated colour [H, W, 3] and its variance [H, W], in `dtype` (atrous_var_passes)."""
+    c = np.ascontiguousarray(color, dtype)
+    for c in atrous_var_passes(color, variance, albedo, normal, iterations, sigma_luma, sigma_normal, sigma_albedo, dtype):
+        pass
+    return np.concatenate([c, np.ones(c.shape[:2] + (1,), dtype)], axis=-1)
 
 
 def temporal_denoise(prev, rgba, guides, ph, **params):

@@ -87,3 +87,58 @@ def test_denoised_noise_is_lower(name):
     ratio = dn.mse(out, clean) / dn.mse(noisy, clean)
     print("%s: MSE denoised / noisy = %.3f" % (name, ratio))
     assert ratio <= GATES[name]
+
+
+# ---- the float32 restatement against the same formulas in float64: 96x64, 1 spp of the oracle, 1 .. 10 passes ----
+FP64_BOUND = 1e-3         # a quarter of an 8-bit step of display-referred values (the bound test_gpu_temporal.py names)
+
+
+@pytest.mark.parametrize("sig", [dict(sigma_color=0.5, sigma_normal=0.1, sigma_albedo=0.1), dict(sigma_color=0.8, sigma_normal=0.35, sigma_albedo=0.05)])
+@pytest.mark.parametrize("name", ["cornell_box", "uv_texture_test", "suzanne_plane"])
+def test_float32_restatement_stays_near_the_float64_filter(name, sig):
+    """atrous(dtype=float32), which the GPU is pinned to, against atrous(dtype=float64) on the same inputs after each of 10
+    passes (steps 1 .. 512, each chain fed by its own previous pass).  The passes past the image size are part of it: at 96x64
+    every tap of steps 128 .. 512 is clamped to the border."""
+    _, pos, fwd, depth = SCENES[name]
+    Wt, Ht = 96, 64
+    osc = oracle.Scene.load_glb(scene_path(name)).build_bvh(20, 8)
+    cam = oracle.default_camera(position=pos, forward=fwd)
+    noisy, _, _ = oracle.render(osc, cam, oracle.default_settings(ray_bounce_limit=depth), Wt, Ht, 1, 1)
+    g = dn.guides(osc, cam, Wt, Ht, 1)
+    p32 = dn.atrous_passes(noisy, g.albedo, g.normal, 10, **sig)
+    p64 = dn.atrous_passes(noisy, g.albedo, g.normal, 10, dtype=np.float64, **sig)
+    errs = []
+    for K, (c32, c64) in enumerate(zip(p32, p64), 1):
+        assert c32.dtype == np.float32 and c64.dtype == np.float64
+        errs.append(float(np.abs(c32 - c64).max()))
+    assert len(errs) == 10
+    print("%s sigma_color %g: max |fp32 - fp64| after passes 1..10 = %s" % (name, sig["sigma_color"], " ".join("%.2e" % e for e in errs)))
+    for K, e in enumerate(errs, 1):
+        assert e <= FP64_BOUND, (name, K, e)
+
+
+def test_float64_argument_leaves_the_float32_restatement_alone():
+    """dtype is a pure addition: the float32 result is what atrous() gave before it had the argument (the loop written out here),
+    and float64 of 0 passes is the input."""
+    rgba, albedo, normal = _random_frame(21, 19, 5)
+    out = dn.atrous(rgba, albedo, normal, iterations=2)
+    f = np.float32
+    c = rgba[..., :3].copy()
+    ys, xs = np.arange(21), np.arange(19)
+    for i in range(2):
+        s = 1 << i
+        wsum, csum = np.zeros((21, 19), f), np.zeros((21, 19, 3), f)
+        for b in range(5):
+            qy = np.clip(ys + (b - 2) * s, 0, 20)
+            for a in range(5):
+                qx = np.clip(xs + (a - 2) * s, 0, 18)
+                cq = c[qy][:, qx]
+                e = (dn._sq(c - cq) * (f(s) * (f(1) / (f(0.5) * f(0.5)))) + dn._sq(normal - normal[qy][:, qx]) * (f(1) / (f(0.1) * f(0.1)))) \
+                    + dn._sq(albedo - albedo[qy][:, qx]) * (f(1) / (f(0.1) * f(0.1)))
+                w = (dn.B3[a] * dn.B3[b]) * np.exp(-e).astype(f)
+                wsum = wsum + w
+                csum = csum + cq * w[..., None]
+        c = (csum / wsum[..., None]).astype(f)
+    assert out.dtype == np.float32 and (out[..., :3].view(np.uint32) == c.view(np.uint32)).all()
+    out64 = dn.atrous(rgba, albedo, normal, iterations=0, dtype=np.float64)
+    assert out64.dtype == np.float64 and (out64 == rgba).all()

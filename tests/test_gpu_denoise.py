@@ -148,7 +148,8 @@ def test_filter_matches_the_restatement(name, W, H):
     img = r.GetRenderTargetImage()
     g = r.renderGuides(cam, sc, 1)
     worst = 0.0
-    for K in (0, 1, 5, 7):                        # (steps up to 64: both filter kernels, lattice tiles in LDS and cache-read taps)
+    for K in (0, 1, 5, 7):                        # (steps up to 64: at these sizes lattice tiles in LDS up to step 16 at most, cache-read taps above;
+                                                      #  the LDS kernel at larger steps and both at steps 128 .. 512: test_gpu_filter_kernels.py)
         for sig in SIGMAS:
             out = r.Denoise(cam, sc, K, **sig)
             if K == 0:

@@ -155,3 +155,41 @@ def test_zero_passes_give_the_integrated_colour():
     assert (out[..., :3].view(np.uint32) == h.color.view(np.uint32)).all() and (out[..., 3] == 1).all()
     _, filtered = tp.temporal_denoise(None, img, g, ph, iterations=3)
     assert np.isfinite(filtered).all() and (filtered[..., 3] == 1).all() and np.abs(filtered[..., :3] - h.color).max() > 1e-3
+
+
+# ---- the float32 restatement of stage (c) against the same formulas in float64: 96x64, oracle frames, 1 .. 10 passes ----
+FP64_BOUND = 1e-3         # a quarter of an 8-bit step of display-referred values (the bound test_gpu_temporal.py names)
+
+
+@pytest.mark.parametrize("sig", [dict(sigma_luma=4.0, sigma_normal=0.1, sigma_albedo=0.1), dict(sigma_luma=1.5, sigma_normal=0.35, sigma_albedo=0.05)])
+@pytest.mark.parametrize("name", ["cornell_box", "uv_texture_test", "two_quads"])
+def test_float32_filter_stays_near_the_float64_filter(name, sig):
+    """atrous_var(dtype=float32), which the GPU is pinned to, against atrous_var(dtype=float64) on the history after one pose (the
+    7x7 spatial variance everywhere) and after three (mixed history lengths and variances), after each of 10 passes.  The filter
+    divides by sigma_luma * sqrt(gv) + 1e-4 and by wsum^2: where the variance is 0 the luminance term is 1e4 |dl|, and this is
+    the check that float32 rounding under those divisions stays below the bound through step 512."""
+    W, H = 96, 64
+    if name == "two_quads":
+        _, osc = rq.programmatic_scene(drt, *tp.two_quads(), 2, 8)
+        seq, depth = [((0.1 * k, 0.1, 8.0), (0.0, 0.0, -1.0)) for k in range(3)], 3
+    else:
+        osc = _scene(name)
+        _, pos, fwd, depth = SCENES[name]
+        seq = [((pos[0], pos[1] + 0.02 * k, pos[2] + 0.03 * k), fwd) for k in range(3)]
+    hist = None
+    for k, (pos, fwd) in enumerate(seq):
+        img, g, ph = _frame(osc, pos, fwd, W, H, depth)
+        hist = tp.reproject(hist, img, g, ph)
+        if k == 1:
+            continue
+        p32 = tp.atrous_var_passes(hist.color, hist.variance, g.albedo, g.normal, 10, **sig)
+        p64 = tp.atrous_var_passes(hist.color, hist.variance, g.albedo, g.normal, 10, dtype=np.float64, **sig)
+        errs = []
+        for c32, c64 in zip(p32, p64):
+            assert c32.dtype == np.float32 and c64.dtype == np.float64 and np.isfinite(c64).all()
+            errs.append(float(np.abs(c32 - c64).max()))
+        assert len(errs) == 10
+        print("%s pose %d sigma_luma %g: max |fp32 - fp64| after passes 1..10 = %s" % (name, k, sig["sigma_luma"], " ".join("%.2e" % e for e in errs)))
+        for K, e in enumerate(errs, 1):
+            assert e <= FP64_BOUND, (name, k, K, e)
+    assert (hist.length > 1).any() and (hist.length >= 3).any()
