@@ -178,6 +178,21 @@ class TemporalParams(C.Structure):
             setattr(self, k, v)
 
 
+class UpscaleParams(C.Structure):
+    """include/drt.h drt_upscale_params: the source (0 framebuffer, 1 denoised target), albedo demodulation, the three
+    edge-stopping sigmas and the albedo floor (defaults 0, 0, 0.1, 0.05, 0.1, 0.01)."""
+    _fields_ = [("source", C.c_int32), ("demodulate", C.c_int32), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float),
+                ("sigma_albedo", C.c_float), ("albedo_floor", C.c_float)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        _lib.drt_default_upscale_params(C.byref(self))
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError("UpscaleParams has no field %r" % k)
+            setattr(self, k, v)
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("samples", "rays", "node_visits", "inner_visits", "tri_tests",
                                            "hits_textured", "hits_flat", "shadow_rays", "inner_visits_shadow",
@@ -300,6 +315,11 @@ _sig("drt_renderer_device_temporal", _P, _P, C.c_int32)
 _sig("drt_renderer_track_motion", C.c_int, _P, C.c_int32)
 _sig("drt_renderer_motion_advance", C.c_int, _P)
 _sig("drt_renderer_motion_vectors", C.c_int, _P, C.POINTER(_CameraPOD), C.POINTER(_CameraPOD), _P, _P, _P)
+_sig("drt_default_upscale_params", None, C.POINTER(UpscaleParams))
+_sig("drt_renderer_upscale", C.c_int, _P, C.POINTER(_CameraPOD), _P, C.c_uint32, C.c_uint32, C.POINTER(UpscaleParams), C.POINTER(C.c_float))
+_sig("drt_renderer_read_upscaled_rgba32f", C.c_int, _P, _P, C.c_size_t)
+_sig("drt_renderer_device_upscaled", _P, _P)
+_sig("drt_debug_upscale", C.c_int, C.c_int32, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(UpscaleParams), _P)
 _sig("drt_scene_get_triangle_order", C.c_int, _P, _P, C.c_int32)
 _sig("drt_scene_refit", C.c_int, _P, _P, _P)
 _sig("drt_renderer_refit", C.c_int, _P, _P, _P, _P, C.POINTER(C.c_float), _P)
@@ -628,6 +648,8 @@ class Renderer:
         self.m_RendererSettings = RendererSettings()
         self.m_LastDenoiseMs = 0.0               # device time of the last Denoise (guides + filter)
         self.m_LastTemporalMs = 0.0              # device time of the last TemporalDenoise (guides + reprojection + filter)
+        self.m_LastUpscaleMs = 0.0               # device time of the last Upscale (both guide passes + the kernel)
+        self._upscaled_size = (0, 0)             # (width, height) of the last Upscale
 
     def _ray_query(self, scene, origins, directions, tmin, tmax, occluded):
         import torch                             # (only here: importing the package does not import torch)
@@ -858,6 +880,30 @@ class Renderer:
         """Device address of the history's colour (which 0) or moments (1) records, None before the first TemporalDenoise."""
         return _lib.drt_renderer_device_temporal(self._h, int(which))
 
+    def Upscale(self, cam, scene, width, height, **params):
+        """Joint-bilateral upsampling of the frame to width x height, steered by the first-hit guides of both sizes
+        (drt_renderer_upscale; `params` = UpscaleParams fields: source 0 = the framebuffer, 1 = the last Denoise / TemporalDenoise
+        result): float32 [height, width, 4], row 0 = bottom.  The renderer's own buffers are left as they are."""
+        self._push_settings()
+        p = UpscaleParams(**params)
+        ms = C.c_float(0)
+        pod = cam._pod()
+        _check(_lib.drt_renderer_upscale(self._h, C.byref(pod), scene._h, int(width), int(height), C.byref(p), C.byref(ms)))
+        self.m_LastUpscaleMs = ms.value
+        self._upscaled_size = (int(width), int(height))
+        return self.GetUpscaledImage()
+
+    def GetUpscaledImage(self):
+        """The last Upscale result as numpy float32 [Ho, Wo, 4] (drt_renderer_read_upscaled_rgba32f)."""
+        w, h = self._upscaled_size
+        out = np.zeros((h, w, 4), np.float32)
+        _check(_lib.drt_renderer_read_upscaled_rgba32f(self._h, out.ctypes.data, out.size))
+        return out
+
+    def DeviceUpscaledTarget(self):
+        """Device address of the last Upscale result (float4 [Ho * Wo]), None before the first Upscale."""
+        return _lib.drt_renderer_device_upscaled(self._h)
+
     def trackMotion(self, enable=True):
         """Follow geometry that Renderer.refit moves (drt_renderer_track_motion): the first refit after a TemporalDenoise keeps
         the triangles as they were, and the next TemporalDenoise reprojects every moved triangle's pixels through that state.
@@ -1023,6 +1069,22 @@ def debug_kat(which, inputs, cam=None, width=0, height=0, device=0):
     pod = cam._pod() if cam is not None else None
     _check(_lib.drt_debug_kat(device, which, a.ctypes.data, a.nbytes, out.ctypes.data, out.nbytes, len(a),
                               C.byref(pod) if pod is not None else None, width, height))
+    return out
+
+
+def debug_upscale(colour, guides_lo, guides_hi, device=0, **params):
+    """The upscale kernel alone on host arrays (drt.h drt_debug_upscale): colour float32 [H, W, 4], guides_lo [H, W, 8] and
+    guides_hi [Ho, Wo, 8] as drt_guide lays them out (albedo rgb, t, normal xyz, prim as int32 bits); `params` = UpscaleParams
+    fields.  Returns float32 [Ho, Wo, 4]."""
+    c = np.ascontiguousarray(colour, np.float32)
+    lo, hi = np.ascontiguousarray(guides_lo, np.float32), np.ascontiguousarray(guides_hi, np.float32)
+    H, W = c.shape[:2]
+    Ho, Wo = hi.shape[:2]
+    if c.shape != (H, W, 4) or lo.shape != (H, W, 8) or hi.shape != (Ho, Wo, 8):
+        raise ValueError("colour [H, W, 4], guides_lo [H, W, 8], guides_hi [Ho, Wo, 8]")
+    p = UpscaleParams(**params)
+    out = np.zeros((Ho, Wo, 4), np.float32)
+    _check(_lib.drt_debug_upscale(device, c.ctypes.data, lo.ctypes.data, hi.ctypes.data, W, H, Wo, Ho, C.byref(p), out.ctypes.data))
     return out
 
 

@@ -23,6 +23,7 @@
 #include "temporal.hpp"
 #include "refit.hpp"
 #include "motion.hpp"
+#include "upscale.hpp"
 #include "radiance.hpp"
 #include "scene_host.hpp"
 #include "bvh_build_device.hpp"
@@ -187,6 +188,12 @@ struct drt_renderer {
     bool mv_track = false, mv_armed = false;
     DeviceArray<TriHot> mv_snap;
     void *mv_guides = nullptr;
+    // drt_renderer_upscale: us_guides = frame 1's guides at the frame size followed by those at the output size, us_out = the
+    // upscaled image, float4[us_width * us_height]; allocated by the first call, again when the output size changes, freed by
+    // resize and destroy (us_width == 0: no result yet)
+    void *us_guides = nullptr;
+    float4 *us_out = nullptr;
+    uint32_t us_width = 0, us_height = 0;
 
     float *cur_accum() const { return ext_accum ? ext_accum : accum; }
     float *cur_rgba() const { return ext_rgba ? ext_rgba : rgba; }
@@ -203,6 +210,13 @@ struct drt_renderer {
     void free_motion_guides() {
         if (mv_guides) (void)hipFree(mv_guides);
         mv_guides = nullptr;
+    }
+    void free_upscale() {
+        if (us_guides) (void)hipFree(us_guides);
+        if (us_out) (void)hipFree(us_out);
+        us_guides = nullptr;
+        us_out = nullptr;
+        us_width = us_height = 0;
     }
     void free_denoise() {
         if (dn_guides) (void)hipFree(dn_guides);
@@ -410,6 +424,7 @@ static int realloc_buffers(drt_renderer *r) {
     r->free_denoise();
     r->free_temporal();
     r->free_motion_guides();
+    r->free_upscale();
     r->local_rows = drt_shard_rows(r->height, r->stripe_rows, r->rank, r->world);
     size_t px = std::max<size_t>((size_t)r->width * r->local_rows, 1);
     HIP_TRY(hipMalloc((void **)&r->accum, px * 3 * sizeof(float)));
@@ -512,6 +527,7 @@ void drt_renderer_destroy(drt_renderer *r) {
     r->free_denoise();
     r->free_temporal();
     r->free_motion_guides();
+    r->free_upscale();
     if (r->ev_dn_start) (void)hipEventDestroy(r->ev_dn_start);
     if (r->ev_dn_stop) (void)hipEventDestroy(r->ev_dn_stop);
     for (hipEvent_t ev : { r->ev_rf_start, r->ev_rf_stop, r->ev_rf_dep })
@@ -742,11 +758,13 @@ static CamConst camera_const(const drt_camera *cam, float width, float height) {
 
 // Per-frame constants of Camera::GetRay (Camera.cu:84-103) and RayGen (RayGen.cuh:68-72), computed on the
 // host with the same fp32 operations in the same order (host libm for tan/sin/cos).
-static void fill_frame_params(const drt_renderer *r, const drt_camera *cam, FrameParams &fp) {
+// width, height: the frame the constants are for; 0 = the renderer's (a guide pass at another size: drt_renderer_upscale).
+static void fill_frame_params(const drt_renderer *r, const drt_camera *cam, FrameParams &fp, uint32_t width = 0, uint32_t height = 0) {
     const drt_settings &s = r->settings;
+    if (width == 0 || height == 0) { width = r->width; height = r->height; }
     auto put = [](float *dst, V3 v) { dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; };
     if (cam) {                                 // (radiance queries have no camera: their rays carry what it would give)
-        const CamConst c = camera_const(cam, (float)r->width, (float)r->height);
+        const CamConst c = camera_const(cam, (float)width, (float)height);
         std::memcpy(fp.cam_pos, c.cam_pos, 12);
         std::memcpy(fp.fwd_focus, c.fwd_focus, 12); std::memcpy(fp.horizontal, c.horizontal, 12); std::memcpy(fp.vertical, c.vertical, 12);
         std::memcpy(fp.disk_u, c.disk_u, 12); std::memcpy(fp.disk_v, c.disk_v, 12);
@@ -766,7 +784,7 @@ static void fill_frame_params(const drt_renderer *r, const drt_camera *cam, Fram
     fp.ext_emissive = r->material_model.emissive != 0; fp.ext_specular = r->material_model.specular != 0;
     fp.ext_emissive_scale = r->material_model.emissive_scale;
     fp.ext_transmission = r->material_model.transmission != 0;
-    fp.width = r->width; fp.height = r->height;
+    fp.width = width; fp.height = height;
     fp.stripe_rows = r->stripe_rows; fp.rank = r->rank; fp.world = r->world; fp.local_rows = r->local_rows;
     fp.accum = r->cur_accum(); fp.rgba = r->cur_rgba();
     fp.counters = r->counting ? r->counters : nullptr;
@@ -1005,7 +1023,9 @@ static bool on_renderer_device(const drt_renderer *r, const void *p) {
 }
 
 // The guide pass on stream `s`, ordered with the ray queries (it shares their HBM stack); the caller has checked the arguments.
-static int enqueue_guides(drt_renderer *r, const drt_camera *cam, const drt_scene *scene, uint32_t frame_index, void *guides, hipStream_t s) {
+// width, height: the size of the image the guides are for, 0 = the renderer's frame (`guides` holds that many records).
+static int enqueue_guides(drt_renderer *r, const drt_camera *cam, const drt_scene *scene, uint32_t frame_index, void *guides, hipStream_t s,
+                          uint32_t width = 0, uint32_t height = 0) {
     if (r->world > 1) return fail(DRT_ERR_UNSUPPORTED, "guides and the denoiser need the whole frame: a sharded renderer (world > 1) holds only its stripes");
     int rc = upload_scene(r, scene);
     if (rc != DRT_OK) return rc;
@@ -1020,7 +1040,7 @@ static int enqueue_guides(drt_renderer *r, const drt_camera *cam, const drt_scen
     }
     FrameParams fp;
     std::memset(&fp, 0, sizeof fp);
-    fill_frame_params(r, cam, fp);
+    fill_frame_params(r, cam, fp, width, height);
     GuideArgs a;
     a.out = guides;
     a.frame = frame_index;
@@ -1369,6 +1389,114 @@ int drt_renderer_motion_vectors(drt_renderer *r, const drt_camera *cam, const dr
     a.pc = prev_cam ? pinhole_of(prev_cam, (float)r->width, (float)r->height) : r->tp_cam;
     HIP_TRY(launch_motion_vectors(a, motion_geometry(r), reinterpret_cast<float4 *>(out), s));
     return query_recorded(r, s);                 // (the next guide pass, on whatever stream, overwrites mv_guides only after this one)
+}
+
+// ------------------------------------------------------------------ guide-driven upscaling (kernel_upscale.hip)
+void drt_default_upscale_params(drt_upscale_params *out) {
+    if (!out) return;
+    out->source = 0;
+    out->demodulate = 0;                         // (include/drt.h: demodulation lost against the oracle on both test scenes)
+    out->sigma_normal = 0.1f; out->sigma_depth = 0.05f; out->sigma_albedo = 0.1f;
+    out->albedo_floor = 0.01f;
+}
+
+// What both entry points check of the parameters and the two sizes (nullptr = fine)
+static const char *upscale_arguments(const drt_upscale_params *p, uint32_t W, uint32_t H, uint32_t Wo, uint32_t Ho) {
+    if (p->source < 0 || p->source > 1) return "source must be 0 (the framebuffer) or 1 (the denoised target)";
+    if (p->demodulate < 0 || p->demodulate > 1) return "demodulate must be 0 or 1";
+    for (float v : { p->sigma_normal, p->sigma_depth, p->sigma_albedo, p->albedo_floor })
+        if (!std::isfinite(v) || !(v > 0.f)) return "every sigma and the albedo floor must be finite and > 0";
+    if (W == 0 || H == 0) return "no frame size";
+    if (Wo < W || Ho < H) return "the output must be at least as large as the frame in both axes";
+    if ((uint64_t)Wo * Ho > (1ull << 31)) return "output too large (at most 2^31 pixels)";
+    return nullptr;
+}
+
+static UpscaleArgs upscale_args(const drt_upscale_params *p, uint32_t W, uint32_t H, uint32_t Wo, uint32_t Ho) {
+    UpscaleArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.width = W; a.height = H; a.out_width = Wo; a.out_height = Ho;
+    a.demodulate = p->demodulate;
+    a.k_normal = 1.0f / (p->sigma_normal * p->sigma_normal);
+    a.k_albedo = 1.0f / (p->sigma_albedo * p->sigma_albedo);
+    a.sigma_depth = p->sigma_depth;
+    a.albedo_floor = p->albedo_floor;
+    return a;
+}
+
+int drt_renderer_upscale(drt_renderer *r, const drt_camera *cam, const drt_scene *scene, uint32_t out_width, uint32_t out_height,
+                         const drt_upscale_params *p, float *delta_ms) {
+    if (delta_ms) *delta_ms = 0.f;
+    if (!r || !cam || !scene || !p) return fail(DRT_ERR_INVALID, "null argument");
+    if (r->width == 0 || r->height == 0) return fail(DRT_ERR_INVALID, "ResizeBuffer has not been called");
+    if (const char *why = upscale_arguments(p, r->width, r->height, out_width, out_height)) return fail(DRT_ERR_INVALID, why);
+    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
+    if (r->world > 1) return fail(DRT_ERR_UNSUPPORTED, "upscaling needs the whole frame: a sharded renderer (world > 1) holds only its stripes");
+    if (p->source == 1 && r->denoised < 0) return fail(DRT_ERR_INVALID, "source 1 is the denoised target: drt_renderer_denoise or drt_renderer_temporal_denoise first");
+    HIP_TRY(hipSetDevice(r->device));
+    (void)hipGetLastError();
+    const size_t px = (size_t)r->width * r->height, out_px = (size_t)out_width * out_height;
+    if (r->us_width != out_width || r->us_height != out_height) {
+        r->free_upscale();
+        HIP_TRY(hipMalloc(&r->us_guides, (px + out_px) * sizeof(drt_guide)));
+        HIP_TRY(hipMalloc((void **)&r->us_out, out_px * sizeof(float4)));
+    }
+    if (!r->ev_dn_start) HIP_TRY(hipEventCreate(&r->ev_dn_start));
+    if (!r->ev_dn_stop) HIP_TRY(hipEventCreate(&r->ev_dn_stop));
+    r->us_width = r->us_height = 0;              // (a failure below leaves no result)
+    drt_guide *lo = static_cast<drt_guide *>(r->us_guides), *hi = lo + px;
+    HIP_TRY(hipEventRecord(r->ev_dn_start, r->stream));
+    int rc = enqueue_guides(r, cam, scene, 1, lo, r->stream);
+    if (rc == DRT_OK) rc = enqueue_guides(r, cam, scene, 1, hi, r->stream, out_width, out_height);
+    if (rc != DRT_OK) { r->free_upscale(); return rc; }
+    UpscaleArgs a = upscale_args(p, r->width, r->height, out_width, out_height);
+    a.color = p->source == 1 ? r->dn_buf[r->denoised] : reinterpret_cast<const float4 *>(r->cur_rgba());
+    a.guides_lo = lo; a.guides_hi = hi;
+    a.out = r->us_out;
+    HIP_TRY(launch_upscale(a, r->stream));
+    HIP_TRY(hipEventRecord(r->ev_dn_stop, r->stream));
+    HIP_TRY(hipEventSynchronize(r->ev_dn_stop));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, r->ev_dn_start, r->ev_dn_stop));
+    if (delta_ms) *delta_ms = ms;
+    r->us_width = out_width; r->us_height = out_height;
+    return DRT_OK;
+}
+
+void *drt_renderer_device_upscaled(drt_renderer *r) { return r && r->us_width ? (void *)r->us_out : nullptr; }
+
+int drt_renderer_read_upscaled_rgba32f(drt_renderer *r, float *dst, size_t dst_floats) {
+    if (!r || !dst) return fail(DRT_ERR_INVALID, "null argument");
+    if (r->us_width == 0) return fail(DRT_ERR_INVALID, "no upscaled image yet: drt_renderer_upscale first");
+    const size_t need = (size_t)r->us_width * r->us_height * 4;
+    if (dst_floats < need) return fail(DRT_ERR_INVALID, "destination too small");
+    HIP_TRY(hipSetDevice(r->device));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    HIP_TRY(hipMemcpy(dst, r->us_out, need * sizeof(float), hipMemcpyDeviceToHost));
+    return DRT_OK;
+}
+
+int drt_debug_upscale(int32_t device, const float *colour, const drt_guide *guides_lo, const drt_guide *guides_hi, uint32_t width, uint32_t height,
+                      uint32_t out_width, uint32_t out_height, const drt_upscale_params *p, float *out) {
+    if (!colour || !guides_lo || !guides_hi || !p || !out) return fail(DRT_ERR_INVALID, "null argument");
+    if (const char *why = upscale_arguments(p, width, height, out_width, out_height)) return fail(DRT_ERR_INVALID, why);
+    HIP_TRY(hipSetDevice(device));
+    const size_t px = (size_t)width * height, out_px = (size_t)out_width * out_height;
+    const size_t off_lo = px * sizeof(float4), off_hi = off_lo + px * sizeof(drt_guide), off_out = off_hi + out_px * sizeof(drt_guide);
+    char *d = nullptr;                           // colour, guides_lo, guides_hi, out: every part a multiple of 16 bytes
+    HIP_TRY(hipMalloc((void **)&d, off_out + out_px * sizeof(float4)));
+    hipError_t e = hipMemcpy(d, colour, off_lo, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d + off_lo, guides_lo, px * sizeof(drt_guide), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d + off_hi, guides_hi, out_px * sizeof(drt_guide), hipMemcpyHostToDevice);
+    UpscaleArgs a = upscale_args(p, width, height, out_width, out_height);
+    a.color = reinterpret_cast<const float4 *>(d);
+    a.guides_lo = d + off_lo; a.guides_hi = d + off_hi;
+    a.out = reinterpret_cast<float4 *>(d + off_out);
+    if (e == hipSuccess) e = launch_upscale(a, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(out, d + off_out, out_px * sizeof(float4), hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (e != hipSuccess) return fail(DRT_ERR_DEVICE, hipGetErrorString(e));
+    return DRT_OK;
 }
 
 // ------------------------------------------------------------------ refit of the device copy (kernel_refit.hip)

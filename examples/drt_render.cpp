@@ -5,6 +5,8 @@
 //   ./drt_render models/cornell_box.glb out.png 1920 1080 4 8  3.6 1.25 0  -1 0 0  --denoise     (writes the a-trous denoised frame)
 //   ./drt_render models/cornell_box.glb out.png 1920 1080 1 8  3.6 1.25 0  -1 0 0  --temporal 12  (12 poses of a small orbit ending at the
 //                                                  given pose, 1 spp each, temporally accumulated and filtered: writes the last pose)
+//   ./drt_render models/cornell_box.glb out.png 960 540 1 8  3.6 1.25 0  -1 0 0  --upscale 1920 1080 --temporal 12   (rendered and filtered
+//                                                  at 960 x 540, rebuilt at 1920 x 1080 from full-size first-hit guides: writes the large image)
 //   DRT_DEVICES=0,1,2,3,4,5,6,7 ./drt_render models/room.glb out.pfm 3840 2160 64 16  0 1.4 2  0 0 -1     (all GPUs of the node: stripes + RCCL gather)
 #include <DustRayTracer.hpp>
 #include <DustRayTracerGL.hpp>
@@ -27,12 +29,20 @@ int main(int argc, char **argv) {
         temporal = std::atoi(argv[argc - 1]);
         argc -= 2;
     }
-    if (argc < 7 || temporal < 0) {
-        std::fprintf(stderr, "usage: %s scene.glb out.pfm width height spp depth [px py pz fx fy fz] [--temporal K] [--denoise]\n", argv[0]);
+    long up_w = 0, up_h = 0;                              // --upscale OW OH: optional, last (before --temporal)
+    const bool upscale = argc > 3 && std::strcmp(argv[argc - 3], "--upscale") == 0;
+    if (upscale) {
+        up_w = std::atol(argv[argc - 2]);
+        up_h = std::atol(argv[argc - 1]);
+        argc -= 3;
+    }
+    if (argc < 7 || temporal < 0 || (upscale && (up_w <= 0 || up_h <= 0))) {
+        std::fprintf(stderr, "usage: %s scene.glb out.pfm width height spp depth [px py pz fx fy fz] [--upscale OW OH] [--temporal K] [--denoise]\n", argv[0]);
         return 2;
     }
     try {
-        const uint32_t W = (uint32_t)std::atoi(argv[3]), H = (uint32_t)std::atoi(argv[4]), spp = (uint32_t)std::atoi(argv[5]);
+        uint32_t W = (uint32_t)std::atoi(argv[3]), H = (uint32_t)std::atoi(argv[4]);
+        const uint32_t spp = (uint32_t)std::atoi(argv[5]);
         Scene scene;
         scene.loadGLTFmodel(argv[1]);
         BVHBuilder builder;                               // EditorLayer.cpp:52-55
@@ -87,6 +97,18 @@ int main(int argc, char **argv) {
             }
             renderer.ReadDenoisedTarget(rgba.data());
             std::printf("temporal: %d poses, %.3f ms per pose\n", temporal, total / (float)temporal);
+        }
+        if (upscale) {
+            // the frame (the filtered one when --denoise or --temporal made it) rebuilt at OW x OH, default parameters otherwise
+            drt_upscale_params p;
+            drt_default_upscale_params(&p);
+            p.source = (denoise || temporal > 0) ? 1 : 0;
+            float ums = 0;
+            renderer.Upscale(&cam, scene, (uint32_t)up_w, (uint32_t)up_h, &ums, &p);
+            std::printf("upscaled: %u x %u -> %ld x %ld, %.3f ms\n", W, H, up_w, up_h, ums);
+            W = (uint32_t)up_w; H = (uint32_t)up_h;
+            rgba.resize((size_t)W * H * 4);
+            renderer.ReadUpscaledTarget(rgba.data());
         }
         const std::string out(argv[2]);
         if (out.size() > 4 && out.compare(out.size() - 4, 4, ".png") == 0) {

@@ -356,12 +356,31 @@ public:
         drt::check(drt_renderer_set_settings(handle, &s));
         drt::check(drt_renderer_motion_vectors(handle, &c, prev_cam ? &pc : nullptr, scene.handle, out, stream));
     }
+    // Guide-driven upscaling of the frame to out_width x out_height (drt_renderer_upscale; blocking): the framebuffer, or with
+    // params->source == 1 the last Denoise / TemporalDenoise result, rebuilt at full size from full-size first-hit guides.
+    // params NULL = drt_default_upscale_params.  A multi-device renderer is refused (DRT_ERR_UNSUPPORTED).
+    void Upscale(Camera *cam, const Scene &scene, uint32_t out_width, uint32_t out_height, float *delta, const drt_upscale_params *params = nullptr) {
+        drt_upscale_params p;
+        drt_default_upscale_params(&p);
+        if (params) p = *params;
+        drt_settings s = m_RendererSettings.pod();
+        drt_camera c = cam->pod();
+        drt::check(drt_renderer_set_settings(handle, &s));
+        drt::check(drt_renderer_upscale(handle, &c, scene.handle, out_width, out_height, &p, delta));
+        m_UpscaledWidth = out_width; m_UpscaledHeight = out_height;
+    }
+    // the last Upscale result: RGBA32F, row 0 = bottom, out_width*out_height*4 floats
+    void ReadUpscaledTarget(float *dst) {
+        drt::check(drt_renderer_read_upscaled_rgba32f(handle, dst, (size_t)m_UpscaledWidth * m_UpscaledHeight * 4));
+    }
+    void *DeviceUpscaledTarget() { return drt_renderer_device_upscaled(handle); }
     // the history of the last TemporalDenoise, width*height*4 floats: which 0 = (colour rgb, N), 1 = (m1, m2, variance, weight sum)
     void ReadTemporal(int which, float *dst) {
         drt::check(drt_renderer_read_temporal(handle, which, dst, (size_t)getBufferWidth() * getBufferHeight() * 4));
     }
 
     RendererSettings m_RendererSettings;
+    uint32_t m_UpscaledWidth = 0, m_UpscaledHeight = 0;      // the size of the last Upscale
     drt_renderer *handle = nullptr;       // the (first) device's renderer
     drt_group *group = nullptr;           // set when the renderer spans several devices
 };
