@@ -1,31 +1,18 @@
-// drt_capi.cpp -- the C ABI of include/drt.h: scene handles, the renderer (device buffers, per-call
-// constants, launches, read-back) and error reporting.
+// drt_capi.cpp -- the C ABI of include/drt.h: scene handles, the renderer's lifecycle (device buffers, per-call constants, launches,
+// read-back), render batches, ray and radiance queries, refit, the debug entry points and error reporting.  The guide pass and the
+// filter stages (denoise, temporal, motion vectors, upscale) are in drt_capi_filters.cpp, what both share in renderer_state.hpp.
 //
 // Replaces class Renderer (Core/Renderer.hpp:14-47, Core/Renderer.cu) and InvokeRenderKernel
 // (Core/Kernel/RenderKernel.cu:37-58).  No GL interop: the framebuffer is a device float4 array.
-#include "../../include/drt.h"
+#include "renderer_state.hpp"
 
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <new>
 #include <stdexcept>
-#include <string>
 
-#include "device_scene.hpp"
-#include "render_kernels.hpp"
 #include "ray_query.hpp"
-#include "denoise.hpp"
-#include "temporal.hpp"
-#include "refit.hpp"
-#include "motion.hpp"
-#include "upscale.hpp"
-#include "radiance.hpp"
-#include "scene_host.hpp"
 #include "bvh_build_device.hpp"
 #include "png_decode.hpp"
 
@@ -34,11 +21,6 @@ using namespace drt;
 namespace {
 
 thread_local std::string g_error;
-
-int fail(int code, const std::string &msg) {
-    g_error = msg;
-    return code;
-}
 
 int from_exception() {
     try {
@@ -53,183 +35,178 @@ int from_exception() {
     } catch (...) { return fail(DRT_ERR_INVALID, "unknown error"); }
 }
 
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return fail(DRT_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));        \
-    } while (0)
-
-template <class T>
-struct DeviceArray {
-    T *ptr = nullptr;
-    size_t count = 0;
-    hipError_t upload(const std::vector<T> &host) {
-        release();
-        count = host.size();
-        size_t bytes = std::max<size_t>(host.size(), 1) * sizeof(T);
-        hipError_t e = hipMalloc((void **)&ptr, bytes);
-        if (e != hipSuccess) { ptr = nullptr; return e; }
-        if (!host.empty()) e = hipMemcpy(ptr, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice);
-        return e;
-    }
-    hipError_t alloc(size_t n) {                 // uninitialised
-        release();
-        hipError_t e = hipMalloc((void **)&ptr, std::max<size_t>(n, 1) * sizeof(T));
-        if (e != hipSuccess) { ptr = nullptr; return e; }
-        count = n;
-        return e;
-    }
-    void release() { if (ptr) (void)hipFree(ptr); ptr = nullptr; count = 0; }
-};
-
 }  // namespace
 
-struct drt_scene {
-    HostScene host;
-};
+int drt::fail(int code, const std::string &msg) {
+    g_error = msg;
+    return code;
+}
 
-struct drt_renderer {
-    int device = 0;
-    drt_settings settings;
-    uint32_t width = 0, height = 0;
-    uint32_t frame_index = 1;                 // m_FrameIndex, Renderer.hpp:41
-    uint32_t stripe_rows = 1, rank = 0, world = 1, local_rows = 0;
-    float *accum = nullptr, *rgba = nullptr;  // internal buffers
-    float *ext_accum = nullptr, *ext_rgba = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-    bool counting = false;
-    bool pending = false;                     // an asynchronous render was enqueued and not waited for yet
-    unsigned long long *counters = nullptr;
-    static constexpr int kMaxSpans = 64;
-    // One 32-byte record per tracing-kernel launch: {max(~first wave in), max(last wave out), status bits, -}.  The records come
-    // zeroed from a ring (one memset per kRecords launches); those of a batch are copied to pinned host memory on the stream, in
-    // front of ev_stop, so that drt_renderer_wait reads spans and status without another trip to the device.
-    static constexpr int kRecords = 1024;
-    unsigned long long *records = nullptr;    // device: kRecords x 4 words
-    unsigned long long *records_host = nullptr;   // pinned: the kMaxSpans records of the last batch
-    int records_used = 0, batch_first_record = 0;
-    int spans_used = 0;                       // launches of the last batch that have a record
-    int launches_last = 0;                     // tracing-kernel launches of the last batch (a batch is split by the sample budget)
-    float span_ms = 0.f;                       // sum of those spans, filled by drt_renderer_wait
-    int wall_clock_khz = 100000;
-    static constexpr int kCounters = 256;
-    unsigned int *tile_counter = nullptr;     // work queue heads of the tracing kernels: kCounters zeroed blocks (kQueueHeadBlockWords each), one per launch, re-zeroed
-    int counters_used = 0;                    // in one memset when all are spent (no memset in front of every launch)
-    void *samples = nullptr;                  // wave_queue: one float4 per (pixel, frame) of a launch
-    size_t samples_bytes = 0;
-    size_t sample_budget = (size_t)1 << 30;   // frames of one batch are split so that a launch needs at most this much
-    int num_cus = 256;
-    int frames_in_flight = 1;                 // drt_renderer_set_frames_in_flight
-    Tuning tune;                              // the environment switches, read by drt_renderer_create
-    TracerChoice choice;                      // the tracing kernel of the last batch (choose_tracer) ...
-    LaunchShape shape;                        // ... and the shape of its last launch
-    WaveQueueCache wq_cache;                  // measured choice among wave_queue's launch packagings
-    PoolScratch pool_scratch;
-    uint32_t pool_t_class[3] = { 0, 0, 0 };   // leaf-size classes of the uploaded scene (path_pool's T queues)
-    bool scene_has_alpha = false;
-    int vote_node = 12, vote_shade = 44, vote_dir = 4, vote_spec = 8;
-    int leaf_chain = -1;                              // DRT_LEAF_CHAIN: -1 = by tree depth (<= 4 levels), 0 / 1 = forced
-    int vote_tail_node = 4, vote_tail_shade = 36;    // once the queue is empty (DRT_VOTE_TN / DRT_VOTE_TS): pops stop waiting for company   // wave_queue phase-voting thresholds (DRT_VOTE_N/S/R/P override)
-    // device copy of the scene last rendered
-    const drt_scene *uploaded_scene = nullptr;
-    uint64_t uploaded_revision = 0;
-    DeviceArray<InnerNode> d_inner;
-    DeviceArray<LeafRange> d_leaves;
-    DeviceArray<TriHot> d_hot;
-    DeviceArray<TriCold> d_cold;
-    DeviceArray<MatDev> d_mats;
-    DeviceArray<MatExt> d_mats_ext;
-    drt_material_model material_model = { 0, 0, 1.0f, 0 };       // emissive, specular, emissive_scale, transmission
-    DeviceArray<TexDev> d_texs;
-    DeviceArray<uint8_t> d_texels;
-    SceneView view;
-    int bvh_depth = 0;
-    // batched ray queries (drt_renderer_trace_rays / _occluded): claim heads, HBM stack levels, and the event after the last
-    // query launch -- the next query waits for it on its own stream (they share heads and stack), a scene re-upload on the host
-    hipEvent_t ev_query = nullptr;
-    hipStream_t query_stream = nullptr;
-    bool query_recorded = false;
-    unsigned int *rq_heads = nullptr;
-    void *rq_stack = nullptr;
-    size_t rq_stack_bytes = 0;
-    FilterKernel filter_kernel = FilterKernel::automatic;      // DRT_FILTER_KERNEL=lds / taps: one a-trous kernel for every pass (unset, or any other value: launch_atrous's rule)
-    int rq_refill_min = 16;                    // DRT_RQ_REFILL: idle lanes that make a wave claim new rays (64 = only when all are)
-    // drt_renderer_denoise: frame 1's guides and the two float4 buffers the passes ping-pong between, allocated by the first call,
-    // freed by resize; denoised = the one that holds the last result (-1: none yet)
-    void *dn_guides = nullptr;
-    float4 *dn_buf[2] = { nullptr, nullptr };
-    int denoised = -1;
-    hipEvent_t ev_dn_start = nullptr, ev_dn_stop = nullptr;
-    // drt_renderer_temporal_denoise: the ping-pong history (three float4 records per pixel and half), allocated by the first call,
-    // freed by resize, destroy and drt_renderer_temporal_reset; tp_cur = the half the last call wrote (-1: no history), tp_cam =
-    // that call's camera as a pinhole.  The filtered result lands in dn_buf.
-    float4 *tp_hist[2][3] = { { nullptr, nullptr, nullptr }, { nullptr, nullptr, nullptr } };
-    int tp_cur = -1;
-    PrevCamera tp_cam;
-    // drt_renderer_refit: the uploaded scene's refit metadata (refit.hpp), built by the first refit after an upload and freed
-    // with the scene copy; out = the root box and the error word the kernels leave
-    bool rf_built = false;
-    DeviceArray<int32_t> rf_order;
-    DeviceArray<float4> rf_avg;
-    DeviceArray<float> rf_ext;
-    DeviceArray<RefitLeaf> rf_leaves;
-    DeviceArray<RefitInner> rf_levels;
-    DeviceArray<uint32_t> rf_height_begin;
-    DeviceArray<float> rf_out;
-    std::vector<uint32_t> rf_heights;
-    int rf_top_nodes = kRefitTopNodes;         // DRT_REFIT_TOP: 0 = one launch per height up to the root
-    int rf_launches = 0;
-    hipEvent_t ev_rf_start = nullptr, ev_rf_stop = nullptr, ev_rf_dep = nullptr;
-    // drt_renderer_track_motion: mv_snap = the TriHot records as they were before the first refit since the last temporal call /
-    // drt_renderer_motion_advance (valid while mv_armed; the buffer is kept for reuse, dropped with the scene copy),
-    // mv_guides = drt_renderer_motion_vectors' guide buffer
-    bool mv_track = false, mv_armed = false;
-    DeviceArray<TriHot> mv_snap;
-    void *mv_guides = nullptr;
-    // drt_renderer_upscale: us_guides = frame 1's guides at the frame size followed by those at the output size, us_out = the
-    // upscaled image, float4[us_width * us_height]; allocated by the first call, again when the output size changes, freed by
-    // resize and destroy (us_width == 0: no result yet)
-    void *us_guides = nullptr;
-    float4 *us_out = nullptr;
-    uint32_t us_width = 0, us_height = 0;
+// ------------------------------------------------------------------ steps that several entry points take (renderer_state.hpp)
+static int copy_scene(drt_renderer *r, const drt_scene *scene) {
+    if (r->uploaded_scene == scene && r->uploaded_revision == scene->host.revision) return DRT_OK;
+    PackedScene ps;
+    try { ps = scene->host.pack(); } catch (...) { return from_exception(); }
+    if (r->query_recorded) HIP_TRY(hipEventSynchronize(r->ev_query));     // a query launch in flight reads the old buffers
+    r->free_scene();
+    HIP_TRY(r->d_inner.upload(ps.inner));
+    HIP_TRY(r->d_leaves.upload(ps.leaves));
+    HIP_TRY(r->d_hot.upload(ps.tri_hot));
+    HIP_TRY(r->d_cold.upload(ps.tri_cold));
+    HIP_TRY(r->d_mats.upload(ps.mats));
+    HIP_TRY(r->d_mats_ext.upload(ps.mats_ext));
+    HIP_TRY(r->d_texs.upload(ps.texs));
+    HIP_TRY(r->d_texels.upload(ps.texels));
+    SceneView &v = r->view;
+    v.inner = r->d_inner.ptr; v.leaves = r->d_leaves.ptr; v.tri_hot = r->d_hot.ptr; v.tri_cold = r->d_cold.ptr;
+    v.mats = r->d_mats.ptr; v.mats_ext = r->d_mats_ext.ptr; v.texs = r->d_texs.ptr; v.texels = r->d_texels.ptr;
+    v.n_inner = (uint32_t)ps.inner.size(); v.n_leaves = (uint32_t)ps.leaves.size();
+    v.n_tris = (uint32_t)ps.tri_hot.size(); v.n_mats = (uint32_t)ps.mats.size(); v.n_texs = (uint32_t)ps.texs.size();
+    v.root_ref = ps.root_ref;
+    std::memcpy(v.root_min, ps.root_min, 12);
+    std::memcpy(v.root_max, ps.root_max, 12);
+    r->bvh_depth = ps.depth;
+    r->scene_has_alpha = ps.any_alpha_texture;
+    path_pool_leaf_classes(ps.leaves, r->pool_t_class);
+    if (r->tune.t_class_set) std::memcpy(r->pool_t_class, r->tune.t_class, sizeof r->pool_t_class);
+    if (r->tune.pool_verbose) std::fprintf(stderr, "path_pool leaf classes: %u %u %u\n", r->pool_t_class[0], r->pool_t_class[1], r->pool_t_class[2]);
+    r->uploaded_scene = scene;
+    r->uploaded_revision = scene->host.revision;
+    return DRT_OK;
+}
 
-    float *cur_accum() const { return ext_accum ? ext_accum : accum; }
-    float *cur_rgba() const { return ext_rgba ? ext_rgba : rgba; }
-    void free_scene() {
-        d_inner.release(); d_leaves.release(); d_hot.release(); d_cold.release();
-        d_mats.release(); d_mats_ext.release(); d_texs.release(); d_texels.release();
-        rf_order.release(); rf_avg.release(); rf_ext.release(); rf_leaves.release(); rf_levels.release();
-        rf_height_begin.release(); rf_out.release();
-        rf_built = false;
-        mv_snap.release();
-        mv_armed = false;
-        uploaded_scene = nullptr;
+int drt::upload_scene(drt_renderer *r, const drt_scene *scene) {
+    if (int rc = copy_scene(r, scene)) return rc;
+    if (r->bvh_depth > 64) return fail(DRT_ERR_UNSUPPORTED, "BVH deeper than 64 levels (the reference's traversal stack, BVHTraversal.cuh:17)");
+    return DRT_OK;
+}
+
+// Camera::GetRay's per-frame constants (Camera.cu:84-103) for a width x height image, computed on the host with the same fp32
+// operations in the same order (host libm for tan).
+CamConst drt::camera_const(const drt_camera *cam, float width, float height) {      // Camera.cu:82 takes floats
+    float theta = cam->vfov_rad / 2;
+    float fov_factor = tanf(theta / 2.0f);
+    float aspect_ratio = width / height;
+    float plane_h = 2.0f * fov_factor * cam->focus_dist;
+    float plane_w = plane_h * aspect_ratio;
+    V3 forward_dir = normalize(V3{ cam->forward[0], cam->forward[1], cam->forward[2] });
+    V3 right_dir = normalize(cross(forward_dir, V3{ 0, 1, 0 }));
+    V3 up_dir = cross(right_dir, forward_dir);
+    V3 horizontal = plane_w * right_dir, vertical = plane_h * up_dir;
+    const float PI = 3.14159265359f;
+    float defocus_radius = cam->focus_dist * tanf((cam->defocus_angle * (PI / 180.f)) / 2.0f);
+    V3 disk_u = defocus_radius * right_dir, disk_v = defocus_radius * up_dir;
+    V3 fwd_focus = forward_dir * cam->focus_dist;
+    auto put = [](float *dst, V3 v) { dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; };
+    CamConst c;
+    std::memcpy(c.cam_pos, cam->position, 12);
+    put(c.fwd_focus, fwd_focus); put(c.horizontal, horizontal); put(c.vertical, vertical);
+    put(c.disk_u, disk_u); put(c.disk_v, disk_v);
+    c.defocus = !(cam->defocus_angle <= 0);
+    c.exposure = cam->exposure;
+    return c;
+}
+
+// Per-frame constants of Camera::GetRay (Camera.cu:84-103) and RayGen (RayGen.cuh:68-72), computed on the
+// host with the same fp32 operations in the same order (host libm for tan/sin/cos).
+// width, height: the frame the constants are for; 0 = the renderer's (a guide pass at another size: drt_renderer_upscale).
+void drt::fill_frame_params(const drt_renderer *r, const drt_camera *cam, FrameParams &fp, uint32_t width, uint32_t height) {
+    const drt_settings &s = r->settings;
+    if (width == 0 || height == 0) { width = r->width; height = r->height; }
+    auto put = [](float *dst, V3 v) { dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; };
+    if (cam) {                                 // (radiance queries have no camera: their rays carry what it would give)
+        const CamConst c = camera_const(cam, (float)width, (float)height);
+        std::memcpy(fp.cam_pos, c.cam_pos, 12);
+        std::memcpy(fp.fwd_focus, c.fwd_focus, 12); std::memcpy(fp.horizontal, c.horizontal, 12); std::memcpy(fp.vertical, c.vertical, 12);
+        std::memcpy(fp.disk_u, c.disk_u, 12); std::memcpy(fp.disk_v, c.disk_v, 12);
+        fp.defocus = c.defocus;
+        fp.exposure = c.exposure;
     }
-    void free_motion_guides() {
-        if (mv_guides) (void)hipFree(mv_guides);
-        mv_guides = nullptr;
+
+    float sx = sinf(s.sunlight_dir[0]), sy = sinf(s.sunlight_dir[1]), cx = cosf(s.sunlight_dir[0]);
+    put(fp.sunpos, V3{ sx * (1 - sy), sy, cx * (1 - sy) } * 100.0f);
+    put(fp.suncol, V3{ s.sunlight_color[0], s.sunlight_color[1], s.sunlight_color[2] } * s.sunlight_intensity);
+    std::memcpy(fp.sky_color, s.sky_color, 12);
+    fp.sky_intensity = s.sky_intensity;
+    fp.gamma_correction = s.gamma_correction != 0; fp.tone_mapping = s.tone_mapping != 0;
+    fp.enable_sunlight = s.enable_sunlight != 0;
+    fp.bounce_limit = s.ray_bounce_limit;
+    fp.render_mode = s.render_mode; fp.debug_mode = s.debug_mode;
+    fp.ext_emissive = r->material_model.emissive != 0; fp.ext_specular = r->material_model.specular != 0;
+    fp.ext_emissive_scale = r->material_model.emissive_scale;
+    fp.ext_transmission = r->material_model.transmission != 0;
+    fp.width = width; fp.height = height;
+    fp.stripe_rows = r->stripe_rows; fp.rank = r->rank; fp.world = r->world; fp.local_rows = r->local_rows;
+    fp.accum = r->cur_accum(); fp.rgba = r->cur_rgba();
+    fp.counters = r->counting ? r->counters.ptr : nullptr;
+    fp.vote_node = r->vote_node; fp.vote_shade = r->vote_shade; fp.vote_dir = r->vote_dir; fp.vote_spec = r->vote_spec; fp.frames_in_flight = r->frames_in_flight; fp.vote_tail_node = r->vote_tail_node; fp.vote_tail_shade = r->vote_tail_shade;
+    {   // tile rows are visited with a golden-ratio stride (kernel_wave_queue.hip, DRT_CHUNK_ORDER)
+        const uint32_t tiles_y = (r->local_rows + 7) / 8;
+        uint32_t step = 1;
+        if (tiles_y > 2 && tiles_y < 65536) {
+            step = std::max<uint32_t>(1, (uint32_t)(0.6180339887 * tiles_y + 0.5));
+            auto gcd = [](uint32_t a, uint32_t b) { while (b) { uint32_t t = a % b; a = b; b = t; } return a; };
+            while (gcd(step, tiles_y) != 1) step++;
+        }
+        fp.row_step = step;
     }
-    void free_upscale() {
-        if (us_guides) (void)hipFree(us_guides);
-        if (us_out) (void)hipFree(us_out);
-        us_guides = nullptr;
-        us_out = nullptr;
-        us_width = us_height = 0;
+    fp.leaf_chain = r->leaf_chain < 0 ? (r->bvh_depth <= 4 ? 1 : 0) : (r->leaf_chain != 0);
+}
+
+bool drt::on_renderer_device(const drt_renderer *r, const void *p) {
+    hipPointerAttribute_t at;
+    std::memset(&at, 0, sizeof at);
+    const hipError_t e = hipPointerGetAttributes(&at, p);
+    (void)hipGetLastError();
+    return e == hipSuccess && (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged) && at.device == r->device;
+}
+
+int drt::query_order(drt_renderer *r, hipStream_t s) {
+    if (r->query_recorded && r->query_stream != s) HIP_TRY(hipStreamWaitEvent(s, r->ev_query, 0));
+    return DRT_OK;
+}
+int drt::query_recorded(drt_renderer *r, hipStream_t s) {
+    HIP_TRY(hipEventRecord(r->ev_query, s));
+    r->query_stream = s;
+    r->query_recorded = true;
+    return DRT_OK;
+}
+
+int drt::traversal_scratch(drt_renderer *r, hipStream_t s, bool occluded, bool heads) {
+    if (heads && !r->rq_heads.ptr) HIP_TRY(r->rq_heads.alloc(kRqHeadWords));
+    const size_t stack_bytes = ray_query_stack_bytes(r->num_cus, r->bvh_depth, occluded);
+    if (stack_bytes > r->rq_stack.bytes()) {
+        if (r->query_recorded) HIP_TRY(hipEventSynchronize(r->ev_query));      // the launch in flight uses the one that goes
+        HIP_TRY(r->rq_stack.alloc(stack_bytes / sizeof(uint32_t)));
     }
-    void free_denoise() {
-        if (dn_guides) (void)hipFree(dn_guides);
-        for (float4 *&b : dn_buf) { if (b) (void)hipFree(b); b = nullptr; }
-        dn_guides = nullptr;
-        denoised = -1;
-    }
-    void free_temporal() {
-        for (auto &half : tp_hist)
-            for (float4 *&b : half) { if (b) (void)hipFree(b); b = nullptr; }
-        tp_cur = -1;
-    }
-};
+    if (heads) HIP_TRY(hipMemsetAsync(r->rq_heads.ptr, 0, r->rq_heads.bytes(), s));
+    return DRT_OK;
+}
+
+int drt::whole_frame(const drt_renderer *r, const char *who) {
+    if (r->world > 1) return fail(DRT_ERR_UNSUPPORTED, std::string(who) + " the whole frame: a sharded renderer (world > 1) holds only its stripes");
+    return DRT_OK;
+}
+
+int drt::stage_open(drt_renderer *r, const char *who) {
+    if (r->width == 0 || r->height == 0) return fail(DRT_ERR_INVALID, "ResizeBuffer has not been called");
+    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
+    if (int rc = who ? whole_frame(r, who) : DRT_OK) return rc;
+    HIP_TRY(hipSetDevice(r->device));
+    (void)hipGetLastError();                   // (see render_batch_impl: only this call's own errors count)
+    return DRT_OK;
+}
+
+int drt::read_back(drt_renderer *r, const float *src, int comps, float *dst, size_t dst_floats) {
+    if (!r || !dst) return fail(DRT_ERR_INVALID, "null argument");
+    size_t need = (size_t)r->width * r->local_rows * (size_t)comps;
+    if (dst_floats < need) return fail(DRT_ERR_INVALID, "destination too small");
+    if (need == 0) return DRT_OK;
+    HIP_TRY(hipSetDevice(r->device));
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    HIP_TRY(hipMemcpy(dst, src, need * sizeof(float), hipMemcpyDeviceToHost));
+    return DRT_OK;
+}
 
 extern "C" {
 
@@ -419,18 +396,14 @@ uint32_t drt_shard_rows(uint32_t height, uint32_t stripe_rows, uint32_t rank, ui
 
 static int realloc_buffers(drt_renderer *r) {
     HIP_TRY(hipSetDevice(r->device));
-    if (r->accum) { (void)hipFree(r->accum); r->accum = nullptr; }
-    if (r->rgba) { (void)hipFree(r->rgba); r->rgba = nullptr; }
-    r->free_denoise();
-    r->free_temporal();
-    r->free_motion_guides();
-    r->free_upscale();
+    r->accum.release();
+    r->rgba.release();
+    r->free_stages();
     r->local_rows = drt_shard_rows(r->height, r->stripe_rows, r->rank, r->world);
     size_t px = std::max<size_t>((size_t)r->width * r->local_rows, 1);
-    HIP_TRY(hipMalloc((void **)&r->accum, px * 3 * sizeof(float)));
-    HIP_TRY(hipMalloc((void **)&r->rgba, px * 4 * sizeof(float)));
-    HIP_TRY(hipMemset(r->rgba, 0, px * 4 * sizeof(float)));
-    return DRT_OK;
+    HIP_TRY(r->accum.alloc(px * 3));
+    HIP_TRY(r->rgba.alloc_zeroed(px * 4));
+    return drt_renderer_reset(r);
 }
 
 drt_renderer *drt_renderer_create(int32_t device) {
@@ -489,14 +462,12 @@ drt_renderer *drt_renderer_create(int32_t device) {
     if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) == hipSuccess && khz > 0) r->wall_clock_khz = khz;
     r->rq_refill_min = std::min(64, std::max(1, env_int("DRT_RQ_REFILL", r->rq_refill_min)));
     r->rf_top_nodes = std::max(0, env_int("DRT_REFIT_TOP", r->rf_top_nodes));
-    if (hipEventCreate(&r->ev_start) != hipSuccess || hipEventCreate(&r->ev_stop) != hipSuccess ||
-        hipEventCreateWithFlags(&r->ev_query, hipEventDisableTiming) != hipSuccess ||
-        hipMalloc((void **)&r->counters, sizeof(drt_counters)) != hipSuccess ||
-        hipMalloc((void **)&r->records, sizeof(unsigned long long) * 4 * drt_renderer::kRecords) != hipSuccess ||
-        hipMemset(r->records, 0, sizeof(unsigned long long) * 4 * drt_renderer::kRecords) != hipSuccess ||
-        hipHostMalloc((void **)&r->records_host, sizeof(unsigned long long) * 4 * drt_renderer::kMaxSpans, hipHostMallocDefault) != hipSuccess ||
-        hipMalloc((void **)&r->tile_counter, sizeof(unsigned int) * drt_renderer::kCounters * kQueueHeadBlockWords) != hipSuccess ||
-        hipMemset(r->tile_counter, 0, sizeof(unsigned int) * drt_renderer::kCounters * kQueueHeadBlockWords) != hipSuccess) {
+    if (r->ev_start.create() != hipSuccess || r->ev_stop.create() != hipSuccess ||
+        r->ev_query.create(hipEventDisableTiming) != hipSuccess ||
+        r->counters.alloc(sizeof(drt_counters) / sizeof(unsigned long long)) != hipSuccess ||
+        r->records.alloc_zeroed(4 * (size_t)drt_renderer::kRecords) != hipSuccess ||
+        r->records_host.alloc(4 * (size_t)drt_renderer::kMaxSpans) != hipSuccess ||
+        r->tile_counter.alloc_zeroed((size_t)drt_renderer::kCounters * kQueueHeadBlockWords) != hipSuccess) {
         fail(DRT_ERR_DEVICE, "cannot create HIP events / counter buffer");
         drt_renderer_destroy(r);
         return nullptr;
@@ -504,38 +475,7 @@ drt_renderer *drt_renderer_create(int32_t device) {
     return r;
 }
 
-void drt_renderer_destroy(drt_renderer *r) {
-    if (!r) return;
-    (void)hipSetDevice(r->device);
-    r->free_scene();
-    if (r->accum) (void)hipFree(r->accum);
-    if (r->rgba) (void)hipFree(r->rgba);
-    if (r->counters) (void)hipFree(r->counters);
-    if (r->records) (void)hipFree(r->records);
-    if (r->records_host) (void)hipHostFree(r->records_host);
-    if (r->tile_counter) (void)hipFree(r->tile_counter);
-    if (r->tune.stats) (void)hipFree(r->tune.stats);
-    if (r->pool_scratch.aux) (void)hipFree(r->pool_scratch.aux);
-    if (r->pool_scratch.aux_slot) (void)hipFree(r->pool_scratch.aux_slot);
-    if (r->pool_scratch.aux_light) (void)hipFree(r->pool_scratch.aux_light);
-    if (r->pool_scratch.aux_next) (void)hipFree(r->pool_scratch.aux_next);
-    if (r->pool_scratch.aux_stack) (void)hipFree(r->pool_scratch.aux_stack);
-    if (r->samples) (void)hipFree(r->samples);
-    if (r->rq_heads) (void)hipFree(r->rq_heads);
-    if (r->rq_stack) (void)hipFree(r->rq_stack);
-    if (r->ev_query) (void)hipEventDestroy(r->ev_query);
-    r->free_denoise();
-    r->free_temporal();
-    r->free_motion_guides();
-    r->free_upscale();
-    if (r->ev_dn_start) (void)hipEventDestroy(r->ev_dn_start);
-    if (r->ev_dn_stop) (void)hipEventDestroy(r->ev_dn_stop);
-    for (hipEvent_t ev : { r->ev_rf_start, r->ev_rf_stop, r->ev_rf_dep })
-        if (ev) (void)hipEventDestroy(ev);
-    if (r->ev_start) (void)hipEventDestroy(r->ev_start);
-    if (r->ev_stop) (void)hipEventDestroy(r->ev_stop);
-    delete r;
-}
+void drt_renderer_destroy(drt_renderer *r) { delete r; }         // (~drt_renderer selects the device; the members release)
 
 int drt_renderer_reset(drt_renderer *r) {                      // Renderer.cu:132-136
     if (!r) return fail(DRT_ERR_INVALID, "null renderer");
@@ -552,21 +492,14 @@ int drt_renderer_resize(drt_renderer *r, uint32_t width, uint32_t height) {   //
     if ((uint64_t)width * height > (1ull << 31)) return fail(DRT_ERR_INVALID, "framebuffer too large (pixel index is 32-bit, RayGen.cuh:74)");
     if (r->ext_accum || r->ext_rgba) return fail(DRT_ERR_INVALID, "unbind external buffers before resizing");
     r->width = width; r->height = height;
-    int rc = realloc_buffers(r);
-    if (rc != DRT_OK) return rc;
-    return drt_renderer_reset(r);
+    return realloc_buffers(r);
 }
 
 int drt_renderer_set_shard(drt_renderer *r, uint32_t stripe_rows, uint32_t rank, uint32_t world) {
     if (!r || stripe_rows == 0 || world == 0 || rank >= world) return fail(DRT_ERR_INVALID, "bad shard description");
     if (r->ext_accum || r->ext_rgba) return fail(DRT_ERR_INVALID, "unbind external buffers before re-sharding");
     r->stripe_rows = stripe_rows; r->rank = rank; r->world = world;
-    if (r->width && r->height) {
-        int rc = realloc_buffers(r);
-        if (rc != DRT_OK) return rc;
-        return drt_renderer_reset(r);
-    }
-    return DRT_OK;
+    return r->width && r->height ? realloc_buffers(r) : DRT_OK;
 }
 
 int drt_renderer_bind_buffers(drt_renderer *r, void *device_accum, void *device_rgba) {
@@ -626,7 +559,7 @@ int drt_renderer_get_counters(drt_renderer *r, drt_counters *out) {
     if (!r || !out) return fail(DRT_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(r->device));
     HIP_TRY(hipStreamSynchronize(r->stream));
-    HIP_TRY(hipMemcpy(out, r->counters, sizeof *out, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, r->counters.ptr, sizeof *out, hipMemcpyDeviceToHost));
     return DRT_OK;
 }
 
@@ -698,110 +631,6 @@ int drt_renderer_kernel_info(const drt_renderer *r, char *buf, size_t cap) {
     return DRT_OK;
 }
 
-static int upload_scene(drt_renderer *r, const drt_scene *scene) {
-    if (r->uploaded_scene == scene && r->uploaded_revision == scene->host.revision) return DRT_OK;
-    PackedScene ps;
-    try { ps = scene->host.pack(); } catch (...) { return from_exception(); }
-    if (r->query_recorded) HIP_TRY(hipEventSynchronize(r->ev_query));     // a query launch in flight reads the old buffers
-    r->free_scene();
-    HIP_TRY(r->d_inner.upload(ps.inner));
-    HIP_TRY(r->d_leaves.upload(ps.leaves));
-    HIP_TRY(r->d_hot.upload(ps.tri_hot));
-    HIP_TRY(r->d_cold.upload(ps.tri_cold));
-    HIP_TRY(r->d_mats.upload(ps.mats));
-    HIP_TRY(r->d_mats_ext.upload(ps.mats_ext));
-    HIP_TRY(r->d_texs.upload(ps.texs));
-    HIP_TRY(r->d_texels.upload(ps.texels));
-    SceneView &v = r->view;
-    v.inner = r->d_inner.ptr; v.leaves = r->d_leaves.ptr; v.tri_hot = r->d_hot.ptr; v.tri_cold = r->d_cold.ptr;
-    v.mats = r->d_mats.ptr; v.mats_ext = r->d_mats_ext.ptr; v.texs = r->d_texs.ptr; v.texels = r->d_texels.ptr;
-    v.n_inner = (uint32_t)ps.inner.size(); v.n_leaves = (uint32_t)ps.leaves.size();
-    v.n_tris = (uint32_t)ps.tri_hot.size(); v.n_mats = (uint32_t)ps.mats.size(); v.n_texs = (uint32_t)ps.texs.size();
-    v.root_ref = ps.root_ref;
-    std::memcpy(v.root_min, ps.root_min, 12);
-    std::memcpy(v.root_max, ps.root_max, 12);
-    r->bvh_depth = ps.depth;
-    r->scene_has_alpha = ps.any_alpha_texture;
-    path_pool_leaf_classes(ps.leaves, r->pool_t_class);
-    if (r->tune.t_class_set) std::memcpy(r->pool_t_class, r->tune.t_class, sizeof r->pool_t_class);
-    if (r->tune.pool_verbose) std::fprintf(stderr, "path_pool leaf classes: %u %u %u\n", r->pool_t_class[0], r->pool_t_class[1], r->pool_t_class[2]);
-    r->uploaded_scene = scene;
-    r->uploaded_revision = scene->host.revision;
-    return DRT_OK;
-}
-
-// Camera::GetRay's per-frame constants (Camera.cu:84-103) for a width x height image, computed on the host with the same fp32
-// operations in the same order (host libm for tan).
-static CamConst camera_const(const drt_camera *cam, float width, float height) {      // Camera.cu:82 takes floats
-    float theta = cam->vfov_rad / 2;
-    float fov_factor = tanf(theta / 2.0f);
-    float aspect_ratio = width / height;
-    float plane_h = 2.0f * fov_factor * cam->focus_dist;
-    float plane_w = plane_h * aspect_ratio;
-    V3 forward_dir = normalize(V3{ cam->forward[0], cam->forward[1], cam->forward[2] });
-    V3 right_dir = normalize(cross(forward_dir, V3{ 0, 1, 0 }));
-    V3 up_dir = cross(right_dir, forward_dir);
-    V3 horizontal = plane_w * right_dir, vertical = plane_h * up_dir;
-    const float PI = 3.14159265359f;
-    float defocus_radius = cam->focus_dist * tanf((cam->defocus_angle * (PI / 180.f)) / 2.0f);
-    V3 disk_u = defocus_radius * right_dir, disk_v = defocus_radius * up_dir;
-    V3 fwd_focus = forward_dir * cam->focus_dist;
-    auto put = [](float *dst, V3 v) { dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; };
-    CamConst c;
-    std::memcpy(c.cam_pos, cam->position, 12);
-    put(c.fwd_focus, fwd_focus); put(c.horizontal, horizontal); put(c.vertical, vertical);
-    put(c.disk_u, disk_u); put(c.disk_v, disk_v);
-    c.defocus = !(cam->defocus_angle <= 0);
-    c.exposure = cam->exposure;
-    return c;
-}
-
-// Per-frame constants of Camera::GetRay (Camera.cu:84-103) and RayGen (RayGen.cuh:68-72), computed on the
-// host with the same fp32 operations in the same order (host libm for tan/sin/cos).
-// width, height: the frame the constants are for; 0 = the renderer's (a guide pass at another size: drt_renderer_upscale).
-static void fill_frame_params(const drt_renderer *r, const drt_camera *cam, FrameParams &fp, uint32_t width = 0, uint32_t height = 0) {
-    const drt_settings &s = r->settings;
-    if (width == 0 || height == 0) { width = r->width; height = r->height; }
-    auto put = [](float *dst, V3 v) { dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; };
-    if (cam) {                                 // (radiance queries have no camera: their rays carry what it would give)
-        const CamConst c = camera_const(cam, (float)width, (float)height);
-        std::memcpy(fp.cam_pos, c.cam_pos, 12);
-        std::memcpy(fp.fwd_focus, c.fwd_focus, 12); std::memcpy(fp.horizontal, c.horizontal, 12); std::memcpy(fp.vertical, c.vertical, 12);
-        std::memcpy(fp.disk_u, c.disk_u, 12); std::memcpy(fp.disk_v, c.disk_v, 12);
-        fp.defocus = c.defocus;
-        fp.exposure = c.exposure;
-    }
-
-    float sx = sinf(s.sunlight_dir[0]), sy = sinf(s.sunlight_dir[1]), cx = cosf(s.sunlight_dir[0]);
-    put(fp.sunpos, V3{ sx * (1 - sy), sy, cx * (1 - sy) } * 100.0f);
-    put(fp.suncol, V3{ s.sunlight_color[0], s.sunlight_color[1], s.sunlight_color[2] } * s.sunlight_intensity);
-    std::memcpy(fp.sky_color, s.sky_color, 12);
-    fp.sky_intensity = s.sky_intensity;
-    fp.gamma_correction = s.gamma_correction != 0; fp.tone_mapping = s.tone_mapping != 0;
-    fp.enable_sunlight = s.enable_sunlight != 0;
-    fp.bounce_limit = s.ray_bounce_limit;
-    fp.render_mode = s.render_mode; fp.debug_mode = s.debug_mode;
-    fp.ext_emissive = r->material_model.emissive != 0; fp.ext_specular = r->material_model.specular != 0;
-    fp.ext_emissive_scale = r->material_model.emissive_scale;
-    fp.ext_transmission = r->material_model.transmission != 0;
-    fp.width = width; fp.height = height;
-    fp.stripe_rows = r->stripe_rows; fp.rank = r->rank; fp.world = r->world; fp.local_rows = r->local_rows;
-    fp.accum = r->cur_accum(); fp.rgba = r->cur_rgba();
-    fp.counters = r->counting ? r->counters : nullptr;
-    fp.vote_node = r->vote_node; fp.vote_shade = r->vote_shade; fp.vote_dir = r->vote_dir; fp.vote_spec = r->vote_spec; fp.frames_in_flight = r->frames_in_flight; fp.vote_tail_node = r->vote_tail_node; fp.vote_tail_shade = r->vote_tail_shade;
-    {   // tile rows are visited with a golden-ratio stride (kernel_wave_queue.hip, DRT_CHUNK_ORDER)
-        const uint32_t tiles_y = (r->local_rows + 7) / 8;
-        uint32_t step = 1;
-        if (tiles_y > 2 && tiles_y < 65536) {
-            step = std::max<uint32_t>(1, (uint32_t)(0.6180339887 * tiles_y + 0.5));
-            auto gcd = [](uint32_t a, uint32_t b) { while (b) { uint32_t t = a % b; a = b; b = t; } return a; };
-            while (gcd(step, tiles_y) != 1) step++;
-        }
-        fp.row_step = step;
-    }
-    fp.leaf_chain = r->leaf_chain < 0 ? (r->bvh_depth <= 4 ? 1 : 0) : (r->leaf_chain != 0);
-}
-
 // The tracing kernel of a batch and its build: every rule that chooses one is here.  Returns nullptr, or why the
 // batch cannot be rendered (DRT_ERR_UNSUPPORTED).
 static const char *choose_tracer(const Tuning &tune, const SceneView &sc, int bvh_depth, bool scene_has_alpha, const FrameParams &fp, TracerChoice &c) {
@@ -850,9 +679,7 @@ static int render_batch_impl(drt_renderer *r, const drt_camera *cam, const drt_s
     // hipGetLastError() after a launch reports the last error of ANY earlier runtime call of this thread -- also one that another
     // library made and handled (RCCL probing peers answers "invalid device ordinal" on a one-GPU box): start from a clean slate
     (void)hipGetLastError();
-    int rc = upload_scene(r, scene);
-    if (rc != DRT_OK) return rc;
-    if (r->bvh_depth > 64) return fail(DRT_ERR_UNSUPPORTED, "BVH deeper than 64 levels (the reference's traversal stack, BVHTraversal.cuh:17)");
+    if (int rc = upload_scene(r, scene)) return rc;
 
     FrameParams fp;
     std::memset(&fp, 0, sizeof fp);
@@ -862,7 +689,7 @@ static int render_batch_impl(drt_renderer *r, const drt_camera *cam, const drt_s
     if (const char *why = choose_tracer(r->tune, r->view, r->bvh_depth, r->scene_has_alpha, fp, r->choice)) return fail(DRT_ERR_UNSUPPORTED, why);
     const TracerChoice &choice = r->choice;
     r->shape = LaunchShape{};
-    if (r->counting) HIP_TRY(hipMemsetAsync(r->counters, 0, sizeof(drt_counters), r->stream));
+    if (r->counting) HIP_TRY(hipMemsetAsync(r->counters.ptr, 0, sizeof(drt_counters), r->stream));
 
     r->spans_used = 0;
     HIP_TRY(hipEventRecord(r->ev_start, r->stream));                   // Renderer.cu:97
@@ -874,42 +701,38 @@ static int render_batch_impl(drt_renderer *r, const drt_camera *cam, const drt_s
         const size_t per_frame = (size_t)r->width * r->local_rows * 4 * sizeof(float);
         uint32_t frames_per_launch = (uint32_t)std::max<size_t>(1, std::min<size_t>(n_frames, r->sample_budget / std::max<size_t>(per_frame, 1)));
         const size_t need = per_frame * frames_per_launch;
-        if (need > r->samples_bytes) {
-            if (r->samples) { (void)hipFree(r->samples); r->samples = nullptr; r->samples_bytes = 0; }
-            HIP_TRY(hipMalloc(&r->samples, std::max<size_t>(need, 16)));
-            r->samples_bytes = need;
-        }
+        if (need > r->samples.bytes()) HIP_TRY(r->samples.alloc(need / sizeof(float4)));
         r->spans_used = 0;
         r->launches_last = 0;
         if (r->records_used + drt_renderer::kMaxSpans > drt_renderer::kRecords) {      // stream order: every launch that used them is over by then
-            HIP_TRY(hipMemsetAsync(r->records, 0, sizeof(unsigned long long) * 4 * drt_renderer::kRecords, r->stream));
+            HIP_TRY(hipMemsetAsync(r->records.ptr, 0, r->records.bytes(), r->stream));
             r->records_used = 0;
         }
         r->batch_first_record = r->records_used;
         for (uint32_t done = 0; done < n_frames; done += frames_per_launch) {
             fp.frame_first = r->frame_index + done;
             fp.n_frames = std::min(frames_per_launch, n_frames - done);
-            unsigned long long *const record = r->spans_used < drt_renderer::kMaxSpans ? r->records + 4 * (size_t)(r->batch_first_record + r->spans_used++) : nullptr;
+            unsigned long long *const record = r->spans_used < drt_renderer::kMaxSpans ? r->records.ptr + 4 * (size_t)(r->batch_first_record + r->spans_used++) : nullptr;
             if (record) r->records_used++;
             fp.span = record;
             unsigned int *const launch_status = record ? reinterpret_cast<unsigned int *>(record + 2) : nullptr;     // (beyond kMaxSpans launches per batch: no status word, the kernel still aborts cleanly)
             r->launches_last++;
             if (r->counters_used == drt_renderer::kCounters) {      // stream order: every launch that used them is over by then
-                HIP_TRY(hipMemsetAsync(r->tile_counter, 0, sizeof(unsigned int) * drt_renderer::kCounters * kQueueHeadBlockWords, r->stream));
+                HIP_TRY(hipMemsetAsync(r->tile_counter.ptr, 0, r->tile_counter.bytes(), r->stream));
                 r->counters_used = 0;
             }
-            unsigned int *const queue_head = r->tile_counter + (size_t)(r->counters_used++) * kQueueHeadBlockWords;
+            unsigned int *const queue_head = r->tile_counter.ptr + (size_t)(r->counters_used++) * kQueueHeadBlockWords;
             if (choice.family == Tracer::path_pool)
-                HIP_TRY(launch_path_pool(r->view, fp, r->bvh_depth, choice, r->pool_t_class, r->tune, r->pool_scratch, queue_head, r->samples, launch_status,
+                HIP_TRY(launch_path_pool(r->view, fp, r->bvh_depth, choice, r->pool_t_class, r->tune, r->pool_scratch, queue_head, r->samples.ptr, launch_status,
                                          r->num_cus, r->stream, &r->shape));
             else
-                HIP_TRY(launch_wave_queue(r->view, fp, r->bvh_depth, choice, r->tune, queue_head, r->samples, r->num_cus, r->stream, &r->shape, r->wq_cache));
+                HIP_TRY(launch_wave_queue(r->view, fp, r->bvh_depth, choice, r->tune, queue_head, r->samples.ptr, r->num_cus, r->stream, &r->shape, r->wq_cache));
         }
     }
     // the launches' records (execution span, status bits) travel to pinned host memory on the stream: drt_renderer_wait reads them
     // after the event, no second round trip to the device (a 1/8-shard step is 0.4 ms)
     if (r->spans_used > 0)
-        HIP_TRY(hipMemcpyAsync(r->records_host, r->records + 4 * (size_t)r->batch_first_record, sizeof(unsigned long long) * 4 * (size_t)r->spans_used, hipMemcpyDeviceToHost, r->stream));
+        HIP_TRY(hipMemcpyAsync(r->records_host.ptr, r->records.ptr + 4 * (size_t)r->batch_first_record, sizeof(unsigned long long) * 4 * (size_t)r->spans_used, hipMemcpyDeviceToHost, r->stream));
     HIP_TRY(hipEventRecord(r->ev_stop, r->stream));                    // Renderer.cu:105
     r->frame_index += n_frames;                                        // Renderer.cu:116
     r->pending = true;
@@ -938,7 +761,7 @@ int drt_renderer_wait(drt_renderer *r, float *delta_ms) {
     r->span_ms = 0.f;
     unsigned int status = 0;
     if (r->spans_used > 0) {
-        const unsigned long long *host = r->records_host;          // (copied on the stream before ev_stop)
+        const unsigned long long *host = r->records_host.ptr;          // (copied on the stream before ev_stop)
         double ticks = 0;
         for (int i = 0; i < r->spans_used; i++) {
             const unsigned long long start = ~host[4 * i], end = host[4 * i + 1];
@@ -969,40 +792,21 @@ static int ray_query_impl(drt_renderer *r, const drt_scene *scene, const drt_ray
     if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
     HIP_TRY(hipSetDevice(r->device));
     (void)hipGetLastError();                   // (see render_batch_impl: only this call's own errors count)
-    for (const void *p : { (const void *)rays, (const void *)out }) {
-        hipPointerAttribute_t at;
-        std::memset(&at, 0, sizeof at);
-        const hipError_t e = hipPointerGetAttributes(&at, p);
-        (void)hipGetLastError();
-        if (e != hipSuccess || !(at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged) || at.device != r->device)
-            return fail(DRT_ERR_INVALID, "rays and results must be device memory on the renderer's device");
-    }
-    int rc = upload_scene(r, scene);
-    if (rc != DRT_OK) return rc;
-    if (r->bvh_depth > 64) return fail(DRT_ERR_UNSUPPORTED, "BVH deeper than 64 levels (the reference's traversal stack, BVHTraversal.cuh:17)");
+    if (!on_renderer_device(r, rays) || !on_renderer_device(r, out))
+        return fail(DRT_ERR_INVALID, "rays and results must be device memory on the renderer's device");
+    if (int rc = upload_scene(r, scene)) return rc;
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : r->stream;
-    if (r->query_recorded && r->query_stream != s) HIP_TRY(hipStreamWaitEvent(s, r->ev_query, 0));
-    if (!r->rq_heads) HIP_TRY(hipMalloc((void **)&r->rq_heads, sizeof(unsigned int) * kRqHeadWords));
-    const size_t stack_bytes = ray_query_stack_bytes(r->num_cus, r->bvh_depth, occluded);
-    if (stack_bytes > r->rq_stack_bytes) {
-        if (r->query_recorded) HIP_TRY(hipEventSynchronize(r->ev_query));
-        if (r->rq_stack) { (void)hipFree(r->rq_stack); r->rq_stack = nullptr; r->rq_stack_bytes = 0; }
-        HIP_TRY(hipMalloc(&r->rq_stack, stack_bytes));
-        r->rq_stack_bytes = stack_bytes;
-    }
-    HIP_TRY(hipMemsetAsync(r->rq_heads, 0, sizeof(unsigned int) * kRqHeadWords, s));
+    if (int rc = query_order(r, s)) return rc;
+    if (int rc = traversal_scratch(r, s, occluded, true)) return rc;
     RayQueryArgs a;
     a.rays = rays; a.out = out; a.n = n;
     a.stack_levels = (uint32_t)std::max(1, r->bvh_depth);
     a.refill_min = (uint32_t)r->rq_refill_min;
-    a.heads = r->rq_heads;
-    a.stack_hbm = (uint32_t *)r->rq_stack;
+    a.heads = r->rq_heads.ptr;
+    a.stack_hbm = r->rq_stack.ptr;
     const char *name = nullptr;                // (kernel_info names the last render kernel: queries leave it alone)
     HIP_TRY(launch_ray_query(r->view, occluded, a, r->num_cus, s, &name));
-    HIP_TRY(hipEventRecord(r->ev_query, s));
-    r->query_stream = s;
-    r->query_recorded = true;
-    return DRT_OK;
+    return query_recorded(r, s);
 }
 
 int drt_renderer_trace_rays(drt_renderer *r, const drt_scene *scene, const drt_ray *rays, drt_hit *hits, uint32_t n, void *hip_stream) {
@@ -1013,73 +817,9 @@ int drt_renderer_occluded(drt_renderer *r, const drt_scene *scene, const drt_ray
     return ray_query_impl(r, scene, rays, occluded, n, hip_stream, true);
 }
 
-// ------------------------------------------------------------------ guide buffers and the a-trous denoiser (kernel_denoise.hip)
-static bool on_renderer_device(const drt_renderer *r, const void *p) {
-    hipPointerAttribute_t at;
-    std::memset(&at, 0, sizeof at);
-    const hipError_t e = hipPointerGetAttributes(&at, p);
-    (void)hipGetLastError();
-    return e == hipSuccess && (at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged) && at.device == r->device;
-}
-
-// The guide pass on stream `s`, ordered with the ray queries (it shares their HBM stack); the caller has checked the arguments.
-// width, height: the size of the image the guides are for, 0 = the renderer's frame (`guides` holds that many records).
-static int enqueue_guides(drt_renderer *r, const drt_camera *cam, const drt_scene *scene, uint32_t frame_index, void *guides, hipStream_t s,
-                          uint32_t width = 0, uint32_t height = 0) {
-    if (r->world > 1) return fail(DRT_ERR_UNSUPPORTED, "guides and the denoiser need the whole frame: a sharded renderer (world > 1) holds only its stripes");
-    int rc = upload_scene(r, scene);
-    if (rc != DRT_OK) return rc;
-    if (r->bvh_depth > 64) return fail(DRT_ERR_UNSUPPORTED, "BVH deeper than 64 levels (the reference's traversal stack, BVHTraversal.cuh:17)");
-    if (r->query_recorded && r->query_stream != s) HIP_TRY(hipStreamWaitEvent(s, r->ev_query, 0));
-    const size_t stack_bytes = ray_query_stack_bytes(r->num_cus, r->bvh_depth, false);
-    if (stack_bytes > r->rq_stack_bytes) {
-        if (r->query_recorded) HIP_TRY(hipEventSynchronize(r->ev_query));
-        if (r->rq_stack) { (void)hipFree(r->rq_stack); r->rq_stack = nullptr; r->rq_stack_bytes = 0; }
-        HIP_TRY(hipMalloc(&r->rq_stack, stack_bytes));
-        r->rq_stack_bytes = stack_bytes;
-    }
-    FrameParams fp;
-    std::memset(&fp, 0, sizeof fp);
-    fill_frame_params(r, cam, fp, width, height);
-    GuideArgs a;
-    a.out = guides;
-    a.frame = frame_index;
-    a.stack_levels = (uint32_t)std::max(1, r->bvh_depth);
-    a.stack_hbm = (uint32_t *)r->rq_stack;
-    HIP_TRY(launch_guides(r->view, fp, a, r->num_cus, s));
-    HIP_TRY(hipEventRecord(r->ev_query, s));
-    r->query_stream = s;
-    r->query_recorded = true;
-    return DRT_OK;
-}
-
-int drt_renderer_render_guides(drt_renderer *r, const drt_camera *cam, const drt_scene *scene, uint32_t frame_index,
-                               drt_guide *guides, void *hip_stream) {
-    if (!r || !cam || !scene || !guides) return fail(DRT_ERR_INVALID, "null argument");
-    if (frame_index == 0) return fail(DRT_ERR_INVALID, "frame indices start at 1");
-    if (r->width == 0 || r->height == 0) return fail(DRT_ERR_INVALID, "ResizeBuffer has not been called");
-    if (((uintptr_t)guides & 15u) != 0) return fail(DRT_ERR_INVALID, "guides must be 16-byte aligned");
-    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
-    HIP_TRY(hipSetDevice(r->device));
-    (void)hipGetLastError();                   // (see render_batch_impl: only this call's own errors count)
-    if (!on_renderer_device(r, guides)) return fail(DRT_ERR_INVALID, "guides must be device memory on the renderer's device");
-    return enqueue_guides(r, cam, scene, frame_index, guides, hip_stream ? (hipStream_t)hip_stream : r->stream);
-}
-
 // ------------------------------------------------------------------ camera rays and radiance queries (kernel_radiance.hip)
 // Both share the ray queries' claim heads and HBM stack: they wait for the last query / guide pass of this renderer on another stream,
 // and record the event the next one waits for.
-static int query_order(drt_renderer *r, hipStream_t s) {
-    if (r->query_recorded && r->query_stream != s) HIP_TRY(hipStreamWaitEvent(s, r->ev_query, 0));
-    return DRT_OK;
-}
-static int query_recorded(drt_renderer *r, hipStream_t s) {
-    HIP_TRY(hipEventRecord(r->ev_query, s));
-    r->query_stream = s;
-    r->query_recorded = true;
-    return DRT_OK;
-}
-
 int drt_renderer_camera_rays(drt_renderer *r, const drt_camera *cams, uint32_t n_cams, uint32_t width, uint32_t height,
                              uint32_t frame_index, drt_path_ray *rays, void *hip_stream) {
     if (!r || !cams || !rays) return fail(DRT_ERR_INVALID, "null argument");
@@ -1092,8 +832,7 @@ int drt_renderer_camera_rays(drt_renderer *r, const drt_camera *cams, uint32_t n
     (void)hipGetLastError();                   // (see render_batch_impl: only this call's own errors count)
     if (!on_renderer_device(r, rays)) return fail(DRT_ERR_INVALID, "rays must be device memory on the renderer's device");
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : r->stream;
-    int rc = query_order(r, s);
-    if (rc != DRT_OK) return rc;
+    if (int rc = query_order(r, s)) return rc;
     const size_t per_cam = (size_t)width * height;
     for (uint32_t c0 = 0; c0 < n_cams; c0 += kCamsPerLaunch) {     // (one launch up to kCamsPerLaunch cameras)
         CameraRaysArgs a;
@@ -1119,21 +858,10 @@ int drt_renderer_radiance(drt_renderer *r, const drt_scene *scene, const drt_pat
     (void)hipGetLastError();                   // (see render_batch_impl: only this call's own errors count)
     if (!on_renderer_device(r, rays) || !on_renderer_device(r, out))
         return fail(DRT_ERR_INVALID, "rays and results must be device memory on the renderer's device");
-    int rc = upload_scene(r, scene);
-    if (rc != DRT_OK) return rc;
-    if (r->bvh_depth > 64) return fail(DRT_ERR_UNSUPPORTED, "BVH deeper than 64 levels (the reference's traversal stack, BVHTraversal.cuh:17)");
+    if (int rc = upload_scene(r, scene)) return rc;
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : r->stream;
-    rc = query_order(r, s);
-    if (rc != DRT_OK) return rc;
-    if (!r->rq_heads) HIP_TRY(hipMalloc((void **)&r->rq_heads, sizeof(unsigned int) * kRqHeadWords));
-    const size_t stack_bytes = ray_query_stack_bytes(r->num_cus, r->bvh_depth, false);
-    if (stack_bytes > r->rq_stack_bytes) {
-        if (r->query_recorded) HIP_TRY(hipEventSynchronize(r->ev_query));
-        if (r->rq_stack) { (void)hipFree(r->rq_stack); r->rq_stack = nullptr; r->rq_stack_bytes = 0; }
-        HIP_TRY(hipMalloc(&r->rq_stack, stack_bytes));
-        r->rq_stack_bytes = stack_bytes;
-    }
-    HIP_TRY(hipMemsetAsync(r->rq_heads, 0, sizeof(unsigned int) * kRqHeadWords, s));
+    if (int rc = query_order(r, s)) return rc;
+    if (int rc = traversal_scratch(r, s, false, true)) return rc;
     FrameParams fp;
     std::memset(&fp, 0, sizeof fp);
     fill_frame_params(r, nullptr, fp);
@@ -1142,361 +870,10 @@ int drt_renderer_radiance(drt_renderer *r, const drt_scene *scene, const drt_pat
     a.stack_levels = (uint32_t)std::max(1, r->bvh_depth);
     a.refill_min = (uint32_t)r->rq_refill_min;
     a.accumulate = accumulate != 0;
-    a.heads = r->rq_heads;
-    a.stack_hbm = (uint32_t *)r->rq_stack;
+    a.heads = r->rq_heads.ptr;
+    a.stack_hbm = r->rq_stack.ptr;
     HIP_TRY(launch_radiance(r->view, fp, r->scene_has_alpha, a, r->num_cus, s));
     return query_recorded(r, s);
-}
-
-void drt_default_denoise_params(drt_denoise_params *out) {
-    if (!out) return;
-    out->iterations = 5;
-    out->sigma_color = 0.5f; out->sigma_normal = 0.1f; out->sigma_albedo = 0.1f;
-}
-
-int drt_renderer_denoise(drt_renderer *r, const drt_camera *cam, const drt_scene *scene, const drt_denoise_params *p, float *delta_ms) {
-    if (delta_ms) *delta_ms = 0.f;
-    if (!r || !cam || !scene || !p) return fail(DRT_ERR_INVALID, "null argument");
-    if (p->iterations < 0 || p->iterations > 10) return fail(DRT_ERR_INVALID, "iterations must lie in [0, 10]");
-    for (float sigma : { p->sigma_color, p->sigma_normal, p->sigma_albedo })
-        if (!std::isfinite(sigma) || !(sigma > 0.f)) return fail(DRT_ERR_INVALID, "every sigma must be finite and > 0");
-    if (r->width == 0 || r->height == 0) return fail(DRT_ERR_INVALID, "ResizeBuffer has not been called");
-    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
-    if (r->world > 1) return fail(DRT_ERR_UNSUPPORTED, "the denoiser needs the whole frame: a sharded renderer (world > 1) holds only its stripes");
-    HIP_TRY(hipSetDevice(r->device));
-    (void)hipGetLastError();
-    const size_t px = (size_t)r->width * r->height;
-    if (!r->dn_guides) {
-        HIP_TRY(hipMalloc(&r->dn_guides, px * sizeof(drt_guide)));
-        HIP_TRY(hipMalloc((void **)&r->dn_buf[0], px * sizeof(float4)));
-        HIP_TRY(hipMalloc((void **)&r->dn_buf[1], px * sizeof(float4)));
-    }
-    if (!r->ev_dn_start) HIP_TRY(hipEventCreate(&r->ev_dn_start));
-    if (!r->ev_dn_stop) HIP_TRY(hipEventCreate(&r->ev_dn_stop));
-    r->denoised = -1;
-    HIP_TRY(hipEventRecord(r->ev_dn_start, r->stream));
-    int rc = enqueue_guides(r, cam, scene, 1, r->dn_guides, r->stream);
-    if (rc != DRT_OK) return rc;
-    const float4 *in = reinterpret_cast<const float4 *>(r->cur_rgba());
-    int out = 0;
-    if (p->iterations == 0) {
-        HIP_TRY(hipMemcpyAsync(r->dn_buf[0], in, px * sizeof(float4), hipMemcpyDeviceToDevice, r->stream));
-    } else {
-        const float inv_sc2 = 1.0f / (p->sigma_color * p->sigma_color);
-        for (int i = 0; i < p->iterations; i++, out ^= 1) {
-            AtrousPass ps;
-            ps.in = i == 0 ? in : r->dn_buf[out ^ 1];
-            ps.out = r->dn_buf[out];
-            ps.guides = r->dn_guides;
-            ps.width = r->width; ps.height = r->height; ps.step = 1u << i;
-            ps.k_color = (float)(1 << i) * inv_sc2;
-            ps.k_normal = 1.0f / (p->sigma_normal * p->sigma_normal);
-            ps.k_albedo = 1.0f / (p->sigma_albedo * p->sigma_albedo);
-            HIP_TRY(launch_atrous(ps, r->filter_kernel, r->stream));
-        }
-        out ^= 1;
-    }
-    HIP_TRY(hipEventRecord(r->ev_dn_stop, r->stream));
-    HIP_TRY(hipEventSynchronize(r->ev_dn_stop));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, r->ev_dn_start, r->ev_dn_stop));
-    if (delta_ms) *delta_ms = ms;
-    r->denoised = out;
-    return DRT_OK;
-}
-
-// ------------------------------------------------------------------ temporal reprojection and the variance-guided filter (kernel_temporal.hip)
-void drt_default_temporal_params(drt_temporal_params *out) {
-    if (!out) return;
-    out->iterations = 5;
-    out->max_history = 32;
-    out->alpha_min = 0.f;
-    out->normal_cos_min = 0.9f;
-    out->sigma_luma = 4.f; out->sigma_normal = 0.1f; out->sigma_albedo = 0.1f;
-}
-
-// The camera as the next call's reprojection sees it: Camera.cu:82's basis and image plane, without jitter and defocus
-static PrevCamera pinhole_of(const drt_camera *cam, float width, float height) {
-    PrevCamera pc;
-    const float fov_factor = tanf((cam->vfov_rad / 2) / 2.0f);
-    pc.plane_h = 2.0f * fov_factor * cam->focus_dist;
-    pc.plane_w = pc.plane_h * (width / height);
-    pc.focus = cam->focus_dist;
-    const V3 f = normalize(V3{ cam->forward[0], cam->forward[1], cam->forward[2] });
-    const V3 right = normalize(cross(f, V3{ 0, 1, 0 })), up = cross(right, f);
-    auto put = [](float *dst, V3 v) { dst[0] = v.x; dst[1] = v.y; dst[2] = v.z; };
-    std::memcpy(pc.pos, cam->position, 12);
-    put(pc.forward, f); put(pc.right, right); put(pc.up, up);
-    return pc;
-}
-
-// The current records and the armed snapshot as the kernels of kernel_motion.hip read them (snapshot NULL = nothing armed: every
-// pixel static)
-static MotionGeometry motion_geometry(const drt_renderer *r) {
-    MotionGeometry geo;
-    geo.hot = reinterpret_cast<const float4 *>(r->d_hot.ptr);
-    geo.snapshot = nullptr;
-    if (r->mv_armed && r->mv_snap.count == r->d_hot.count && r->d_hot.count != 0) geo.snapshot = reinterpret_cast<const float4 *>(r->mv_snap.ptr);
-    return geo;
-}
-
-int drt_renderer_temporal_denoise(drt_renderer *r, const drt_camera *cam, const drt_scene *scene, const drt_temporal_params *p, float *delta_ms) {
-    if (delta_ms) *delta_ms = 0.f;
-    if (!r || !cam || !scene || !p) return fail(DRT_ERR_INVALID, "null argument");
-    if (p->iterations < 0 || p->iterations > 10) return fail(DRT_ERR_INVALID, "iterations must lie in [0, 10]");
-    if (p->max_history < 1) return fail(DRT_ERR_INVALID, "max_history must be at least 1");
-    if (!(p->alpha_min >= 0.f && p->alpha_min <= 1.f)) return fail(DRT_ERR_INVALID, "alpha_min must lie in [0, 1]");
-    if (!std::isfinite(p->normal_cos_min)) return fail(DRT_ERR_INVALID, "normal_cos_min must be finite");
-    for (float sigma : { p->sigma_luma, p->sigma_normal, p->sigma_albedo })
-        if (!std::isfinite(sigma) || !(sigma > 0.f)) return fail(DRT_ERR_INVALID, "every sigma must be finite and > 0");
-    if (r->width == 0 || r->height == 0) return fail(DRT_ERR_INVALID, "ResizeBuffer has not been called");
-    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
-    if (r->world > 1) return fail(DRT_ERR_UNSUPPORTED, "the temporal filter needs the whole frame: a sharded renderer (world > 1) holds only its stripes");
-    HIP_TRY(hipSetDevice(r->device));
-    (void)hipGetLastError();
-    const size_t px = (size_t)r->width * r->height;
-    if (!r->dn_guides) {
-        HIP_TRY(hipMalloc(&r->dn_guides, px * sizeof(drt_guide)));
-        HIP_TRY(hipMalloc((void **)&r->dn_buf[0], px * sizeof(float4)));
-        HIP_TRY(hipMalloc((void **)&r->dn_buf[1], px * sizeof(float4)));
-    }
-    if (!r->tp_hist[0][0]) {
-        r->tp_cur = -1;
-        for (auto &half : r->tp_hist)
-            for (float4 *&b : half) HIP_TRY(hipMalloc((void **)&b, px * sizeof(float4)));
-    }
-    if (!r->ev_dn_start) HIP_TRY(hipEventCreate(&r->ev_dn_start));
-    if (!r->ev_dn_stop) HIP_TRY(hipEventCreate(&r->ev_dn_stop));
-    r->denoised = -1;
-    HIP_TRY(hipEventRecord(r->ev_dn_start, r->stream));
-    int rc = enqueue_guides(r, cam, scene, 1, r->dn_guides, r->stream);
-    if (rc != DRT_OK) return rc;
-
-    const int half = r->tp_cur < 0 ? 0 : r->tp_cur ^ 1;
-    const CamConst cc = camera_const(cam, (float)r->width, (float)r->height);
-    ReprojectArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.frame = reinterpret_cast<const float4 *>(r->cur_rgba());
-    a.guides = r->dn_guides;
-    a.cur = TemporalHistory{ r->tp_hist[half][0], r->tp_hist[half][1], r->tp_hist[half][2] };
-    a.prev = TemporalHistory{ r->tp_hist[half ^ 1][0], r->tp_hist[half ^ 1][1], r->tp_hist[half ^ 1][2] };
-    a.width = r->width; a.height = r->height;
-    a.has_prev = r->tp_cur >= 0;
-    std::memcpy(a.cam_pos, cc.cam_pos, 12); std::memcpy(a.fwd_focus, cc.fwd_focus, 12);
-    std::memcpy(a.horizontal, cc.horizontal, 12); std::memcpy(a.vertical, cc.vertical, 12);
-    if (a.has_prev) a.pc = r->tp_cam;
-    a.max_history = (float)p->max_history; a.alpha_min = p->alpha_min; a.normal_cos_min = p->normal_cos_min;
-    r->tp_cur = -1;                            // (a failure below leaves no history)
-    if (r->mv_armed) {                         // geometry moved since the last call: P' and n' of the moved rule (kernel_motion.hip)
-        HIP_TRY(launch_motion_reproject(a, motion_geometry(r), r->stream));
-        r->mv_armed = false;                   // the geometry as it is now is the previous geometry of the next call
-    } else {
-        HIP_TRY(launch_temporal_reproject(a, r->num_cus, r->stream));
-    }
-
-    int out = 0;
-    if (p->iterations == 0) {
-        HIP_TRY(launch_temporal_copy(a.cur.color, r->dn_buf[0], (uint32_t)px, r->stream));
-    } else {
-        for (int i = 0; i < p->iterations; i++, out ^= 1) {
-            AtrousVarPass ps;
-            ps.in = i == 0 ? a.cur.color : r->dn_buf[out ^ 1];
-            ps.var_src = i == 0 ? a.cur.moments : nullptr;
-            ps.out = r->dn_buf[out];
-            ps.guides = r->dn_guides;
-            ps.width = r->width; ps.height = r->height; ps.step = 1u << i;
-            ps.last = i == p->iterations - 1;
-            ps.sigma_luma = p->sigma_luma;
-            ps.k_normal = 1.0f / (p->sigma_normal * p->sigma_normal);
-            ps.k_albedo = 1.0f / (p->sigma_albedo * p->sigma_albedo);
-            HIP_TRY(launch_atrous_var(ps, r->filter_kernel, r->stream));
-        }
-        out ^= 1;
-    }
-    HIP_TRY(hipEventRecord(r->ev_dn_stop, r->stream));
-    HIP_TRY(hipEventSynchronize(r->ev_dn_stop));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, r->ev_dn_start, r->ev_dn_stop));
-    if (delta_ms) *delta_ms = ms;
-    r->tp_cam = pinhole_of(cam, (float)r->width, (float)r->height);
-    r->tp_cur = half;
-    r->denoised = out;
-    return DRT_OK;
-}
-
-int drt_renderer_temporal_reset(drt_renderer *r) {
-    if (!r) return fail(DRT_ERR_INVALID, "null argument");
-    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
-    if (r->tp_hist[0][0]) {
-        HIP_TRY(hipSetDevice(r->device));
-        HIP_TRY(hipStreamSynchronize(r->stream));
-    }
-    r->free_temporal();
-    return DRT_OK;
-}
-
-void *drt_renderer_device_temporal(drt_renderer *r, int32_t which) {
-    return r && r->tp_cur >= 0 && (which == 0 || which == 1) ? (void *)r->tp_hist[r->tp_cur][which == 0 ? 0 : 2] : nullptr;
-}
-
-// ------------------------------------------------------------------ motion tracking and motion vectors (kernel_motion.hip)
-int drt_renderer_track_motion(drt_renderer *r, int32_t enable) {
-    if (!r) return fail(DRT_ERR_INVALID, "null argument");
-    r->mv_track = enable != 0;
-    if (!r->mv_track) {
-        if (r->mv_snap.ptr) {
-            HIP_TRY(hipSetDevice(r->device));
-            HIP_TRY(hipDeviceSynchronize());     // (a motion-vector pass on a caller's stream may still read them)
-        }
-        r->mv_snap.release();
-        r->mv_armed = false;
-    }
-    return DRT_OK;
-}
-
-int drt_renderer_motion_advance(drt_renderer *r) {
-    if (!r) return fail(DRT_ERR_INVALID, "null argument");
-    r->mv_armed = false;
-    return DRT_OK;
-}
-
-int drt_renderer_motion_vectors(drt_renderer *r, const drt_camera *cam, const drt_camera *prev_cam, const drt_scene *scene, float *out,
-                                void *hip_stream) {
-    if (!r || !cam || !scene || !out) return fail(DRT_ERR_INVALID, "null argument");
-    if (r->width == 0 || r->height == 0) return fail(DRT_ERR_INVALID, "ResizeBuffer has not been called");
-    if (((uintptr_t)out & 15u) != 0) return fail(DRT_ERR_INVALID, "out must be 16-byte aligned");
-    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
-    if (!prev_cam && r->tp_cur < 0) return fail(DRT_ERR_INVALID, "no previous camera: pass prev_cam or call drt_renderer_temporal_denoise first");
-    HIP_TRY(hipSetDevice(r->device));
-    (void)hipGetLastError();
-    if (!on_renderer_device(r, out)) return fail(DRT_ERR_INVALID, "out must be device memory on the renderer's device");
-    if (r->world > 1) return fail(DRT_ERR_UNSUPPORTED, "motion vectors need the whole frame: a sharded renderer (world > 1) holds only its stripes");
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : r->stream;
-    int rc = upload_scene(r, scene);             // (nothing is allocated for a scene the guide pass refuses)
-    if (rc != DRT_OK) return rc;
-    if (r->bvh_depth > 64) return fail(DRT_ERR_UNSUPPORTED, "BVH deeper than 64 levels (the reference's traversal stack, BVHTraversal.cuh:17)");
-    if (!r->mv_guides) HIP_TRY(hipMalloc(&r->mv_guides, (size_t)r->width * r->height * sizeof(drt_guide)));
-    rc = enqueue_guides(r, cam, scene, 1, r->mv_guides, s);
-    if (rc != DRT_OK) return rc;
-    const CamConst cc = camera_const(cam, (float)r->width, (float)r->height);
-    ReprojectArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.guides = r->mv_guides;
-    a.width = r->width; a.height = r->height;
-    a.has_prev = 1;
-    std::memcpy(a.cam_pos, cc.cam_pos, 12); std::memcpy(a.fwd_focus, cc.fwd_focus, 12);
-    std::memcpy(a.horizontal, cc.horizontal, 12); std::memcpy(a.vertical, cc.vertical, 12);
-    a.pc = prev_cam ? pinhole_of(prev_cam, (float)r->width, (float)r->height) : r->tp_cam;
-    HIP_TRY(launch_motion_vectors(a, motion_geometry(r), reinterpret_cast<float4 *>(out), s));
-    return query_recorded(r, s);                 // (the next guide pass, on whatever stream, overwrites mv_guides only after this one)
-}
-
-// ------------------------------------------------------------------ guide-driven upscaling (kernel_upscale.hip)
-void drt_default_upscale_params(drt_upscale_params *out) {
-    if (!out) return;
-    out->source = 0;
-    out->demodulate = 0;                         // (include/drt.h: demodulation lost against the oracle on both test scenes)
-    out->sigma_normal = 0.1f; out->sigma_depth = 0.05f; out->sigma_albedo = 0.1f;
-    out->albedo_floor = 0.01f;
-}
-
-// What both entry points check of the parameters and the two sizes (nullptr = fine)
-static const char *upscale_arguments(const drt_upscale_params *p, uint32_t W, uint32_t H, uint32_t Wo, uint32_t Ho) {
-    if (p->source < 0 || p->source > 1) return "source must be 0 (the framebuffer) or 1 (the denoised target)";
-    if (p->demodulate < 0 || p->demodulate > 1) return "demodulate must be 0 or 1";
-    for (float v : { p->sigma_normal, p->sigma_depth, p->sigma_albedo, p->albedo_floor })
-        if (!std::isfinite(v) || !(v > 0.f)) return "every sigma and the albedo floor must be finite and > 0";
-    if (W == 0 || H == 0) return "no frame size";
-    if (Wo < W || Ho < H) return "the output must be at least as large as the frame in both axes";
-    if ((uint64_t)Wo * Ho > (1ull << 31)) return "output too large (at most 2^31 pixels)";
-    return nullptr;
-}
-
-static UpscaleArgs upscale_args(const drt_upscale_params *p, uint32_t W, uint32_t H, uint32_t Wo, uint32_t Ho) {
-    UpscaleArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.width = W; a.height = H; a.out_width = Wo; a.out_height = Ho;
-    a.demodulate = p->demodulate;
-    a.k_normal = 1.0f / (p->sigma_normal * p->sigma_normal);
-    a.k_albedo = 1.0f / (p->sigma_albedo * p->sigma_albedo);
-    a.sigma_depth = p->sigma_depth;
-    a.albedo_floor = p->albedo_floor;
-    return a;
-}
-
-int drt_renderer_upscale(drt_renderer *r, const drt_camera *cam, const drt_scene *scene, uint32_t out_width, uint32_t out_height,
-                         const drt_upscale_params *p, float *delta_ms) {
-    if (delta_ms) *delta_ms = 0.f;
-    if (!r || !cam || !scene || !p) return fail(DRT_ERR_INVALID, "null argument");
-    if (r->width == 0 || r->height == 0) return fail(DRT_ERR_INVALID, "ResizeBuffer has not been called");
-    if (const char *why = upscale_arguments(p, r->width, r->height, out_width, out_height)) return fail(DRT_ERR_INVALID, why);
-    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
-    if (r->world > 1) return fail(DRT_ERR_UNSUPPORTED, "upscaling needs the whole frame: a sharded renderer (world > 1) holds only its stripes");
-    if (p->source == 1 && r->denoised < 0) return fail(DRT_ERR_INVALID, "source 1 is the denoised target: drt_renderer_denoise or drt_renderer_temporal_denoise first");
-    HIP_TRY(hipSetDevice(r->device));
-    (void)hipGetLastError();
-    const size_t px = (size_t)r->width * r->height, out_px = (size_t)out_width * out_height;
-    if (r->us_width != out_width || r->us_height != out_height) {
-        r->free_upscale();
-        HIP_TRY(hipMalloc(&r->us_guides, (px + out_px) * sizeof(drt_guide)));
-        HIP_TRY(hipMalloc((void **)&r->us_out, out_px * sizeof(float4)));
-    }
-    if (!r->ev_dn_start) HIP_TRY(hipEventCreate(&r->ev_dn_start));
-    if (!r->ev_dn_stop) HIP_TRY(hipEventCreate(&r->ev_dn_stop));
-    r->us_width = r->us_height = 0;              // (a failure below leaves no result)
-    drt_guide *lo = static_cast<drt_guide *>(r->us_guides), *hi = lo + px;
-    HIP_TRY(hipEventRecord(r->ev_dn_start, r->stream));
-    int rc = enqueue_guides(r, cam, scene, 1, lo, r->stream);
-    if (rc == DRT_OK) rc = enqueue_guides(r, cam, scene, 1, hi, r->stream, out_width, out_height);
-    if (rc != DRT_OK) { r->free_upscale(); return rc; }
-    UpscaleArgs a = upscale_args(p, r->width, r->height, out_width, out_height);
-    a.color = p->source == 1 ? r->dn_buf[r->denoised] : reinterpret_cast<const float4 *>(r->cur_rgba());
-    a.guides_lo = lo; a.guides_hi = hi;
-    a.out = r->us_out;
-    HIP_TRY(launch_upscale(a, r->stream));
-    HIP_TRY(hipEventRecord(r->ev_dn_stop, r->stream));
-    HIP_TRY(hipEventSynchronize(r->ev_dn_stop));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, r->ev_dn_start, r->ev_dn_stop));
-    if (delta_ms) *delta_ms = ms;
-    r->us_width = out_width; r->us_height = out_height;
-    return DRT_OK;
-}
-
-void *drt_renderer_device_upscaled(drt_renderer *r) { return r && r->us_width ? (void *)r->us_out : nullptr; }
-
-int drt_renderer_read_upscaled_rgba32f(drt_renderer *r, float *dst, size_t dst_floats) {
-    if (!r || !dst) return fail(DRT_ERR_INVALID, "null argument");
-    if (r->us_width == 0) return fail(DRT_ERR_INVALID, "no upscaled image yet: drt_renderer_upscale first");
-    const size_t need = (size_t)r->us_width * r->us_height * 4;
-    if (dst_floats < need) return fail(DRT_ERR_INVALID, "destination too small");
-    HIP_TRY(hipSetDevice(r->device));
-    HIP_TRY(hipStreamSynchronize(r->stream));
-    HIP_TRY(hipMemcpy(dst, r->us_out, need * sizeof(float), hipMemcpyDeviceToHost));
-    return DRT_OK;
-}
-
-int drt_debug_upscale(int32_t device, const float *colour, const drt_guide *guides_lo, const drt_guide *guides_hi, uint32_t width, uint32_t height,
-                      uint32_t out_width, uint32_t out_height, const drt_upscale_params *p, float *out) {
-    if (!colour || !guides_lo || !guides_hi || !p || !out) return fail(DRT_ERR_INVALID, "null argument");
-    if (const char *why = upscale_arguments(p, width, height, out_width, out_height)) return fail(DRT_ERR_INVALID, why);
-    HIP_TRY(hipSetDevice(device));
-    const size_t px = (size_t)width * height, out_px = (size_t)out_width * out_height;
-    const size_t off_lo = px * sizeof(float4), off_hi = off_lo + px * sizeof(drt_guide), off_out = off_hi + out_px * sizeof(drt_guide);
-    char *d = nullptr;                           // colour, guides_lo, guides_hi, out: every part a multiple of 16 bytes
-    HIP_TRY(hipMalloc((void **)&d, off_out + out_px * sizeof(float4)));
-    hipError_t e = hipMemcpy(d, colour, off_lo, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d + off_lo, guides_lo, px * sizeof(drt_guide), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d + off_hi, guides_hi, out_px * sizeof(drt_guide), hipMemcpyHostToDevice);
-    UpscaleArgs a = upscale_args(p, width, height, out_width, out_height);
-    a.color = reinterpret_cast<const float4 *>(d);
-    a.guides_lo = d + off_lo; a.guides_hi = d + off_hi;
-    a.out = reinterpret_cast<float4 *>(d + off_out);
-    if (e == hipSuccess) e = launch_upscale(a, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(out, d + off_out, out_px * sizeof(float4), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(DRT_ERR_DEVICE, hipGetErrorString(e));
-    return DRT_OK;
 }
 
 // ------------------------------------------------------------------ refit of the device copy (kernel_refit.hip)
@@ -1578,9 +955,7 @@ int drt_renderer_refit(drt_renderer *r, const drt_scene *scene, const float *pos
     for (const float *p : { positions, normals })
         if (p && !device_range_on_renderer(r, p, bytes))
             return fail(DRT_ERR_INVALID, "positions and normals must be float[n][3][3] in device memory on the renderer's device");
-    int rc = upload_scene(r, scene);
-    if (rc != DRT_OK) return rc;
-    if (r->bvh_depth > 64) return fail(DRT_ERR_UNSUPPORTED, "BVH deeper than 64 levels (the reference's traversal stack, BVHTraversal.cuh:17)");
+    if (int rc = upload_scene(r, scene)) return rc;
     if (!r->rf_built) {
         RefitPlan plan;
         try { plan = refit_plan(scene->host); } catch (...) { return from_exception(); }
@@ -1594,12 +969,12 @@ int drt_renderer_refit(drt_renderer *r, const drt_scene *scene, const float *pos
         r->rf_heights = plan.height_begin;
         r->rf_built = true;
     }
-    if (!r->ev_rf_start) HIP_TRY(hipEventCreate(&r->ev_rf_start));
-    if (!r->ev_rf_stop) HIP_TRY(hipEventCreate(&r->ev_rf_stop));
-    if (!r->ev_rf_dep) HIP_TRY(hipEventCreateWithFlags(&r->ev_rf_dep, hipEventDisableTiming));
+    HIP_TRY(r->ev_rf_start.create());
+    HIP_TRY(r->ev_rf_stop.create());
+    HIP_TRY(r->ev_rf_dep.create(hipEventDisableTiming));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : r->stream;
     // nothing is written before the renderer's queries / guide passes in flight and the work on its stream are done
-    if (r->query_recorded && r->query_stream != s) HIP_TRY(hipStreamWaitEvent(s, r->ev_query, 0));
+    if (int rc = query_order(r, s)) return rc;
     if (s != r->stream) {
         HIP_TRY(hipEventRecord(r->ev_rf_dep, r->stream));
         HIP_TRY(hipStreamWaitEvent(s, r->ev_rf_dep, 0));
@@ -1664,21 +1039,8 @@ int drt_debug_read_device_scene(drt_renderer *r, void *inner, size_t inner_bytes
     return DRT_OK;
 }
 
-void *drt_renderer_device_denoised(drt_renderer *r) { return r && r->denoised >= 0 ? (void *)r->dn_buf[r->denoised] : nullptr; }
-
 int drt_renderer_render(drt_renderer *r, const drt_camera *cam, const drt_scene *scene, float *delta_ms) {
     return drt_renderer_render_batch(r, cam, scene, 1, delta_ms);
-}
-
-static int read_back(drt_renderer *r, const float *src, int comps, float *dst, size_t dst_floats) {
-    if (!r || !dst) return fail(DRT_ERR_INVALID, "null argument");
-    size_t need = (size_t)r->width * r->local_rows * (size_t)comps;
-    if (dst_floats < need) return fail(DRT_ERR_INVALID, "destination too small");
-    if (need == 0) return DRT_OK;
-    HIP_TRY(hipSetDevice(r->device));
-    HIP_TRY(hipStreamSynchronize(r->stream));
-    HIP_TRY(hipMemcpy(dst, src, need * sizeof(float), hipMemcpyDeviceToHost));
-    return DRT_OK;
 }
 
 int drt_renderer_read_rgba32f(drt_renderer *r, float *dst, size_t dst_floats) {
@@ -1687,29 +1049,15 @@ int drt_renderer_read_rgba32f(drt_renderer *r, float *dst, size_t dst_floats) {
 int drt_renderer_read_accum(drt_renderer *r, float *dst, size_t dst_floats) {
     return read_back(r, r ? r->cur_accum() : nullptr, 3, dst, dst_floats);
 }
-int drt_renderer_read_denoised_rgba32f(drt_renderer *r, float *dst, size_t dst_floats) {
-    if (r && r->denoised < 0) return fail(DRT_ERR_INVALID, "no denoised image yet: drt_renderer_denoise first");
-    return read_back(r, r ? (const float *)r->dn_buf[r->denoised] : nullptr, 4, dst, dst_floats);
-}
-
-int drt_renderer_read_temporal(drt_renderer *r, int32_t which, float *dst, size_t dst_floats) {
-    if (!r || !dst) return fail(DRT_ERR_INVALID, "null argument");
-    if (which < 0 || which > 1) return fail(DRT_ERR_INVALID, "which must be 0 (colour, N) or 1 (moments, variance, weight)");
-    if (r->tp_cur < 0) return fail(DRT_ERR_INVALID, "no temporal history yet: drt_renderer_temporal_denoise first");
-    return read_back(r, (const float *)r->tp_hist[r->tp_cur][which == 0 ? 0 : 2], 4, dst, dst_floats);
-}
 
 static int debug_check_exact(int32_t device, int which, uint64_t *mismatches, uint64_t *fast_path_count) {
     if (!mismatches || !fast_path_count) return fail(DRT_ERR_INVALID, "null argument");
     HIP_TRY(hipSetDevice(device));
-    unsigned long long *d = nullptr;
-    HIP_TRY(hipMalloc((void **)&d, 2 * sizeof(unsigned long long)));
-    hipError_t e = hipMemset(d, 0, 2 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = launch_check_rcp(which, 0u, 1ull << 32, d, nullptr);
+    DeviceArray<unsigned long long> d;
+    HIP_TRY(d.alloc_zeroed(2));
+    HIP_TRY(launch_check_rcp(which, 0u, 1ull << 32, d.ptr, nullptr));
     unsigned long long h[2] = { 0, 0 };
-    if (e == hipSuccess) e = hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(DRT_ERR_DEVICE, hipGetErrorString(e));
+    HIP_TRY(hipMemcpy(h, d.ptr, sizeof h, hipMemcpyDeviceToHost));
     *mismatches = h[0]; *fast_path_count = h[1];
     return DRT_OK;
 }
@@ -1746,20 +1094,18 @@ int drt_debug_kat(int32_t device, int32_t which, const void *in, size_t in_bytes
     if (which == 4) {
         if (!cam || width == 0 || height == 0) return fail(DRT_ERR_INVALID, "camera KAT needs a camera and a frame size");
         drt_renderer tmp;
+        tmp.device = device;
         drt_default_settings(&tmp.settings);
         tmp.width = width; tmp.height = height;
         fill_frame_params(&tmp, cam, fp);
     }
-    void *d_in = nullptr, *d_out = nullptr;
-    HIP_TRY(hipMalloc(&d_in, std::max<size_t>(in_bytes, 16)));
-    hipError_t e = hipMalloc(&d_out, std::max<size_t>(out_bytes, 16));
-    if (e == hipSuccess) e = hipMemcpy(d_in, in, in_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(d_out, 0, out_bytes);
-    if (e == hipSuccess) e = launch_kat(which, d_in, d_out, n, fp, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost);
-    (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    if (e != hipSuccess) return fail(DRT_ERR_DEVICE, hipGetErrorString(e));
+    DeviceArray<uint8_t> d_in, d_out;
+    HIP_TRY(d_in.alloc(std::max<size_t>(in_bytes, 16)));
+    HIP_TRY(d_out.alloc(std::max<size_t>(out_bytes, 16)));
+    HIP_TRY(hipMemcpy(d_in.ptr, in, in_bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(d_out.ptr, 0, out_bytes));
+    HIP_TRY(launch_kat(which, d_in.ptr, d_out.ptr, n, fp, nullptr));
+    HIP_TRY(hipMemcpy(out, d_out.ptr, out_bytes, hipMemcpyDeviceToHost));
     return DRT_OK;
 }
 
@@ -1797,15 +1143,11 @@ int drt_debug_pool_stats(drt_renderer *r, uint64_t out[40], int32_t reset) {
 int drt_debug_hash_cycles(int32_t device, uint32_t max_len, uint32_t *pairs_out, uint32_t cap_pairs, uint32_t *found) {
     if (!pairs_out || !found || cap_pairs == 0) return fail(DRT_ERR_INVALID, "bad argument");
     HIP_TRY(hipSetDevice(device));
-    uint32_t *d = nullptr;
-    const size_t bytes = (1 + 2 * (size_t)cap_pairs) * sizeof(uint32_t);
-    HIP_TRY(hipMalloc((void **)&d, bytes));
-    hipError_t e = hipMemset(d, 0, bytes);
-    if (e == hipSuccess) e = launch_hash_cycles(max_len, d, cap_pairs, nullptr);
-    std::vector<uint32_t> h(1 + 2 * (size_t)cap_pairs);
-    if (e == hipSuccess) e = hipMemcpy(h.data(), d, bytes, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(DRT_ERR_DEVICE, hipGetErrorString(e));
+    DeviceArray<uint32_t> d;
+    HIP_TRY(d.alloc_zeroed(1 + 2 * (size_t)cap_pairs));
+    HIP_TRY(launch_hash_cycles(max_len, d.ptr, cap_pairs, nullptr));
+    std::vector<uint32_t> h(d.count);
+    HIP_TRY(hipMemcpy(h.data(), d.ptr, d.bytes(), hipMemcpyDeviceToHost));
     *found = h[0];
     std::memcpy(pairs_out, h.data() + 1, 2 * (size_t)std::min<uint32_t>(h[0], cap_pairs) * sizeof(uint32_t));
     return DRT_OK;

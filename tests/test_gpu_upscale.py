@@ -204,6 +204,35 @@ def second_temporal(sc, cam):
     return r.TemporalDenoise(cam, sc)
 
 
+def test_resize_drops_every_stage_target():
+    """ResizeBuffer drops the denoised target, the temporal history and the upscaled image, and the stages that run afterwards give,
+    bit for bit, what a renderer gives that only ever had the new size: the buffers are allocated again at that size, the upscaler's
+    source 1 reads the target the temporal filter just wrote, and no stage keeps state (history, armed motion) from the old size."""
+    sc, pos, fwd, depth = scene("cornell_box")
+    cam = camera(pos, fwd)
+
+    def stages(r, Wo, Ho):
+        r.RenderBatch(cam, sc, 1)
+        r.Denoise(cam, sc)
+        r.TemporalDenoise(cam, sc)
+        r.motionVectors(cam, sc, prev_cam=cam)
+        r.Upscale(cam, sc, Wo, Ho, source=1)
+        return (r.GetDenoisedImage(), *r.GetTemporalHistory(), r.GetUpscaledImage())
+
+    a = renderer(32, 16, depth)
+    stages(a, 64, 32)
+    assert a.DeviceDenoisedTarget() and a.DeviceTemporalHistory(0) and a.DeviceUpscaledTarget()
+    a.ResizeBuffer(40, 16)
+    assert a.DeviceDenoisedTarget() is None and a.DeviceTemporalHistory(0) is None and a.DeviceUpscaledTarget() is None
+    for read in (a.GetDenoisedImage, a.GetTemporalHistory, a.GetUpscaledImage):
+        assert _code(read) == drt.ERR_INVALID
+    after = stages(a, 80, 32)
+    fresh = stages(renderer(40, 16, depth), 80, 32)
+    assert after[0].shape == (16, 40, 4) and after[-1].shape == (32, 80, 4) and len(after) == len(fresh) == 7
+    for x, y in zip(after, fresh):
+        assert x.shape == y.shape and (u32(x) == u32(y)).all()
+
+
 # MSE(upscaled) / MSE(plain bilinear of the same 80 x 60, 64-spp image) against 512 spp at 160 x 120, measured with the restatement on
 # the CPU oracle (which shares the renderer's image bit for bit; only expf differs): the bound is that ratio plus 25 %
 ORACLE_RATIO = {"cornell_box": 0.3385, "uv_texture_test": 0.2702}
