@@ -193,6 +193,29 @@ class UpscaleParams(C.Structure):
             setattr(self, k, v)
 
 
+class AdaptiveParams(C.Structure):
+    """include/drt.h drt_adaptive_params: the samples of one call (0 = 4 per pixel), the per-call bounds of a pixel's count, the
+    relative standard error below which a pixel is converged (0 = off) and the luminance floor (defaults 0, 1, 64, 0, 0.01)."""
+    _fields_ = [("budget", C.c_uint32), ("min_spp", C.c_uint32), ("max_spp", C.c_uint32), ("target_error", C.c_float),
+                ("luma_floor", C.c_float)]
+
+    def __init__(self, **kw):
+        super().__init__()
+        _lib.drt_default_adaptive_params(C.byref(self))
+        for k, v in kw.items():
+            if k not in dict(self._fields_):
+                raise TypeError("AdaptiveParams has no field %r" % k)
+            setattr(self, k, v)
+
+
+class AdaptiveInfo(C.Structure):
+    """include/drt.h drt_adaptive_info: what one RenderAdaptive call did."""
+    _fields_ = [("samples", C.c_uint32), ("active_pixels", C.c_uint32), ("max_count", C.c_uint32), ("ms", C.c_float)]
+
+    def __repr__(self):
+        return "AdaptiveInfo(samples=%d, active_pixels=%d, max_count=%d, ms=%.3f)" % (self.samples, self.active_pixels, self.max_count, self.ms)
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("samples", "rays", "node_visits", "inner_visits", "tri_tests",
                                            "hits_textured", "hits_flat", "shadow_rays", "inner_visits_shadow",
@@ -320,6 +343,12 @@ _sig("drt_renderer_upscale", C.c_int, _P, C.POINTER(_CameraPOD), _P, C.c_uint32,
 _sig("drt_renderer_read_upscaled_rgba32f", C.c_int, _P, _P, C.c_size_t)
 _sig("drt_renderer_device_upscaled", _P, _P)
 _sig("drt_debug_upscale", C.c_int, C.c_int32, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(UpscaleParams), _P)
+_sig("drt_default_adaptive_params", None, C.POINTER(AdaptiveParams))
+_sig("drt_renderer_render_adaptive", C.c_int, _P, C.POINTER(_CameraPOD), _P, C.POINTER(AdaptiveParams), C.POINTER(AdaptiveInfo))
+_sig("drt_renderer_adaptive_reset", C.c_int, _P)
+_sig("drt_renderer_read_adaptive", C.c_int, _P, C.c_int32, _P, C.c_size_t)
+_sig("drt_renderer_device_adaptive", _P, _P, C.c_int32)
+_sig("drt_debug_adaptive_plan", C.c_int, C.c_int32, _P, C.c_uint32, C.POINTER(AdaptiveParams), C.c_int32, _P, _P, C.POINTER(C.c_uint64))
 _sig("drt_scene_get_triangle_order", C.c_int, _P, _P, C.c_int32)
 _sig("drt_scene_refit", C.c_int, _P, _P, _P)
 _sig("drt_renderer_refit", C.c_int, _P, _P, _P, _P, C.POINTER(C.c_float), _P)
@@ -571,6 +600,7 @@ FLT_MAX = float(np.finfo(np.float32).max)
 RayHits = collections.namedtuple("RayHits", "t prim u v")     # closest-hit query results (Renderer.traceRays)
 TemporalHistory = collections.namedtuple("TemporalHistory", "color length moments variance weight")  # Renderer.GetTemporalHistory
 Guides = collections.namedtuple("Guides", "albedo normal t prim")  # first-hit guide buffers (Renderer.renderGuides)
+AdaptiveState = collections.namedtuple("AdaptiveState", "sum count m1 m2 last_q last_count")  # Renderer.GetAdaptiveState
 
 
 def _ray_batch(torch, dev, origins, directions, tmin, tmax):
@@ -650,6 +680,7 @@ class Renderer:
         self.m_LastTemporalMs = 0.0              # device time of the last TemporalDenoise (guides + reprojection + filter)
         self.m_LastUpscaleMs = 0.0               # device time of the last Upscale (both guide passes + the kernel)
         self._upscaled_size = (0, 0)             # (width, height) of the last Upscale
+        self.m_LastAdaptiveMs = 0.0              # device time of the last RenderAdaptive (plan + ray lists + tracing + fold)
 
     def _ray_query(self, scene, origins, directions, tmin, tmax, occluded):
         import torch                             # (only here: importing the package does not import torch)
@@ -904,6 +935,39 @@ class Renderer:
         """Device address of the last Upscale result (float4 [Ho * Wo]), None before the first Upscale."""
         return _lib.drt_renderer_device_upscaled(self._h)
 
+    def RenderAdaptive(self, cam, scene, spp=4.0, **params):
+        """One adaptive call (drt_renderer_render_adaptive; `params` = AdaptiveParams fields): int(spp * W * H) samples -- or
+        `budget` if given -- go where the per-pixel state says the noise is; the framebuffer then shows sum / n of every pixel.
+        The first call after a reset or resize is uniform.  Returns the AdaptiveInfo (samples, active_pixels, max_count, ms)."""
+        self._push_settings()
+        if "budget" not in params:
+            params["budget"] = int(spp * self.getBufferWidth() * self.getBufferHeight())
+        p = AdaptiveParams(**params)
+        info = AdaptiveInfo()
+        pod = cam._pod()
+        _check(_lib.drt_renderer_render_adaptive(self._h, C.byref(pod), scene._h, C.byref(p), C.byref(info)))
+        self.m_LastAdaptiveMs = info.ms
+        return info
+
+    def GetAdaptiveState(self):
+        """The per-pixel state of adaptive sampling (drt_renderer_read_adaptive): AdaptiveState(sum [H, W, 3] float32, count [H, W]
+        uint32, m1 [H, W], m2 [H, W] float32, last_q [H, W], last_count [H, W] uint32 -- the last call's weights and counts)."""
+        H, W = self.getBufferHeight(), self.getBufferWidth()
+        a, b = np.zeros((H, W, 4), np.float32), np.zeros((H, W, 4), np.float32)
+        _check(_lib.drt_renderer_read_adaptive(self._h, 0, a.ctypes.data, a.nbytes))
+        _check(_lib.drt_renderer_read_adaptive(self._h, 1, b.ctypes.data, b.nbytes))
+        au, bu = a.view(np.uint32), b.view(np.uint32)
+        return AdaptiveState(a[..., :3].copy(), au[..., 3].copy(), b[..., 0].copy(), b[..., 1].copy(), bu[..., 2].copy(), bu[..., 3].copy())
+
+    def DeviceAdaptiveState(self, which=0):
+        """Device address of the state's (sum, n) records (which 0) or (m1, m2, last q, last count) records (1), None before the
+        first RenderAdaptive."""
+        return _lib.drt_renderer_device_adaptive(self._h, int(which))
+
+    def resetAdaptive(self):
+        """Drop the adaptive state (drt_renderer_adaptive_reset): the next RenderAdaptive is uniform again."""
+        _check(_lib.drt_renderer_adaptive_reset(self._h))
+
     def trackMotion(self, enable=True):
         """Follow geometry that Renderer.refit moves (drt_renderer_track_motion): the first refit after a TemporalDenoise keeps
         the triangles as they were, and the next TemporalDenoise reprojects every moved triangle's pixels through that state.
@@ -1086,6 +1150,18 @@ def debug_upscale(colour, guides_lo, guides_hi, device=0, **params):
     out = np.zeros((Ho, Wo, 4), np.float32)
     _check(_lib.drt_debug_upscale(device, c.ctypes.data, lo.ctypes.data, hi.ctypes.data, W, H, Wo, Ho, C.byref(p), out.ctypes.data))
     return out
+
+
+def debug_adaptive_plan(q, thresholded=False, device=0, **params):
+    """Counts and their exclusive prefix sum on the device from made-up weights (drt.h drt_debug_adaptive_plan): q uint32 [n];
+    `params` = AdaptiveParams fields.  Returns (counts uint32 [n], offsets uint32 [n], Q)."""
+    q = np.ascontiguousarray(q, np.uint32).reshape(-1)
+    p = AdaptiveParams(**params)
+    counts, offsets = np.zeros(len(q), np.uint32), np.zeros(len(q), np.uint32)
+    Q = C.c_uint64(0)
+    _check(_lib.drt_debug_adaptive_plan(device, q.ctypes.data, len(q), C.byref(p), 1 if thresholded else 0, counts.ctypes.data,
+                                        offsets.ctypes.data, C.byref(Q)))
+    return counts, offsets, int(Q.value)
 
 
 def debug_decode_image(file_bytes):

@@ -1,6 +1,7 @@
 // drt_capi.cpp -- the C ABI of include/drt.h: scene handles, the renderer's lifecycle (device buffers, per-call constants, launches,
 // read-back), render batches, ray and radiance queries, refit, the debug entry points and error reporting.  The guide pass and the
-// filter stages (denoise, temporal, motion vectors, upscale) are in drt_capi_filters.cpp, what both share in renderer_state.hpp.
+// filter stages (denoise, temporal, motion vectors, upscale) are in drt_capi_filters.cpp, adaptive sampling is in
+// drt_capi_adaptive.cpp, what they share in renderer_state.hpp.
 //
 // Replaces class Renderer (Core/Renderer.hpp:14-47, Core/Renderer.cu) and InvokeRenderKernel
 // (Core/Kernel/RenderKernel.cu:37-58).  No GL interop: the framebuffer is a device float4 array.
@@ -483,6 +484,7 @@ int drt_renderer_reset(drt_renderer *r) {                      // Renderer.cu:13
     if (r->cur_accum() && r->width && r->local_rows)
         HIP_TRY(hipMemsetAsync(r->cur_accum(), 0, (size_t)r->width * r->local_rows * 3 * sizeof(float), r->stream));
     r->frame_index = 1;
+    r->free_adaptive();                        // (adaptive calls are blocking: nothing in flight reads the state; no state, no work)
     return DRT_OK;
 }
 

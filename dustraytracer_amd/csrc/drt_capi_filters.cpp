@@ -10,13 +10,13 @@
 using namespace drt;
 
 // The timed span of a stage on the renderer's stream: stage_begin opens it, stage_end closes it, waits and stores the time
-static int stage_begin(drt_renderer *r) {
+int drt::stage_begin(drt_renderer *r) {
     HIP_TRY(r->ev_dn_start.create());
     HIP_TRY(r->ev_dn_stop.create());
     HIP_TRY(hipEventRecord(r->ev_dn_start, r->stream));
     return DRT_OK;
 }
-static int stage_end(drt_renderer *r, float *delta_ms) {
+int drt::stage_end(drt_renderer *r, float *delta_ms) {
     HIP_TRY(hipEventRecord(r->ev_dn_stop, r->stream));
     HIP_TRY(hipEventSynchronize(r->ev_dn_stop));
     float ms = 0.f;

@@ -1,4 +1,4 @@
-// renderer_state.hpp -- what the translation units of the C ABI share (drt_capi.cpp, drt_capi_filters.cpp): the renderer's state,
+// renderer_state.hpp -- what the translation units of the C ABI share (drt_capi.cpp, drt_capi_filters.cpp, drt_capi_adaptive.cpp): the renderer's state,
 // the owners of its device memory, pinned memory and events, error reporting, the steps several entry points take.  Not exported.
 #pragma once
 #include "../../include/drt.h"
@@ -15,6 +15,7 @@
 #include "denoise.hpp"
 #include "temporal.hpp"
 #include "radiance.hpp"
+#include "adaptive.hpp"
 #include "refit.hpp"
 #include "scene_host.hpp"
 
@@ -196,6 +197,15 @@ struct drt_renderer {
     DeviceArray<drt_guide> us_guides;
     DeviceArray<float4> us_out;
     uint32_t us_width = 0, us_height = 0;
+    // drt_renderer_render_adaptive: the per-pixel state (ad_state[0] = sum rgb and n, ad_state[1] = m1, m2, the last call's q and
+    // count), the plan's arrays (weights, counts, offsets, the scan's block sums, the totals) and the ray list and sample buffer of
+    // one pixel range; allocated by the first call (the last two grow with the largest range), freed by resize, re-shard,
+    // destroy, drt_renderer_adaptive_reset and drt_renderer_reset (ad_state[0].ptr == nullptr: no state)
+    DeviceArray<float4> ad_state[2];
+    DeviceArray<uint32_t> ad_q, ad_counts, ad_offsets, ad_block_sums;
+    DeviceArray<drt::AdaptiveTotals> ad_totals;
+    DeviceArray<drt_path_ray> ad_rays;
+    DeviceArray<float4> ad_samples;
 
     drt_renderer() = default;
     ~drt_renderer() {                          // the members release what they own, on this device
@@ -229,8 +239,13 @@ struct drt_renderer {
             for (auto &b : half) b.release();
         tp_cur = -1;
     }
+    void free_adaptive() {
+        ad_state[0].release(); ad_state[1].release();
+        ad_q.release(); ad_counts.release(); ad_offsets.release(); ad_block_sums.release(); ad_totals.release();
+        ad_rays.release(); ad_samples.release();
+    }
     void free_stages() {                       // resize and re-shard: every stage's buffers are of the old frame
-        free_denoise(); free_temporal(); mv_guides.release(); free_upscale();
+        free_denoise(); free_temporal(); mv_guides.release(); free_upscale(); free_adaptive();
     }
 };
 
@@ -252,6 +267,10 @@ int traversal_scratch(drt_renderer *r, hipStream_t s, bool occluded, bool heads)
 int stage_open(drt_renderer *r, const char *who);
 int whole_frame(const drt_renderer *r, const char *who);
 int read_back(drt_renderer *r, const float *src, int comps, float *dst, size_t dst_floats);
+// The timed span of a stage on the renderer's stream (drt_capi_filters.cpp): stage_begin opens it, stage_end closes it, waits and
+// stores the device time
+int stage_begin(drt_renderer *r);
+int stage_end(drt_renderer *r, float *delta_ms);
 
 }  // namespace drt
 

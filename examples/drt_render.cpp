@@ -7,6 +7,9 @@
 //                                                  given pose, 1 spp each, temporally accumulated and filtered: writes the last pose)
 //   ./drt_render models/cornell_box.glb out.png 960 540 1 8  3.6 1.25 0  -1 0 0  --upscale 1920 1080 --temporal 12   (rendered and filtered
 //                                                  at 960 x 540, rebuilt at 1920 x 1080 from full-size first-hit guides: writes the large image)
+//   ./drt_render models/cornell_box.glb out.png 1920 1080 1 8  3.6 1.25 0  -1 0 0  --adaptive 4 --target-error 0.01 --adaptive-calls 8
+//                                                  (up to 8 adaptive calls of 4 samples per pixel each, spent where the noise is, until every
+//                                                  pixel's relative error is below 1 %: writes sum / n; the spp argument is not used)
 //   DRT_DEVICES=0,1,2,3,4,5,6,7 ./drt_render models/room.glb out.pfm 3840 2160 64 16  0 1.4 2  0 0 -1     (all GPUs of the node: stripes + RCCL gather)
 #include <DustRayTracer.hpp>
 #include <DustRayTracerGL.hpp>
@@ -36,8 +39,27 @@ int main(int argc, char **argv) {
         up_h = std::atol(argv[argc - 1]);
         argc -= 3;
     }
-    if (argc < 7 || temporal < 0 || (upscale && (up_w <= 0 || up_h <= 0))) {
-        std::fprintf(stderr, "usage: %s scene.glb out.pfm width height spp depth [px py pz fx fy fz] [--upscale OW OH] [--temporal K] [--denoise]\n", argv[0]);
+    int adaptive_calls = 8;                               // --adaptive SPP [--target-error E] [--adaptive-calls K]: optional, last (before --upscale)
+    double adaptive_spp = 0, target_error = 0;
+    const bool calls_given = argc > 2 && std::strcmp(argv[argc - 2], "--adaptive-calls") == 0;
+    if (calls_given) {
+        adaptive_calls = std::atoi(argv[argc - 1]);
+        argc -= 2;
+    }
+    const bool error_given = argc > 2 && std::strcmp(argv[argc - 2], "--target-error") == 0;
+    if (error_given) {
+        target_error = std::atof(argv[argc - 1]);
+        argc -= 2;
+    }
+    const bool adaptive = argc > 2 && std::strcmp(argv[argc - 2], "--adaptive") == 0;
+    if (adaptive) {
+        adaptive_spp = std::atof(argv[argc - 1]);
+        argc -= 2;
+    }
+    if (argc < 7 || temporal < 0 || (upscale && (up_w <= 0 || up_h <= 0)) || ((calls_given || error_given) && !adaptive) ||
+        (adaptive && (!(adaptive_spp >= 1) || adaptive_calls < 1 || !(target_error >= 0)))) {
+        std::fprintf(stderr, "usage: %s scene.glb out.pfm width height spp depth [px py pz fx fy fz] [--adaptive SPP [--target-error E] [--adaptive-calls K]] "
+                             "[--upscale OW OH] [--temporal K] [--denoise]\n", argv[0]);
         return 2;
     }
     try {
@@ -63,11 +85,31 @@ int main(int argc, char **argv) {
         renderer.m_RendererSettings.max_samples = (int)spp + 1;
         renderer.ResizeBuffer(W, H);
         float ms = 0;
-        renderer.RenderBatch(&cam, scene, spp, &ms);
         std::vector<float> rgba((size_t)W * H * 4);
-        renderer.ReadRenderTarget(rgba.data());
-        std::printf("%zu triangles, %u x %u, %u spp on %d GPU%s: %.3f ms (%.1f Msamples/s)\n", scene.trianglesCount(), W, H, spp,
-                    renderer.deviceCount(), renderer.deviceCount() > 1 ? "s" : "", ms, (double)W * H * spp / ms / 1e3);
+        if (adaptive) {
+            // K adaptive calls of SPP samples per pixel each instead of the frame loop; over once every pixel is converged
+            drt_adaptive_params p;
+            drt_default_adaptive_params(&p);
+            p.budget = (uint32_t)std::min(adaptive_spp * (double)W * (double)H, 4294967295.0);       // (the library refuses 2^31 and more)
+            p.target_error = (float)target_error;
+            unsigned long long samples = 0;
+            int calls = 0;
+            while (calls < adaptive_calls) {
+                const drt_adaptive_info info = renderer.RenderAdaptive(&cam, scene, &p);
+                calls++;
+                samples += info.samples;
+                ms += info.ms;
+                if (info.active_pixels == 0) break;
+            }
+            renderer.ReadRenderTarget(rgba.data());
+            std::printf("%zu triangles, %u x %u, adaptive: %d calls, %llu samples (%.2f per pixel): %.3f ms\n", scene.trianglesCount(), W, H, calls,
+                        samples, (double)samples / ((double)W * H), ms);
+        } else {
+            renderer.RenderBatch(&cam, scene, spp, &ms);
+            renderer.ReadRenderTarget(rgba.data());
+            std::printf("%zu triangles, %u x %u, %u spp on %d GPU%s: %.3f ms (%.1f Msamples/s)\n", scene.trianglesCount(), W, H, spp,
+                        renderer.deviceCount(), renderer.deviceCount() > 1 ? "s" : "", ms, (double)W * H * spp / ms / 1e3);
+        }
         if (denoise) {                                    // the a-trous filter of the frame, default parameters (drt_default_denoise_params)
             drt_denoise_params p;
             drt_default_denoise_params(&p);

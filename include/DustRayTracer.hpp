@@ -255,6 +255,7 @@ public:
     void RenderBatch(Camera *cam, const Scene &scene, uint32_t n_frames, float *delta) {
         drt_settings s = m_RendererSettings.pod();
         drt_camera c = cam->pod();
+        m_AdaptiveFrame = false;
         if (group) {
             drt::check(drt_group_set_settings(group, &s));
             drt::check(drt_group_render_batch(group, &c, scene.handle, n_frames, delta));
@@ -278,9 +279,9 @@ public:
     // replaces GLuint& GetRenderTargetImage_name(): RGBA32F, row 0 = bottom, width*height*4 floats
     void ReadRenderTarget(float *dst) {
         const size_t n = (size_t)getBufferWidth() * getBufferHeight() * 4;
-        drt::check(group ? drt_group_read_rgba32f(group, dst, n) : drt_renderer_read_rgba32f(handle, dst, n));
+        drt::check(gathered() ? drt_group_read_rgba32f(group, dst, n) : drt_renderer_read_rgba32f(handle, dst, n));
     }
-    void *DeviceRenderTarget() { return group ? drt_group_device_rgba(group) : drt_renderer_device_rgba(handle); }
+    void *DeviceRenderTarget() { return gathered() ? drt_group_device_rgba(group) : drt_renderer_device_rgba(handle); }
     // Batched ray queries (drt_renderer_trace_rays / _occluded: device arrays, enqueued on `stream`, NULL = the renderer's).
     // A multi-device renderer answers them on its first device (handle = drt_group_renderer(group, 0)).
     void TraceRays(const Scene &scene, const drt_ray *rays, drt_hit *hits, uint32_t n, void *stream = nullptr) {
@@ -374,12 +375,37 @@ public:
         drt::check(drt_renderer_read_upscaled_rgba32f(handle, dst, (size_t)m_UpscaledWidth * m_UpscaledHeight * 4));
     }
     void *DeviceUpscaledTarget() { return drt_renderer_device_upscaled(handle); }
+    // Adaptive sampling (drt_renderer_render_adaptive; blocking): one call spends params->budget samples (0 = 4 per pixel) where the
+    // per-pixel state says the noise is and leaves sum / n in the framebuffer (ReadRenderTarget and the filters read it).  The first
+    // call after a reset or resize is uniform.  params NULL = drt_default_adaptive_params.  A multi-device renderer is refused.
+    drt_adaptive_info RenderAdaptive(Camera *cam, const Scene &scene, const drt_adaptive_params *params = nullptr) {
+        drt_adaptive_params p;
+        drt_default_adaptive_params(&p);
+        if (params) p = *params;
+        drt_adaptive_info info;
+        drt_settings s = m_RendererSettings.pod();
+        drt_camera c = cam->pod();
+        drt::check(drt_renderer_set_settings(handle, &s));
+        drt::check(drt_renderer_render_adaptive(handle, &c, scene.handle, &p, &info));
+        m_AdaptiveFrame = true;
+        return info;
+    }
+    void ResetAdaptive() { drt::check(drt_renderer_adaptive_reset(handle)); }
+    // the adaptive state, width*height*4 words: which 0 = (sum rgb, n as uint32), 1 = (m1, m2, the last call's q and count as uint32)
+    void ReadAdaptiveState(int which, void *dst) {
+        drt::check(drt_renderer_read_adaptive(handle, which, dst, (size_t)getBufferWidth() * getBufferHeight() * 16));
+    }
     // the history of the last TemporalDenoise, width*height*4 floats: which 0 = (colour rgb, N), 1 = (m1, m2, variance, weight sum)
     void ReadTemporal(int which, float *dst) {
         drt::check(drt_renderer_read_temporal(handle, which, dst, (size_t)getBufferWidth() * getBufferHeight() * 4));
     }
 
+    // A group's frame is the image its stripes were gathered into.  An adaptive call (a group of one device only: a sharded renderer
+    // is refused) writes the device's own framebuffer instead, which then is the frame until the next RenderBatch.
+    bool gathered() const { return group && !m_AdaptiveFrame; }
+
     RendererSettings m_RendererSettings;
+    bool m_AdaptiveFrame = false;         // the last frame came from RenderAdaptive
     uint32_t m_UpscaledWidth = 0, m_UpscaledHeight = 0;      // the size of the last Upscale
     drt_renderer *handle = nullptr;       // the (first) device's renderer
     drt_group *group = nullptr;           // set when the renderer spans several devices

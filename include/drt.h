@@ -27,7 +27,7 @@ extern "C" {
 
 /* 2: drt_counters grew by sampler_tries; drt_group_* and drt_material_model entry points (round 2) are part of it; the ray-query
  * entry points (drt_renderer_trace_rays / _occluded), the guide / denoise entry points, the refit entry points and the camera-ray /
- * radiance entry points and the upscaling entry points are additions to it */
+ * radiance entry points, the upscaling entry points and the adaptive-sampling entry points are additions to it */
 #define DRT_ABI_VERSION 2
 
 typedef enum {
@@ -210,7 +210,7 @@ int           drt_renderer_render_batch(drt_renderer *r, const drt_camera *cam, 
  * and returns its device time.  Lets a caller keep several frames in flight (one renderer + stream per frame). */
 int           drt_renderer_render_batch_async(drt_renderer *r, const drt_camera *cam, const drt_scene *scene, uint32_t n_frames);
 int           drt_renderer_wait(drt_renderer *r, float *delta_ms);
-int           drt_renderer_reset(drt_renderer *r);                            /* resetAccumulationBuffer: zero + sample_count = 1 */
+int           drt_renderer_reset(drt_renderer *r);                            /* resetAccumulationBuffer: zero + sample_count = 1 (and the adaptive state, if any, is dropped) */
 uint32_t      drt_renderer_width(const drt_renderer *r);                      /* getBufferWidth */
 uint32_t      drt_renderer_height(const drt_renderer *r);                     /* getBufferHeight */
 uint32_t      drt_renderer_sample_count(const drt_renderer *r);               /* getSampleCount == m_FrameIndex (starts at 1) */
@@ -469,6 +469,62 @@ int           drt_renderer_camera_rays(drt_renderer *r, const drt_camera *cams, 
                                        uint32_t frame_index, drt_path_ray *rays, void *hip_stream);
 int           drt_renderer_radiance(drt_renderer *r, const drt_scene *scene, const drt_path_ray *rays, float *out, uint32_t n,
                                     int32_t accumulate, void *hip_stream);
+
+/* ---- adaptive sampling: spend each call's samples where the noise is (new; the reference gives every pixel one sample per frame) ----
+ * drt_renderer_render_adaptive(r, cam, scene, params, info) spends `budget` samples on the frame, more of them where the pixels are
+ * noisier, and keeps a per-pixel state from call to call.  Every sample is a sample the uniform renderer would take: the k-th
+ * sample a pixel ever receives is its sample of frame k, and the samples are summed in frame order.  A pixel that has received n
+ * samples therefore holds, bit for bit, what drt_renderer_read_accum shows at that pixel after a reset and n drt_renderer_render
+ * calls with the same camera, scene and settings.  Pixel p = x + y * width, row 0 = bottom, as everywhere.
+ * Per-pixel state (allocated by the first call; freed by resize, re-shard, destroy, drt_renderer_adaptive_reset and
+ *   drt_renderer_reset, after which the next call starts from nothing; without a state drt_renderer_reset does what it always did):
+ *   sum (three fp32: the running colour sum), n (uint32: the samples so far), m1 = sum of Y and m2 = sum of Y * Y in fp32 with Y =
+ *   lum(c) of a sample's colour c (lum as defined above: 0.2126f c.r + 0.7152f c.g + 0.0722f c.b), every * and + rounded on its own,
+ *   left to right as written.
+ * Weight of a pixel, all fp32, one rounding per operation:  n < 2: the weight is unknown, q = 16777215.  Otherwise
+ *   mean = m1 / n,  var = fmaxf(m2 / n - mean * mean, 0),  w = sqrtf(var / n) / (mean + luma_floor)    (n converted to fp32)
+ *   (the standard error of the mean luminance relative to the mean: radiance is not negative, so neither is w).
+ *   If target_error > 0 and w <= target_error: q = 0, the pixel is CONVERGED.  Else s = w * 65536.0f and
+ *   q = s < 16777215.0f ? (uint32)s : 16777215  (written so that a NaN or infinite w takes the cap); q == 0 here is converged too.
+ * Counts, all integer arithmetic:  Q = sum of q (uint64),  extra = budget - min_spp * pixels,  active = the pixels with q > 0.
+ *   A converged pixel gets 0 samples when target_error > 0 and min_spp otherwise; an active pixel gets
+ *   min(max_spp, min_spp + (uint32)((uint64)extra * q / Q)).  If Q == 0 and target_error == 0 every pixel gets min(max_spp, min_spp +
+ *   extra / pixels).  The counts never sum to more than budget; what the floors and max_spp drop is not redistributed.  On the first
+ *   call every pixel is unknown, all q are equal and the call is uniform: no pilot pass is needed.
+ * Samples.  A pixel with state count n and call count c receives samples k = 1..c: sample k is the radiance (drt_renderer_radiance:
+ *   the current settings and material model) of Camera::GetRay for that pixel in frame n + k -- uv = ((float)x / width) * 2 - 1,
+ *   ((float)y / height) * 2 - 1, seed = (x + y * width) * (n + k) in uint32, the camera's constants for the frame size, exactly
+ *   drt_renderer_camera_rays' rule.  They are folded in that order: sum += c_k (one fp32 add per component), m1 += Y, m2 += Y * Y;
+ *   then n += c.
+ * Image.  sum / (float)n per component with alpha 1, (0, 0, 0, 1) where n == 0, written for EVERY pixel to the framebuffer (the
+ *   bound one after drt_renderer_bind_buffers): drt_renderer_read_rgba32f, the denoisers, the upscaler and the GL target see it
+ *   without change.  A later drt_renderer_render overwrites the framebuffer as it always did.
+ * The accumulation buffer, the sample count, the counters, kernel info and span, the temporal history, the denoised and the upscaled
+ * target are not touched.  Blocking.  info (may be NULL): samples = the sum of the counts, active_pixels, max_count = the largest
+ * count, ms = the device time of the call.  When the samples of a call need more than the renderer's per-launch sample memory (48
+ * bytes per sample; DRT_SAMPLE_MB), they are traced in contiguous pixel ranges, which changes no bit.
+ * drt_renderer_read_adaptive: which 0 = float4 {sum, bits of n}, 1 = float4 {m1, m2, bits of the last call's q, bits of its count}
+ * per pixel, width * height * 16 bytes; drt_renderer_device_adaptive: the same arrays on the device, NULL before the first call.
+ * drt_debug_adaptive_plan runs the counts and their exclusive prefix sum alone on host arrays (q, counts, offsets: uint32[pixels];
+ * `thresholded` stands for target_error > 0, params->target_error is not read; Q_out may be NULL), for tests that make up q.
+ * DRT_ERR_INVALID: a NULL argument (info excepted), no frame size, a pending drt_renderer_render_batch_async batch, min_spp >
+ * max_spp, max_spp < 1, a budget below min_spp * pixels or of 2^31 samples or more, a target_error not finite or < 0, a luma_floor
+ * not finite or not > 0, `which` outside 0..1, a too short dst, a read before the first call.  DRT_ERR_UNSUPPORTED: a sharded
+ * renderer (world > 1), render_mode DEBUGMODE, a tree deeper than 64 levels.
+ * Out of scope: adaptive sampling inside the frame loop's own kernels; drt_group and sharded renderers; feeding the temporal
+ * filter's variance into the weights; redistributing what the floors drop; a linear (pre-tone-curve) target. */
+typedef struct drt_adaptive_params { uint32_t budget;      /* samples this call; >= min_spp * pixels, < 2^31 */
+                                     uint32_t min_spp, max_spp;       /* per call; default 1, 64; min <= max, max >= 1 */
+                                     float target_error, luma_floor;  /* default 0 (off), 0.01; finite, >= 0 resp. > 0 */ } drt_adaptive_params;
+typedef struct drt_adaptive_info   { uint32_t samples, active_pixels, max_count; float ms; } drt_adaptive_info;
+void          drt_default_adaptive_params(drt_adaptive_params *out);           /* budget 0 = 4 * pixels at call time */
+int           drt_renderer_render_adaptive(drt_renderer *r, const drt_camera *cam, const drt_scene *scene, const drt_adaptive_params *p,
+                                           drt_adaptive_info *info);
+int           drt_renderer_adaptive_reset(drt_renderer *r);               /* drop the state; the next call is uniform again */
+int           drt_renderer_read_adaptive(drt_renderer *r, int32_t which, void *dst, size_t dst_bytes);
+void         *drt_renderer_device_adaptive(drt_renderer *r, int32_t which);     /* device float4[width*height], NULL before the first call */
+int           drt_debug_adaptive_plan(int32_t device, const uint32_t *q, uint32_t pixels, const drt_adaptive_params *p, int32_t thresholded,
+                                      uint32_t *counts, uint32_t *offsets, uint64_t *Q_out);
 
 /* ---- BVH refit for moving geometry (new; the reference rebuilds) ----
  * A refit keeps the tree's topology, node order and triangle order and recomputes the boxes bottom-up from new vertex positions.
