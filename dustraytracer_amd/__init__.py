@@ -349,6 +349,8 @@ _sig("drt_renderer_adaptive_reset", C.c_int, _P)
 _sig("drt_renderer_read_adaptive", C.c_int, _P, C.c_int32, _P, C.c_size_t)
 _sig("drt_renderer_device_adaptive", _P, _P, C.c_int32)
 _sig("drt_debug_adaptive_plan", C.c_int, C.c_int32, _P, C.c_uint32, C.POINTER(AdaptiveParams), C.c_int32, _P, _P, C.POINTER(C.c_uint64))
+_sig("drt_debug_adaptive_weights", C.c_int, C.c_int32, _P, _P, C.c_uint32, C.POINTER(AdaptiveParams), _P, C.POINTER(C.c_uint64),
+     C.POINTER(C.c_uint32))
 _sig("drt_scene_get_triangle_order", C.c_int, _P, _P, C.c_int32)
 _sig("drt_scene_refit", C.c_int, _P, _P, _P)
 _sig("drt_renderer_refit", C.c_int, _P, _P, _P, _P, C.POINTER(C.c_float), _P)
@@ -1162,6 +1164,23 @@ def debug_adaptive_plan(q, thresholded=False, device=0, **params):
     _check(_lib.drt_debug_adaptive_plan(device, q.ctypes.data, len(q), C.byref(p), 1 if thresholded else 0, counts.ctypes.data,
                                         offsets.ctypes.data, C.byref(Q)))
     return counts, offsets, int(Q.value)
+
+
+def debug_adaptive_weights(state, device=0, **params):
+    """The weights stage on made-up state records, inside the whole plan as a call runs it (drt.h drt_debug_adaptive_weights):
+    `state` has n (or count) uint32 [P], m1 and m2 float32 [P], as tests/adaptive_ref.py's State or AdaptiveState; `params` =
+    AdaptiveParams fields.  Returns (q uint32 [P], Q, active)."""
+    n = np.ascontiguousarray(state.n if hasattr(state, "n") else state.count, np.uint32).reshape(-1)
+    s0, s1 = np.zeros((len(n), 4), np.float32), np.zeros((len(n), 4), np.float32)
+    s0.view(np.uint32)[:, 3] = n
+    s1[:, 0] = np.asarray(state.m1, np.float32).reshape(-1)
+    s1[:, 1] = np.asarray(state.m2, np.float32).reshape(-1)
+    p = AdaptiveParams(**params)
+    q = np.zeros(len(n), np.uint32)
+    Q, active = C.c_uint64(0), C.c_uint32(0)
+    _check(_lib.drt_debug_adaptive_weights(device, s0.ctypes.data, s1.ctypes.data, len(n), C.byref(p), q.ctypes.data, C.byref(Q),
+                                           C.byref(active)))
+    return q, int(Q.value), int(active.value)
 
 
 def debug_decode_image(file_bytes):

@@ -197,4 +197,31 @@ int drt_debug_adaptive_plan(int32_t device, const uint32_t *q, uint32_t pixels, 
     return DRT_OK;
 }
 
+int drt_debug_adaptive_weights(int32_t device, const float *state0, const float *state1, uint32_t pixels, const drt_adaptive_params *p,
+                               uint32_t *q, uint64_t *Q_out, uint32_t *active_out) {
+    if (!state0 || !state1 || !p || !q) return fail(DRT_ERR_INVALID, "null argument");
+    uint32_t budget = 0;
+    if (const char *why = adaptive_arguments(p, pixels, &budget)) return fail(DRT_ERR_INVALID, why);
+    HIP_TRY(hipSetDevice(device));
+    DeviceArray<float4> d_s0, d_s1;
+    DeviceArray<uint32_t> d_q, d_counts, d_offsets, d_sums;
+    DeviceArray<AdaptiveTotals> d_tot;
+    HIP_TRY(alloc_group(pixels, d_s0, d_s1));
+    HIP_TRY(alloc_group(pixels, d_q, d_counts, d_offsets));
+    HIP_TRY(d_sums.alloc((pixels + kScanBlock - 1) / kScanBlock));
+    HIP_TRY(d_tot.alloc_zeroed(1));
+    HIP_TRY(hipMemcpy(d_s0.ptr, state0, (size_t)pixels * sizeof(float4), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_s1.ptr, state1, (size_t)pixels * sizeof(float4), hipMemcpyHostToDevice));
+    AdaptivePlanArgs a = plan_args(p, pixels, budget, p->target_error > 0.f);      // (as drt_renderer_render_adaptive sets them)
+    a.state0 = d_s0.ptr; a.state1 = d_s1.ptr;
+    a.q = d_q.ptr; a.counts = d_counts.ptr; a.offsets = d_offsets.ptr; a.block_sums = d_sums.ptr; a.totals = d_tot.ptr;
+    HIP_TRY(launch_adaptive_plan(a, nullptr));
+    AdaptiveTotals tot;
+    HIP_TRY(hipMemcpy(&tot, d_tot.ptr, sizeof tot, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(q, d_q.ptr, (size_t)pixels * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (Q_out) *Q_out = tot.Q;
+    if (active_out) *active_out = tot.active;
+    return DRT_OK;
+}
+
 }  // extern "C"

@@ -490,7 +490,11 @@ int           drt_renderer_radiance(drt_renderer *r, const drt_scene *scene, con
  *   A converged pixel gets 0 samples when target_error > 0 and min_spp otherwise; an active pixel gets
  *   min(max_spp, min_spp + (uint32)((uint64)extra * q / Q)).  If Q == 0 and target_error == 0 every pixel gets min(max_spp, min_spp +
  *   extra / pixels).  The counts never sum to more than budget; what the floors and max_spp drop is not redistributed.  On the first
- *   call every pixel is unknown, all q are equal and the call is uniform: no pilot pass is needed.
+ *   call every pixel is unknown, all q are equal and the call is uniform: no pilot pass is needed.  A consequence of the floors: where
+ *   extra * q < Q for every pixel -- min_spp == 0 and a budget below one sample per pixel on a state whose weights are all equal,
+ *   the first call included -- every count is 0: the call succeeds with samples == 0, the state is as it was (allocated and zero on
+ *   a first call: n == 0 everywhere) and the image is sum / n of it, (0, 0, 0, 1) where n == 0.  The next call is planned as if this
+ *   one had not been made.
  * Samples.  A pixel with state count n and call count c receives samples k = 1..c: sample k is the radiance (drt_renderer_radiance:
  *   the current settings and material model) of Camera::GetRay for that pixel in frame n + k -- uv = ((float)x / width) * 2 - 1,
  *   ((float)y / height) * 2 - 1, seed = (x + y * width) * (n + k) in uint32, the camera's constants for the frame size, exactly
@@ -507,6 +511,10 @@ int           drt_renderer_radiance(drt_renderer *r, const drt_scene *scene, con
  * per pixel, width * height * 16 bytes; drt_renderer_device_adaptive: the same arrays on the device, NULL before the first call.
  * drt_debug_adaptive_plan runs the counts and their exclusive prefix sum alone on host arrays (q, counts, offsets: uint32[pixels];
  * `thresholded` stands for target_error > 0, params->target_error is not read; Q_out may be NULL), for tests that make up q.
+ * drt_debug_adaptive_weights runs the weights stage on made-up state records (state0, state1: float4[pixels] laid out as
+ * drt_renderer_read_adaptive's which 0 and 1; only the bits of n, m1 and m2 are read) inside the whole plan, as a call runs it with
+ * these params: q[pixels] = the weights, *Q_out = their sum, *active_out = the pixels with q > 0 (either may be NULL), for tests
+ * that make up moments no render produces.
  * DRT_ERR_INVALID: a NULL argument (info excepted), no frame size, a pending drt_renderer_render_batch_async batch, min_spp >
  * max_spp, max_spp < 1, a budget below min_spp * pixels or of 2^31 samples or more, a target_error not finite or < 0, a luma_floor
  * not finite or not > 0, `which` outside 0..1, a too short dst, a read before the first call.  DRT_ERR_UNSUPPORTED: a sharded
@@ -525,6 +533,8 @@ int           drt_renderer_read_adaptive(drt_renderer *r, int32_t which, void *d
 void         *drt_renderer_device_adaptive(drt_renderer *r, int32_t which);     /* device float4[width*height], NULL before the first call */
 int           drt_debug_adaptive_plan(int32_t device, const uint32_t *q, uint32_t pixels, const drt_adaptive_params *p, int32_t thresholded,
                                       uint32_t *counts, uint32_t *offsets, uint64_t *Q_out);
+int           drt_debug_adaptive_weights(int32_t device, const float *state0, const float *state1, uint32_t pixels,
+                                         const drt_adaptive_params *p, uint32_t *q, uint64_t *Q_out, uint32_t *active_out);
 
 /* ---- BVH refit for moving geometry (new; the reference rebuilds) ----
  * A refit keeps the tree's topology, node order and triangle order and recomputes the boxes bottom-up from new vertex positions.

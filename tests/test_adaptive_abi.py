@@ -14,7 +14,7 @@ from tests.scenes import ROOT
 drt = pytest.importorskip("dustraytracer_amd")
 
 NEW = ["drt_default_adaptive_params", "drt_renderer_render_adaptive", "drt_renderer_adaptive_reset", "drt_renderer_read_adaptive",
-       "drt_renderer_device_adaptive", "drt_debug_adaptive_plan"]
+       "drt_renderer_device_adaptive", "drt_debug_adaptive_plan", "drt_debug_adaptive_weights"]
 FIELDS = [("budget", 0), ("min_spp", 4), ("max_spp", 8), ("target_error", 12), ("luma_floor", 16)]
 INFO = [("samples", 0), ("active_pixels", 4), ("max_count", 8), ("ms", 12)]
 
@@ -25,7 +25,7 @@ def test_the_new_symbols_are_exported_and_bound():
     assert all(getattr(drt._lib, n).argtypes is not None for n in NEW)
     for name in ("RenderAdaptive", "GetAdaptiveState", "DeviceAdaptiveState", "resetAdaptive"):
         assert callable(getattr(drt.Renderer, name))
-    assert callable(drt.debug_adaptive_plan)
+    assert callable(drt.debug_adaptive_plan) and callable(drt.debug_adaptive_weights)
     assert drt.AdaptiveState._fields == ("sum", "count", "m1", "m2", "last_q", "last_count")
     assert drt._lib.drt_abi_version() == 2
 
@@ -91,6 +91,19 @@ def test_null_handles_and_bad_arguments_are_invalid_without_a_gpu():
         assert L.drt_debug_adaptive_plan(*(ok[:3] + (ctypes.byref(b),) + ok[4:])) == drt.ERR_INVALID, bad
     big = np.zeros(1, np.uint32)                                # budget 0 = 4 per pixel: 2^29 pixels would make it 2^31
     assert L.drt_debug_adaptive_plan(0, big.ctypes.data, 1 << 29, ctypes.byref(p), 0, big.ctypes.data, big.ctypes.data, None) == drt.ERR_INVALID
+    # so does the weights-only entry (Q and active are optional)
+    s0, s1 = np.zeros((4, 4), np.float32), np.zeros((4, 4), np.float32)
+    ok = (0, s0.ctypes.data, s1.ctypes.data, 4, ctypes.byref(p), q.ctypes.data, None, None)
+    for i in (1, 2, 4, 5):
+        assert L.drt_debug_adaptive_weights(*(ok[:i] + (None,) + ok[i + 1:])) == drt.ERR_INVALID, i
+    assert b"null" in L.drt_last_error()
+    assert L.drt_debug_adaptive_weights(*(ok[:3] + (0,) + ok[4:])) == drt.ERR_INVALID                # no pixels
+    for bad in (dict(min_spp=3, max_spp=2), dict(min_spp=0, max_spp=0), dict(budget=3), dict(budget=1 << 31), dict(min_spp=5, budget=19),
+                dict(target_error=-1.0), dict(target_error=float("nan")), dict(target_error=float("inf")), dict(luma_floor=0.0),
+                dict(luma_floor=-0.01), dict(luma_floor=float("nan")), dict(luma_floor=float("inf"))):
+        b = drt.AdaptiveParams(**bad)
+        assert L.drt_debug_adaptive_weights(*(ok[:4] + (ctypes.byref(b),) + ok[5:])) == drt.ERR_INVALID, bad
+    assert L.drt_debug_adaptive_weights(0, s0.ctypes.data, s1.ctypes.data, 1 << 29, ctypes.byref(p), q.ctypes.data, None, None) == drt.ERR_INVALID
 
 
 def test_the_header_states_the_rule_and_what_is_out_of_scope():

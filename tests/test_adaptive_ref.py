@@ -3,6 +3,7 @@ compare the kernels with has to be right on its own.  No GPU."""
 import numpy as np
 import pytest
 
+from tests import adaptive_cases as ac
 from tests import adaptive_ref as ar
 
 F = np.float32
@@ -131,3 +132,58 @@ def test_offsets_fold_and_image():
     img = ar.image(st)
     assert (img[:, 0] == [2, 15, 200]).all() and (img[:, 3] == 1).all()
     assert (ar.image(ar.empty_state(2)) == [0, 0, 0, 1]).all()
+
+
+# ---------------------------------------------------------------- the edge table of the weights stage (tests/adaptive_cases.py)
+
+@pytest.mark.parametrize("luma_floor", ac.LUMA_FLOORS)
+def test_the_weight_table_is_what_it_claims_to_be(luma_floor):
+    t = ac.weight_table(luma_floor)
+    P = len(t.n)
+    assert P <= 3000, "the largest size of the GPU test has to hold the whole table"
+    assert not (t.m1 < 0).any(), "negative m1 is left out (see adaptive_cases)"
+    q = ar.weights(t, ac.TARGET_ERROR, luma_floor)
+    for what, share in (("converged", (q == 0).mean()), ("cap", (q == CAP).mean()), ("in between", ((q > 0) & (q < CAP)).mean())):
+        assert share >= 0.10, "%s: %.1f %% of the table" % (what, 100 * share)
+    q0 = ar.weights(t, 0.0, luma_floor)
+    assert ((q0 > 0) & (q == 0)).mean() >= 0.05, "target_error has to decide a fair share"
+    # every n and every kind of moment the table promises
+    assert set(ac.N_EDGES) <= set(int(v) for v in t.n)
+    for n in ac.N_EDGES:
+        assert ((t.n == n) & (t.m1 == 0) & (t.m2 == 0)).any(), n
+    tiny = np.finfo(F).tiny
+    big = (t.n >= 2)
+    assert (big & np.isposinf(t.m2) & np.isfinite(t.m1)).any() and (big & np.isposinf(t.m1) & np.isposinf(t.m2)).any()
+    assert (big & np.isnan(t.m1)).any() and (big & np.isnan(t.m2)).any()
+    assert (big & (t.m1 > 0) & (t.m1 < tiny)).any() and (big & (t.m2 > 0) & (t.m2 < tiny)).any()
+    with np.errstate(all="ignore"):
+        mean = (t.m1 / t.n.astype(F)).astype(F)
+        assert (big & np.isfinite(mean) & np.isinf((mean * mean).astype(F)) & np.isfinite((t.m2 / t.n.astype(F)).astype(F))).any(), \
+            "mean * mean overflows while m2 / n does not"
+    raw = ac.raw_variance(t)
+    assert (big & np.isnan(raw) & ~np.isnan(t.m1) & ~np.isnan(t.m2)).any(), "inf - inf"
+    # constant luminance: the clamp is reached by rounding alone, and missed by rounding alone
+    c = ac.constant_luminance(np.random.default_rng(2024))
+    raw = ac.raw_variance(c)
+    assert (raw < 0).sum() >= 10 and (raw > 0).sum() >= 10 and (raw == 0).sum() >= 1
+
+
+@pytest.mark.parametrize("luma_floor", ac.LUMA_FLOORS)
+def test_both_border_runs_contain_the_flip(luma_floor):
+    for run in ac.border_runs(luma_floor, "target"):
+        assert len(run.n) == ac.RUN and (np.diff(run.m2.view(np.uint32).astype(np.int64)) == 1).all()      # consecutive float32 values
+        q = ar.weights(run, ac.TARGET_ERROR, luma_floor)
+        assert (q[:ac.RUN // 2] == 0).all() and (q[ac.RUN // 2:] > 0).all() and (q[ac.RUN // 2:] < CAP).all()
+        assert (ar.weights(run, 0.0, luma_floor) > 0).all()
+    assert sum(int((ac.w_of(run, luma_floor) == F(ac.TARGET_ERROR)).sum()) for run in ac.border_runs(luma_floor, "target")) >= 3, \
+        "w == target_error itself has to be in the table: the one input that tells `<=` from `<`"
+    for run in ac.border_runs(luma_floor, "cap"):
+        assert len(run.n) == ac.RUN and (np.diff(run.m2.view(np.uint32).astype(np.int64)) == 1).all()
+        for te in (0.0, ac.TARGET_ERROR):
+            q = ar.weights(run, te, luma_floor)
+            assert (q[:ac.RUN // 2] < CAP).all() and q[ac.RUN // 2 - 1] >= CAP - 8 and (q[ac.RUN // 2:] == CAP).all()
+    t = ac.weight_table(luma_floor)                                # and the table holds them
+    rows = set(zip(t.n.tolist(), t.m1.view(np.uint32).tolist(), t.m2.view(np.uint32).tolist()))
+    for which in ("target", "cap"):
+        for run in ac.border_runs(luma_floor, which):
+            assert set(zip(run.n.tolist(), run.m1.view(np.uint32).tolist(), run.m2.view(np.uint32).tolist())) <= rows

@@ -20,15 +20,25 @@ pytestmark = pytest.mark.gpu
 
 W, H = 64, 48
 PX = W * H
-CALLS, SPP, MAX_SPP = 3, 3, 8
-FRAMES = CALLS * MAX_SPP                       # no pixel can have received more samples than this
+CALLS, SPP, MAX_SPP = 3, 3, 8                  # (of a config that does not say otherwise)
 _scenes, _runs = {}, {}
 
+# name -> (scene, settings[, what the config sets of its own: size (w, h), camera (Camera -> None), material (the model's arguments,
+# on both renderers), spp (one per call), max_spp])
 CONFIGS = {
     "cornell_box": ("cornell_box", dict(ray_bounce_limit=4)),
     "sunlight": ("cornell_box", dict(ray_bounce_limit=4, enableSunlight=1)),
     "no_tone_curve": ("cornell_box", dict(ray_bounce_limit=4, tone_mapping=0, gamma_correction=0)),
     "alpha_cutouts": ("uv_texture_test", dict(ray_bounce_limit=4)),
+    # a thin lens: every camera constant the ray list copies is live (disk_u != disk_v: the camera looks along -x)
+    "lens": ("cornell_box", dict(ray_bounce_limit=4), dict(camera=lambda cam: vars(cam).update(
+        defocus_angle=1.5, focus_dist=3.0, exposure=2.5, vfov_rad=float(np.float32(np.deg2rad(47.0)))))),
+    "odd_size": ("cornell_box", dict(ray_bounce_limit=4), dict(size=(61, 37))),      # 2 257 pixels: no multiple of 8, 64, 256, 1024
+    "hbm_scene": ("cs16_dust", dict(ray_bounce_limit=4)),                            # tree and triangles live in HBM
+    "materials": ("emissive_test", dict(ray_bounce_limit=4), dict(material=(1, 1, 2.5))),
+    # the ray buffers regrow, then are too large: 1, 8, 1 -- three calls the rule makes uniform whatever the pose (n = 1 is unknown;
+    # a budget of min_spp per pixel leaves no extra) -- and then the same with ragged counts: 16 regrows them again, 1
+    "growing": ("cornell_box", dict(ray_bounce_limit=4), dict(spp=(1, 8, 1, 16, 1), max_spp=32)),
 }
 
 
@@ -48,10 +58,12 @@ def scene(name):
     return _scenes[name][0]
 
 
-def camera(name):
+def camera(name, setup=None):
     _, pos, fwd, _ = SCENES[name]
     cam = drt.Camera(pos)
     cam.m_Forward_dir = np.array(fwd, np.float32)
+    if setup:
+        setup(cam)
     return cam
 
 
@@ -79,23 +91,28 @@ def uniform_accumulations(r, cam, sc, frames):
 
 
 def run(config):
-    """Three adaptive calls on one renderer, everything the tests look at read back once; and the uniform renderer's view of the
-    same frames from another one."""
+    """The config's adaptive calls on one renderer (three of SPP unless it says otherwise), everything the tests look at read back
+    once; and the uniform renderer's view of the same frames from another one."""
     if config not in _runs:
-        name, settings = CONFIGS[config]
-        sc, cam = scene(name), camera(name)
-        plain = renderer(settings)
-        accum_after = uniform_accumulations(plain, cam, sc, FRAMES)
-        samples = {k: plain.radiance(sc, plain.cameraRays(cam, W, H, k))[0, ..., :3].reshape(-1, 3) for k in range(1, FRAMES + 1)}
-        r = renderer(settings)
+        name, settings, own = (CONFIGS[config] + ({},))[:3]
+        w, h = own.get("size", (W, H))
+        spp, max_spp = own.get("spp", (SPP,) * CALLS), own.get("max_spp", MAX_SPP)
+        sc, cam = scene(name), camera(name, own.get("camera"))
+        plain, r = renderer(settings, w, h), renderer(settings, w, h)
+        if "material" in own:
+            plain.setMaterialModel(*own["material"])
+            r.setMaterialModel(*own["material"])
         steps = []
-        before = ar.empty_state(PX)
-        for _ in range(CALLS):
-            info = r.RenderAdaptive(cam, sc, spp=SPP, max_spp=MAX_SPP)
+        before = ar.empty_state(w * h)
+        for s in spp:
+            info = r.RenderAdaptive(cam, sc, spp=s, max_spp=max_spp)
             after, q, c = state_of(r)
-            steps.append(dict(before=before, after=after, q=q, c=c, info=info, image=r.GetRenderTargetImage().reshape(-1, 4)))
+            steps.append(dict(before=before, after=after, q=q, c=c, info=info, image=r.GetRenderTargetImage().reshape(-1, 4), spp=s))
             before = after
-        _runs[config] = dict(steps=steps, accum_after=accum_after, samples=samples)
+        frames = int(before.n.max())                   # (no pixel has received more samples than this)
+        accum_after = uniform_accumulations(plain, cam, sc, frames)
+        samples = {k: plain.radiance(sc, plain.cameraRays(cam, w, h, k))[0, ..., :3].reshape(-1, 3) for k in range(1, frames + 1)}
+        _runs[config] = dict(steps=steps, accum_after=accum_after, samples=samples, px=w * h, max_spp=max_spp, frames=len(spp) * max_spp)
     return _runs[config]
 
 
@@ -112,14 +129,14 @@ def assert_bits(got, ref, what):
 @pytest.mark.parametrize("config", list(CONFIGS))
 def test_a_pixel_with_n_samples_holds_the_uniform_accumulation_after_n_frames(config):
     d = run(config)
-    pixels = np.arange(PX)
+    pixels = np.arange(d["px"])
     for i, st in enumerate(d["steps"]):
         n = st["after"].n
-        assert n.max() <= FRAMES and st["info"].samples == int(st["c"].sum()) <= SPP * PX
+        assert n.max() <= d["frames"] and st["info"].samples == int(st["c"].sum()) <= st["spp"] * d["px"]
         assert_bits(st["after"].sum, d["accum_after"][n, pixels], "%s call %d: sum vs accumulation after n frames" % (config, i))
         assert_bits(st["image"], ar.image(st["after"]), "%s call %d: framebuffer vs sum / n" % (config, i))
     first, last = d["steps"][0], d["steps"][-1]
-    assert (first["c"] == SPP).all() and first["info"].max_count == SPP            # every pixel unknown: uniform
+    assert (first["c"] == first["spp"]).all() and first["info"].max_count == first["spp"]      # every pixel unknown: uniform
     assert len(np.unique(last["after"].n)) > 2, "the later calls must not be uniform: the test would show nothing"
 
 
@@ -129,7 +146,7 @@ def test_a_pixel_with_n_samples_holds_the_uniform_accumulation_after_n_frames(co
 def test_weights_counts_and_moments_equal_the_restatement(config):
     d = run(config)
     for i, st in enumerate(d["steps"]):
-        q, c = ar.plan(st["before"], SPP * PX, max_spp=MAX_SPP)
+        q, c = ar.plan(st["before"], st["spp"] * d["px"], max_spp=d["max_spp"])
         assert (st["q"] == q).all(), "%s call %d: %d weights differ" % (config, i, (st["q"] != q).sum())
         assert (st["c"] == c).all(), "%s call %d: %d counts differ" % (config, i, (st["c"] != c).sum())
         assert st["info"].active_pixels == int((q > 0).sum()) and st["info"].max_count == int(c.max())
