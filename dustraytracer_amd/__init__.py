@@ -325,6 +325,7 @@ _sig("drt_debug_check_rcp", C.c_int, C.c_int32, C.POINTER(C.c_uint64), C.POINTER
 _sig("drt_debug_check_sqrt", C.c_int, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
 _sig("drt_renderer_trace_rays", C.c_int, _P, _P, _P, _P, C.c_uint32, _P)
 _sig("drt_renderer_occluded", C.c_int, _P, _P, _P, _P, C.c_uint32, _P)
+_sig("drt_renderer_nearest", C.c_int, _P, _P, _P, _P, C.c_uint32, _P)
 _sig("drt_renderer_render_guides", C.c_int, _P, C.POINTER(_CameraPOD), _P, C.c_uint32, _P, _P)
 _sig("drt_default_denoise_params", None, C.POINTER(DenoiseParams))
 _sig("drt_renderer_denoise", C.c_int, _P, C.POINTER(_CameraPOD), _P, C.POINTER(DenoiseParams), C.POINTER(C.c_float))
@@ -600,6 +601,7 @@ class RendererGroup:
 
 FLT_MAX = float(np.finfo(np.float32).max)
 RayHits = collections.namedtuple("RayHits", "t prim u v")     # closest-hit query results (Renderer.traceRays)
+Nearest = collections.namedtuple("Nearest", "point d2 prim u v side")   # nearest-surface query results (Renderer.nearest)
 TemporalHistory = collections.namedtuple("TemporalHistory", "color length moments variance weight")  # Renderer.GetTemporalHistory
 Guides = collections.namedtuple("Guides", "albedo normal t prim")  # first-hit guide buffers (Renderer.renderGuides)
 AdaptiveState = collections.namedtuple("AdaptiveState", "sum count m1 m2 last_q last_count")  # Renderer.GetAdaptiveState
@@ -720,6 +722,61 @@ class Renderer:
         if directions is None and tmin == 0.0 and tmax == float("inf"):
             tmin = tmax = None
         return self._ray_query(scene, origins, directions, tmin, tmax, True)
+
+    def nearest(self, scene, points, max_dist=float("inf")):
+        """The closest point of the mesh for every point (drt_renderer_nearest): Nearest(point [N, 3], d2, prim, u, v, side), prim -1 =
+        nothing within max_dist (then point = 0, d2 = max_dist^2).  points [N, 3] float32 with max_dist a scalar or [N], or packed
+        [N, 4] (p, max_dist).  Device tensors in, device tensors out (enqueued on the current torch stream); numpy in, numpy out.
+        After refit(scene, positions) the moved geometry is the one queried."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+
+        def bad(msg):
+            return DrtError(ERR_INVALID, msg)
+
+        def as_tensor(a, what):
+            if isinstance(a, np.ndarray):
+                if a.dtype != np.float32:
+                    raise bad("%s: dtype %s, float32 expected" % (what, a.dtype))
+                return torch.from_numpy(np.ascontiguousarray(a))
+            if torch.is_tensor(a):
+                if a.dtype != torch.float32:
+                    raise bad("%s: dtype %s, torch.float32 expected" % (what, a.dtype))
+                if a.device != dev:
+                    raise bad("%s: on %s, the renderer is on %s" % (what, a.device, dev))
+                return a
+            raise bad("%s: a numpy array or a torch tensor expected" % what)
+
+        from_numpy = isinstance(points, np.ndarray)
+        pts = as_tensor(points, "points")
+        if pts.dim() != 2 or pts.shape[1] not in (3, 4):
+            raise bad("points: shape %s, [N, 3] or [N, 4] expected" % (tuple(pts.shape),))
+        n = pts.shape[0]
+        per_point = not isinstance(max_dist, (int, float, np.floating, np.integer))
+        if pts.shape[1] == 4:
+            if per_point or float(max_dist) != float("inf"):
+                raise bad("packed points carry their own max_dist")
+            packed = pts.to(dev) if from_numpy else pts
+            if not packed.is_contiguous() or packed.data_ptr() % 16:
+                packed = packed.contiguous().clone()
+        else:
+            if per_point:
+                if isinstance(max_dist, np.ndarray) != from_numpy:
+                    raise bad("mix of numpy arrays and device tensors")
+                md = as_tensor(max_dist, "max_dist")
+                if md.dim() != 1 or md.shape[0] != n:
+                    raise bad("max_dist: shape %s for %d points" % (tuple(md.shape), n))
+            packed = torch.empty((n, 4), dtype=torch.float32, device=dev)     # packed on the device, on the current stream
+            packed[:, 0:3] = pts.to(dev) if from_numpy else pts
+            packed[:, 3] = (md.to(dev) if from_numpy else md) if per_point else float(max_dist)
+        out = torch.empty((n, 8), dtype=torch.float32, device=dev)
+        if n:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(_lib.drt_renderer_nearest(self._h, scene._h, packed.data_ptr(), out.data_ptr(), n, stream))
+        if from_numpy:
+            h = out.cpu().numpy()
+            return Nearest(h[:, 0:3].copy(), h[:, 3].copy(), h.view(np.int32)[:, 4].copy(), h[:, 5].copy(), h[:, 6].copy(), h[:, 7].copy())
+        return Nearest(out[:, 0:3], out[:, 3], out.view(torch.int32)[:, 4], out[:, 5], out[:, 6], out[:, 7])
 
     def renderGuides(self, cam, scene, frame_index=1, as_torch=False):
         """First-hit guide buffers of frame `frame_index` (drt_renderer_render_guides): Guides(albedo [H, W, 3], normal [H, W, 3],

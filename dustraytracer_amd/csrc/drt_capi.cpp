@@ -14,6 +14,7 @@
 #include <stdexcept>
 
 #include "ray_query.hpp"
+#include "nearest.hpp"
 #include "bvh_build_device.hpp"
 #include "png_decode.hpp"
 
@@ -817,6 +818,33 @@ int drt_renderer_trace_rays(drt_renderer *r, const drt_scene *scene, const drt_r
 
 int drt_renderer_occluded(drt_renderer *r, const drt_scene *scene, const drt_ray *rays, uint8_t *occluded, uint32_t n, void *hip_stream) {
     return ray_query_impl(r, scene, rays, occluded, n, hip_stream, true);
+}
+
+// ------------------------------------------------------------------ nearest-surface queries (kernel_nearest.hip)
+// Validated, ordered and given scratch as the ray queries are: the kernel shares their claim heads and the closest-hit HBM stack.
+int drt_renderer_nearest(drt_renderer *r, const drt_scene *scene, const drt_point *points, drt_nearest *out, uint32_t n, void *hip_stream) {
+    if (!r || !scene) return fail(DRT_ERR_INVALID, "null argument");
+    if (n == 0) return DRT_OK;
+    if (!points || !out) return fail(DRT_ERR_INVALID, "null point or result pointer");
+    if (((uintptr_t)points & 15u) != 0 || ((uintptr_t)out & 15u) != 0) return fail(DRT_ERR_INVALID, "points and results must be 16-byte aligned");
+    if (n > 0x7fffffffu) return fail(DRT_ERR_INVALID, "at most 2^31 - 1 points per call");
+    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
+    HIP_TRY(hipSetDevice(r->device));
+    (void)hipGetLastError();                   // (see render_batch_impl: only this call's own errors count)
+    if (!on_renderer_device(r, points) || !on_renderer_device(r, out))
+        return fail(DRT_ERR_INVALID, "points and results must be device memory on the renderer's device");
+    if (int rc = upload_scene(r, scene)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : r->stream;
+    if (int rc = query_order(r, s)) return rc;
+    if (int rc = traversal_scratch(r, s, false, true)) return rc;
+    NearestArgs a;
+    a.points = points; a.out = out; a.n = n;
+    a.stack_levels = (uint32_t)std::max(1, r->bvh_depth);
+    a.refill_min = (uint32_t)r->rq_refill_min;
+    a.heads = r->rq_heads.ptr;
+    a.stack_hbm = r->rq_stack.ptr;
+    HIP_TRY(launch_nearest(r->view, a, r->num_cus, s));
+    return query_recorded(r, s);
 }
 
 // ------------------------------------------------------------------ camera rays and radiance queries (kernel_radiance.hip)

@@ -290,6 +290,11 @@ public:
     void Occluded(const Scene &scene, const drt_ray *rays, uint8_t *occluded, uint32_t n, void *stream = nullptr) {
         drt::check(drt_renderer_occluded(handle, scene.handle, rays, occluded, n, stream));
     }
+    // new: the closest point of the mesh for each of n points (drt_renderer_nearest: device arrays, enqueued on `stream`); after
+    // Refit the moved geometry is the one queried
+    void Nearest(const Scene &scene, const drt_point *points, drt_nearest *out, uint32_t n, void *stream = nullptr) {
+        drt::check(drt_renderer_nearest(handle, scene.handle, points, out, n, stream));
+    }
     // new: RayGen's primary rays of n_cams cameras for a width x height image, frame `frame_index` (drt_renderer_camera_rays): a device
     // drt_path_ray[n_cams * width * height], enqueued on `stream`
     void CameraRays(const drt_camera *cams, uint32_t n_cams, uint32_t width, uint32_t height, uint32_t frame_index, drt_path_ray *rays,

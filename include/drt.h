@@ -27,7 +27,8 @@ extern "C" {
 
 /* 2: drt_counters grew by sampler_tries; drt_group_* and drt_material_model entry points (round 2) are part of it; the ray-query
  * entry points (drt_renderer_trace_rays / _occluded), the guide / denoise entry points, the refit entry points and the camera-ray /
- * radiance entry points, the upscaling entry points and the adaptive-sampling entry points are additions to it */
+ * radiance entry points, the upscaling entry points, the adaptive-sampling entry points and the nearest-surface entry point
+ * (drt_renderer_nearest) are additions to it */
 #define DRT_ABI_VERSION 2
 
 typedef enum {
@@ -245,6 +246,46 @@ typedef struct drt_ray { float org[3]; float tmin; float dir[3]; float tmax; } d
 typedef struct drt_hit { float t; int32_t prim; float u, v; } drt_hit;                      /* 16 B */
 int           drt_renderer_trace_rays(drt_renderer *r, const drt_scene *scene, const drt_ray *rays, drt_hit *hits, uint32_t n, void *hip_stream);
 int           drt_renderer_occluded(drt_renderer *r, const drt_scene *scene, const drt_ray *rays, uint8_t *occluded, uint32_t n, void *hip_stream);
+
+/* ---- nearest-surface queries (new; the reference asks the scene about rays only) ----
+ * One query = a point p and a search radius max_dist; the answer is the closest point of the mesh within that radius.
+ * All arithmetic is fp32 with one rounding per operation, in the order written; dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z, / is the
+ * correctly rounded division.
+ * Per triangle k: (v0, e1 = v1 - v0, e2 = v2 - v0) as the ray test reads them (the stored edges; v1, v2 are not recomputed).  The
+ * closest point follows Ericson, Real-Time Collision Detection 5.1.5:
+ *   ap = p - v0, d1 = dot(e1, ap), d2 = dot(e2, ap);  bp = ap - e1, d3 = dot(e1, bp), d4 = dot(e2, bp);
+ *   cp = ap - e2, d5 = dot(e1, cp), d6 = dot(e2, cp);  vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6, va = d3 d6 - d5 d4.
+ * The first case that matches, in this order, gives (u, v):
+ *   1. d1 <= 0 && d2 <= 0                         (0, 0)
+ *   2. d3 >= 0 && d4 <= d3                        (1, 0)
+ *   3. vc <= 0 && d1 >= 0 && d3 <= 0              (d1 / (d1 - d3), 0)
+ *   4. d6 >= 0 && d5 <= d6                        (0, 1)
+ *   5. vb <= 0 && d2 >= 0 && d6 <= 0              (0, d2 / (d2 - d6))
+ *   6. va <= 0 && d4 - d3 >= 0 && d5 - d6 >= 0    w = (d4 - d3) / ((d4 - d3) + (d5 - d6)): (1 - w, w)
+ *   7. otherwise                                  den = 1 / ((va + vb) + vc): (vb den, vc den)
+ * Then c = (v0 + e1 u) + e2 v, diff = p - c, dist2 = dot(diff, diff).  A NaN dist2 (a NaN query; a zero-area triangle whose matching
+ * case divides 0 by 0, such as case 3 when v0 = v1) never wins: every comparison below is a strict <.  A zero-area triangle whose
+ * matching case has a quotient (v1 = v2, three collinear vertices) counts as the segment or point it is.
+ * Box distance: per axis d = fmaxf(fmaxf(bmin - p, 0), p - bmax) (a NaN operand is dropped), box2 = (dx dx + dy dy) + dz dz.
+ * Traversal: best = max_dist * max_dist, prim = -1.  The root is pushed with its box2.  A popped entry is dropped unless
+ * box2 < best.  A leaf tests its triangles in order; a candidate replaces the result iff dist2 < best (the first one found wins a
+ * tie).  An interior node computes box2 of both children and pushes a child iff its box2 < best, the farther one first
+ * (b1 > b2 -> child 1), so the nearer one is popped first: drt_renderer_trace_rays' stack discipline with box2 in place of the entry
+ * distance.
+ * Result: on a hit drt_nearest {c, dist2, prim, u, v, side}, prim = triangle index in drt_scene_get_triangles order,
+ * side = dot(p - c, fn) < 0 ? -1 : 1 with fn the stored face normal; on a miss (nothing within max_dist, NaN input)
+ * {0, 0, 0, max_dist * max_dist, -1, 0, 0, 0}.  A result depends on its point and the scene only.
+ * What this is not: alpha cut-outs are ignored (a geometric query).  `side` is the side of the nearest triangle's plane, not an
+ * inside / outside classification: at an edge or vertex of a non-convex mesh it can disagree with a parity test (a robust sign --
+ * pseudonormals, ray parity -- is out of scope, as are k-nearest and radius-gather queries).
+ * Conventions are drt_renderer_trace_rays': device pointers on the renderer's device, 16-byte aligned, n < 2^31, n == 0 is a no-op,
+ * hip_stream NULL = the renderer's stream, the call only enqueues, in order with the other queries (the same event), the scene is
+ * uploaded as for rendering and a refitted device copy (drt_renderer_refit) is the one queried.  Legal on a sharded renderer.  The
+ * framebuffer, accumulation, sample count, counters, kernel info and kernel span are not touched.  Errors as for the ray queries,
+ * DRT_ERR_UNSUPPORTED beyond 64 levels and DRT_ERR_INVALID while an asynchronous batch is pending included. */
+typedef struct drt_point   { float p[3]; float max_dist; } drt_point;                                    /* 16 B */
+typedef struct drt_nearest { float point[3]; float d2; int32_t prim; float u, v, side; } drt_nearest;   /* 32 B */
+int           drt_renderer_nearest(drt_renderer *r, const drt_scene *scene, const drt_point *points, drt_nearest *out, uint32_t n, void *hip_stream);
 
 /* ---- first-hit guide buffers and the a-trous denoiser (new; the reference's TODO list, RayGen.cuh:13-21, starts with "DLSS 3.5
  * like features") ----
