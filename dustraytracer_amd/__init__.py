@@ -326,6 +326,9 @@ _sig("drt_debug_check_sqrt", C.c_int, C.c_int32, C.POINTER(C.c_uint64), C.POINTE
 _sig("drt_renderer_trace_rays", C.c_int, _P, _P, _P, _P, C.c_uint32, _P)
 _sig("drt_renderer_occluded", C.c_int, _P, _P, _P, _P, C.c_uint32, _P)
 _sig("drt_renderer_nearest", C.c_int, _P, _P, _P, _P, C.c_uint32, _P)
+_sig("drt_renderer_crossings", C.c_int, _P, _P, _P, _P, C.c_uint32, _P)
+_sig("drt_renderer_inside", C.c_int, _P, _P, _P, _P, C.c_uint32, C.c_int32, _P)
+_sig("drt_renderer_signed_distance", C.c_int, _P, _P, _P, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_renderer_render_guides", C.c_int, _P, C.POINTER(_CameraPOD), _P, C.c_uint32, _P, _P)
 _sig("drt_default_denoise_params", None, C.POINTER(DenoiseParams))
 _sig("drt_renderer_denoise", C.c_int, _P, C.POINTER(_CameraPOD), _P, C.POINTER(DenoiseParams), C.POINTER(C.c_float))
@@ -602,6 +605,8 @@ class RendererGroup:
 FLT_MAX = float(np.finfo(np.float32).max)
 RayHits = collections.namedtuple("RayHits", "t prim u v")     # closest-hit query results (Renderer.traceRays)
 Nearest = collections.namedtuple("Nearest", "point d2 prim u v side")   # nearest-surface query results (Renderer.nearest)
+Crossings = collections.namedtuple("Crossings", "count winding")       # crossing counts of rays (Renderer.crossings)
+INSIDE_RULES = {"parity": 0, "winding": 1}                              # Renderer.inside / signedDistance: drt.h DRT_INSIDE_*
 TemporalHistory = collections.namedtuple("TemporalHistory", "color length moments variance weight")  # Renderer.GetTemporalHistory
 Guides = collections.namedtuple("Guides", "albedo normal t prim")  # first-hit guide buffers (Renderer.renderGuides)
 AdaptiveState = collections.namedtuple("AdaptiveState", "sum count m1 m2 last_q last_count")  # Renderer.GetAdaptiveState
@@ -671,6 +676,50 @@ def _ray_batch(torch, dev, origins, directions, tmin, tmax):
     return rays, from_numpy
 
 
+def _point_batch(torch, dev, points, max_dist):
+    """(points [N, 4] float32 (p, max_dist) on `dev`, 16-byte aligned, came_from_numpy).  Raises DrtError(ERR_INVALID) on a wrong
+    dtype, shape or device."""
+    def bad(msg):
+        return DrtError(ERR_INVALID, msg)
+
+    def as_tensor(a, what):
+        if isinstance(a, np.ndarray):
+            if a.dtype != np.float32:
+                raise bad("%s: dtype %s, float32 expected" % (what, a.dtype))
+            return torch.from_numpy(np.ascontiguousarray(a))
+        if torch.is_tensor(a):
+            if a.dtype != torch.float32:
+                raise bad("%s: dtype %s, torch.float32 expected" % (what, a.dtype))
+            if a.device != dev:
+                raise bad("%s: on %s, the renderer is on %s" % (what, a.device, dev))
+            return a
+        raise bad("%s: a numpy array or a torch tensor expected" % what)
+
+    from_numpy = isinstance(points, np.ndarray)
+    pts = as_tensor(points, "points")
+    if pts.dim() != 2 or pts.shape[1] not in (3, 4):
+        raise bad("points: shape %s, [N, 3] or [N, 4] expected" % (tuple(pts.shape),))
+    n = pts.shape[0]
+    per_point = not isinstance(max_dist, (int, float, np.floating, np.integer))
+    if pts.shape[1] == 4:
+        if per_point or float(max_dist) != float("inf"):
+            raise bad("packed points carry their own max_dist")
+        packed = pts.to(dev) if from_numpy else pts
+        if not packed.is_contiguous() or packed.data_ptr() % 16:
+            packed = packed.contiguous().clone()
+    else:
+        if per_point:
+            if isinstance(max_dist, np.ndarray) != from_numpy:
+                raise bad("mix of numpy arrays and device tensors")
+            md = as_tensor(max_dist, "max_dist")
+            if md.dim() != 1 or md.shape[0] != n:
+                raise bad("max_dist: shape %s for %d points" % (tuple(md.shape), n))
+        packed = torch.empty((n, 4), dtype=torch.float32, device=dev)     # packed on the device, on the current stream
+        packed[:, 0:3] = pts.to(dev) if from_numpy else pts
+        packed[:, 3] = (md.to(dev) if from_numpy else md) if per_point else float(max_dist)
+    return packed, from_numpy
+
+
 class Renderer:
     """Core/Renderer.hpp:14-47."""
 
@@ -730,45 +779,8 @@ class Renderer:
         After refit(scene, positions) the moved geometry is the one queried."""
         import torch                             # (only here: importing the package does not import torch)
         dev = torch.device("cuda", self._device)
-
-        def bad(msg):
-            return DrtError(ERR_INVALID, msg)
-
-        def as_tensor(a, what):
-            if isinstance(a, np.ndarray):
-                if a.dtype != np.float32:
-                    raise bad("%s: dtype %s, float32 expected" % (what, a.dtype))
-                return torch.from_numpy(np.ascontiguousarray(a))
-            if torch.is_tensor(a):
-                if a.dtype != torch.float32:
-                    raise bad("%s: dtype %s, torch.float32 expected" % (what, a.dtype))
-                if a.device != dev:
-                    raise bad("%s: on %s, the renderer is on %s" % (what, a.device, dev))
-                return a
-            raise bad("%s: a numpy array or a torch tensor expected" % what)
-
-        from_numpy = isinstance(points, np.ndarray)
-        pts = as_tensor(points, "points")
-        if pts.dim() != 2 or pts.shape[1] not in (3, 4):
-            raise bad("points: shape %s, [N, 3] or [N, 4] expected" % (tuple(pts.shape),))
-        n = pts.shape[0]
-        per_point = not isinstance(max_dist, (int, float, np.floating, np.integer))
-        if pts.shape[1] == 4:
-            if per_point or float(max_dist) != float("inf"):
-                raise bad("packed points carry their own max_dist")
-            packed = pts.to(dev) if from_numpy else pts
-            if not packed.is_contiguous() or packed.data_ptr() % 16:
-                packed = packed.contiguous().clone()
-        else:
-            if per_point:
-                if isinstance(max_dist, np.ndarray) != from_numpy:
-                    raise bad("mix of numpy arrays and device tensors")
-                md = as_tensor(max_dist, "max_dist")
-                if md.dim() != 1 or md.shape[0] != n:
-                    raise bad("max_dist: shape %s for %d points" % (tuple(md.shape), n))
-            packed = torch.empty((n, 4), dtype=torch.float32, device=dev)     # packed on the device, on the current stream
-            packed[:, 0:3] = pts.to(dev) if from_numpy else pts
-            packed[:, 3] = (md.to(dev) if from_numpy else md) if per_point else float(max_dist)
+        packed, from_numpy = _point_batch(torch, dev, points, max_dist)
+        n = packed.shape[0]
         out = torch.empty((n, 8), dtype=torch.float32, device=dev)
         if n:
             stream = torch.cuda.current_stream(dev).cuda_stream
@@ -777,6 +789,86 @@ class Renderer:
             h = out.cpu().numpy()
             return Nearest(h[:, 0:3].copy(), h[:, 3].copy(), h.view(np.int32)[:, 4].copy(), h[:, 5].copy(), h[:, 6].copy(), h[:, 7].copy())
         return Nearest(out[:, 0:3], out[:, 3], out.view(torch.int32)[:, 4], out[:, 5], out[:, 6], out[:, 7])
+
+    def crossings(self, scene, origins, directions=None, tmin=0.0, tmax=float("inf")):
+        """Every triangle each ray passes through within (tmin, tmax) (drt_renderer_crossings): Crossings(count uint32 [N], winding
+        int32 [N]), winding = exits minus entries by the triangles' own winding.  Alpha cut-outs are ignored.  Arguments as traceRays."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        if directions is None and tmin == 0.0 and tmax == float("inf"):
+            tmin = tmax = None
+        rays, from_numpy = _ray_batch(torch, dev, origins, directions, tmin, tmax)
+        n = rays.shape[0]
+        out = torch.empty((n, 2), dtype=torch.int32, device=dev)
+        if n:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(_lib.drt_renderer_crossings(self._h, scene._h, rays.data_ptr(), out.data_ptr(), n, stream))
+        if from_numpy:
+            h = out.cpu().numpy()
+            return Crossings(h[:, 0].copy().view(np.uint32), h[:, 1].copy())
+        return Crossings(out[:, 0], out[:, 1])       # (torch has no uint32 arithmetic: count is an int32 tensor, < 2^31 triangles)
+
+    @staticmethod
+    def _inside_rule(rule):
+        if rule not in INSIDE_RULES:
+            raise DrtError(ERR_INVALID, "rule %r: 'parity' or 'winding' expected" % (rule,))
+        return INSIDE_RULES[rule]
+
+    def inside(self, scene, points, rule="parity", votes=False):
+        """Whether each point lies inside the closed mesh (drt_renderer_inside): three fixed rays per point vote by the parity of
+        their crossing count (rule="parity") or by their winding sum (rule="winding", which needs consistent orientation as well);
+        bool [N], inside = two votes or more, or with votes=True the uint8 number of votes, 0..3.  points [N, 3] float32 (or packed
+        [N, 4]; max_dist is ignored).  Device tensors in, device tensors out (enqueued on the current torch stream); numpy in, numpy
+        out.  After refit(scene, positions) the moved geometry is the one queried.  A point on the surface has no defined answer."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        rule = self._inside_rule(rule)
+        packed, from_numpy = _point_batch(torch, dev, points, float("inf"))
+        n = packed.shape[0]
+        out = torch.empty(n, dtype=torch.uint8, device=dev)
+        if n:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(_lib.drt_renderer_inside(self._h, scene._h, packed.data_ptr(), out.data_ptr(), n, rule, stream))
+        res = out if votes else out >= 2
+        return res.cpu().numpy() if from_numpy else res
+
+    def signedDistance(self, scene, points, max_dist=float("inf"), rule="parity"):
+        """nearest(scene, points, max_dist) with side = -1 inside the closed mesh, +1 outside, by inside()'s vote
+        (drt_renderer_signed_distance); miss records carry the sign too.  The signed distance is side * sqrt(d2)."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        rule = self._inside_rule(rule)
+        packed, from_numpy = _point_batch(torch, dev, points, max_dist)
+        n = packed.shape[0]
+        out = torch.empty((n, 8), dtype=torch.float32, device=dev)
+        if n:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(_lib.drt_renderer_signed_distance(self._h, scene._h, packed.data_ptr(), out.data_ptr(), n, rule, stream))
+        if from_numpy:
+            h = out.cpu().numpy()
+            return Nearest(h[:, 0:3].copy(), h[:, 3].copy(), h.view(np.int32)[:, 4].copy(), h[:, 5].copy(), h[:, 6].copy(), h[:, 7].copy())
+        return Nearest(out[:, 0:3], out[:, 3], out.view(torch.int32)[:, 4], out[:, 5], out[:, 6], out[:, 7])
+
+    def sdfGrid(self, scene, resolution, lo=None, hi=None, rule="parity"):
+        """A signed distance field: float32 [Z, Y, X] device tensor of side * sqrt(d2) at the cell centres of a grid over the box
+        (lo, hi), by default the scene's bounds.  resolution: an int or (X, Y, Z).  The points are made on the device."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        self._inside_rule(rule)
+        res = (int(resolution),) * 3 if isinstance(resolution, (int, np.integer)) else tuple(int(v) for v in resolution)
+        if len(res) != 3 or min(res) < 1:
+            raise DrtError(ERR_INVALID, "resolution: a positive int or three of them expected")
+        if lo is None or hi is None:
+            nodes = scene.m_BVHNodes
+            if len(nodes) == 0:
+                raise DrtError(ERR_INVALID, "sdfGrid: an empty scene has no bounds; give lo and hi")
+            lo = nodes[-1]["bmin"] if lo is None else lo                      # the root is the last node
+            hi = nodes[-1]["bmax"] if hi is None else hi
+        lo, hi = np.asarray(lo, np.float32).reshape(3), np.asarray(hi, np.float32).reshape(3)
+        axes = [float(lo[k]) + (torch.arange(res[k], dtype=torch.float32, device=dev) + 0.5) * (float(hi[k] - lo[k]) / res[k]) for k in range(3)]
+        z, y, x = torch.meshgrid(axes[2], axes[1], axes[0], indexing="ij")
+        near = self.signedDistance(scene, torch.stack([x, y, z], dim=-1).reshape(-1, 3), rule=rule)
+        return (near.side * torch.sqrt(near.d2)).reshape(res[2], res[1], res[0])
 
     def renderGuides(self, cam, scene, frame_index=1, as_torch=False):
         """First-hit guide buffers of frame `frame_index` (drt_renderer_render_guides): Guides(albedo [H, W, 3], normal [H, W, 3],

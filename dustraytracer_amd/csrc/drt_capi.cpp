@@ -15,6 +15,7 @@
 
 #include "ray_query.hpp"
 #include "nearest.hpp"
+#include "crossings.hpp"
 #include "bvh_build_device.hpp"
 #include "png_decode.hpp"
 
@@ -845,6 +846,58 @@ int drt_renderer_nearest(drt_renderer *r, const drt_scene *scene, const drt_poin
     a.stack_hbm = r->rq_stack.ptr;
     HIP_TRY(launch_nearest(r->view, a, r->num_cus, s));
     return query_recorded(r, s);
+}
+
+// ------------------------------------------------------------------ crossing counts, inside votes, signed distance (kernel_crossings.hip)
+// Validated, ordered and given scratch as the ray queries are: the kernel shares their claim heads and the occlusion query's HBM stack.
+static int bad_rule(int32_t rule) {
+    return fail(DRT_ERR_INVALID, "rule " + std::to_string(rule) + ": 0 (parity) or 1 (winding) expected");
+}
+
+// in: rays or points (16-byte aligned); out: what `kind` says, aligned to out_align bytes
+static int crossings_impl(drt_renderer *r, const drt_scene *scene, const void *in, void *out, size_t out_align, uint32_t n, int32_t rule,
+                          void *hip_stream, drt::CrossingsOut kind) {
+    if (!r || !scene) return fail(DRT_ERR_INVALID, "null argument");
+    if (n == 0) return DRT_OK;
+    if (!in || !out) return fail(DRT_ERR_INVALID, "null query or result pointer");
+    if (((uintptr_t)in & 15u) != 0 || ((uintptr_t)out & (out_align - 1)) != 0)
+        return fail(DRT_ERR_INVALID, "queries must be 16-byte aligned, results " + std::to_string(out_align) + "-byte aligned");
+    if (n > 0x7fffffffu) return fail(DRT_ERR_INVALID, "at most 2^31 - 1 queries per call");
+    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
+    HIP_TRY(hipSetDevice(r->device));
+    (void)hipGetLastError();                   // (see render_batch_impl: only this call's own errors count)
+    if (!on_renderer_device(r, in) || !on_renderer_device(r, out))
+        return fail(DRT_ERR_INVALID, "queries and results must be device memory on the renderer's device");
+    if (int rc = upload_scene(r, scene)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : r->stream;
+    if (int rc = query_order(r, s)) return rc;
+    if (int rc = traversal_scratch(r, s, true, true)) return rc;
+    CrossingsArgs a;
+    a.in = in; a.out = out; a.n = n;
+    a.stack_levels = (uint32_t)std::max(1, r->bvh_depth);
+    a.refill_min = (uint32_t)r->rq_refill_min;
+    a.rule = (uint32_t)rule;
+    a.heads = r->rq_heads.ptr;
+    a.stack_hbm = r->rq_stack.ptr;
+    HIP_TRY(launch_crossings(r->view, kind, a, r->num_cus, s));
+    return query_recorded(r, s);
+}
+
+int drt_renderer_crossings(drt_renderer *r, const drt_scene *scene, const drt_ray *rays, drt_crossings *out, uint32_t n, void *hip_stream) {
+    return crossings_impl(r, scene, rays, out, 8, n, 0, hip_stream, drt::CrossingsOut::crossings);
+}
+
+int drt_renderer_inside(drt_renderer *r, const drt_scene *scene, const drt_point *points, uint8_t *votes, uint32_t n, int32_t rule, void *hip_stream) {
+    if (rule != 0 && rule != 1) return bad_rule(rule);
+    return crossings_impl(r, scene, points, votes, 1, n, rule, hip_stream, drt::CrossingsOut::votes);
+}
+
+// The nearest kernel writes the records, then the point-mode kernel replaces their `side` words: two launches on one stream.
+int drt_renderer_signed_distance(drt_renderer *r, const drt_scene *scene, const drt_point *points, drt_nearest *out, uint32_t n, int32_t rule,
+                                 void *hip_stream) {
+    if (rule != 0 && rule != 1) return bad_rule(rule);
+    if (int rc = drt_renderer_nearest(r, scene, points, out, n, hip_stream)) return rc;
+    return crossings_impl(r, scene, points, out, 16, n, rule, hip_stream, drt::CrossingsOut::side);
 }
 
 // ------------------------------------------------------------------ camera rays and radiance queries (kernel_radiance.hip)

@@ -295,6 +295,19 @@ public:
     void Nearest(const Scene &scene, const drt_point *points, drt_nearest *out, uint32_t n, void *stream = nullptr) {
         drt::check(drt_renderer_nearest(handle, scene.handle, points, out, n, stream));
     }
+    // new: every triangle each ray passes through (drt_renderer_crossings), the inside vote of each point, 0..3 with 2 or more =
+    // inside (drt_renderer_inside), and Nearest's records with side = -1 inside / +1 outside (drt_renderer_signed_distance);
+    // rule = DRT_INSIDE_PARITY or DRT_INSIDE_WINDING.  Device arrays, enqueued on `stream`.
+    void Crossings(const Scene &scene, const drt_ray *rays, drt_crossings *out, uint32_t n, void *stream = nullptr) {
+        drt::check(drt_renderer_crossings(handle, scene.handle, rays, out, n, stream));
+    }
+    void Inside(const Scene &scene, const drt_point *points, uint8_t *votes, uint32_t n, int32_t rule = DRT_INSIDE_PARITY, void *stream = nullptr) {
+        drt::check(drt_renderer_inside(handle, scene.handle, points, votes, n, rule, stream));
+    }
+    void SignedDistance(const Scene &scene, const drt_point *points, drt_nearest *out, uint32_t n, int32_t rule = DRT_INSIDE_PARITY,
+                        void *stream = nullptr) {
+        drt::check(drt_renderer_signed_distance(handle, scene.handle, points, out, n, rule, stream));
+    }
     // new: RayGen's primary rays of n_cams cameras for a width x height image, frame `frame_index` (drt_renderer_camera_rays): a device
     // drt_path_ray[n_cams * width * height], enqueued on `stream`
     void CameraRays(const drt_camera *cams, uint32_t n_cams, uint32_t width, uint32_t height, uint32_t frame_index, drt_path_ray *rays,

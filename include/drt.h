@@ -27,8 +27,8 @@ extern "C" {
 
 /* 2: drt_counters grew by sampler_tries; drt_group_* and drt_material_model entry points (round 2) are part of it; the ray-query
  * entry points (drt_renderer_trace_rays / _occluded), the guide / denoise entry points, the refit entry points and the camera-ray /
- * radiance entry points, the upscaling entry points, the adaptive-sampling entry points and the nearest-surface entry point
- * (drt_renderer_nearest) are additions to it */
+ * radiance entry points, the upscaling entry points, the adaptive-sampling entry points, the nearest-surface entry point
+ * (drt_renderer_nearest) and the crossing-count entry points (drt_renderer_crossings / _inside / _signed_distance) are additions to it */
 #define DRT_ABI_VERSION 2
 
 typedef enum {
@@ -282,10 +282,44 @@ int           drt_renderer_occluded(drt_renderer *r, const drt_scene *scene, con
  * hip_stream NULL = the renderer's stream, the call only enqueues, in order with the other queries (the same event), the scene is
  * uploaded as for rendering and a refitted device copy (drt_renderer_refit) is the one queried.  Legal on a sharded renderer.  The
  * framebuffer, accumulation, sample count, counters, kernel info and kernel span are not touched.  Errors as for the ray queries,
- * DRT_ERR_UNSUPPORTED beyond 64 levels and DRT_ERR_INVALID while an asynchronous batch is pending included. */
+ * DRT_ERR_UNSUPPORTED beyond 64 levels and DRT_ERR_INVALID while an asynchronous batch is pending included.
+ * (The sign that `side` is not: drt_renderer_inside and drt_renderer_signed_distance, below.) */
 typedef struct drt_point   { float p[3]; float max_dist; } drt_point;                                    /* 16 B */
 typedef struct drt_nearest { float point[3]; float d2; int32_t prim; float u, v, side; } drt_nearest;   /* 32 B */
 int           drt_renderer_nearest(drt_renderer *r, const drt_scene *scene, const drt_point *points, drt_nearest *out, uint32_t n, void *hip_stream);
+
+/* ---- crossing counts, inside / outside and signed distance (new; the sign that drt_renderer_nearest leaves open) ----
+ * Crossings of a ray (a drt_ray, read as drt_renderer_trace_rays reads it: dir as given, inv_dir = 1/dir): the triangles it passes
+ * through, all of them.  The triangle test is the renderer's (Intersection.cu, the arithmetic of the ray queries) on the stored
+ * (v0, e1, e2), with det = dot(e1, cross(dir, e2)).  A triangle counts iff the test hits, t > tmin and t < tmax.  Alpha cut-outs are
+ * ignored (a geometric query, as drt_renderer_nearest is).  Per ray, count = the number of counted triangles and winding = the sum
+ * over them of (det < 0 ? +1 : -1): exits minus entries by the triangle's own winding e1 x e2, not by the stored face normal.
+ * Traversal is drt_renderer_occluded's without the early exit: the root is skipped if d < 0 || d > tmax, a child is pushed iff
+ * d >= 0 && !(d > tmax), the farther child is pushed first, the same stack bound applies.  Each triangle lies in one leaf, so the
+ * result does not depend on the traversal order.  Result: drt_crossings {count, winding}, 8 bytes; an empty scene or a NaN ray gives
+ * {0, 0}.  (The boxes cull as they do for the ray queries: a triangle whose box the fp32 slab test misses is not counted.)
+ * Inside vote of a point: three rays are cast from p with tmin = 0, tmax = +inf and the fixed fp32 directions
+ *   D0 = (0.6180340f, 0.4142136f, 0.6687403f)   D1 = (-0.7320508f, 0.2360680f, 0.6403124f)   D2 = (0.3166248f, -0.8660254f, 0.3872983f)
+ * used as given, not normalised; no component is zero, so the slab test's 0 * inf case cannot arise.  Ray j votes inside iff count_j
+ * is odd (rule 0, parity) or winding_j != 0 (rule 1, winding).  The answer is one byte per point: the number of rays voting
+ * inside, 0..3; inside means 2 or more.  drt_point's max_dist is ignored.
+ * Signed distance: drt_renderer_nearest's record for the point, unchanged in its first seven words; the last word, side, is
+ * replaced by -1 (inside) or +1 (outside) from the vote, in miss records too.
+ * What this is not: a point on the surface has no defined answer (t > 1e-6 decides, per ray); parity assumes a closed mesh; winding
+ * assumes consistent orientation as well.  Angle-weighted pseudonormals, generalised winding numbers for open meshes and an ordered
+ * list of the first K hits per ray are out of scope.
+ * Conventions and errors are drt_renderer_nearest's: device pointers on the renderer's device, rays / points / drt_nearest records
+ * 16-byte aligned, drt_crossings 8-byte aligned, n < 2^31, n == 0 is a no-op, hip_stream NULL = the renderer's stream, the call only
+ * enqueues, in order with the other queries, a refitted device copy is the one queried, legal on a sharded renderer,
+ * DRT_ERR_UNSUPPORTED beyond 64 levels, DRT_ERR_INVALID while an asynchronous batch is pending and for a rule other than 0 or 1
+ * (checked first).  drt_renderer_signed_distance enqueues the nearest query and then the vote on the same stream.  The framebuffer,
+ * accumulation, sample count, counters, kernel info and kernel span are not touched. */
+typedef struct drt_crossings { uint32_t count; int32_t winding; } drt_crossings;                         /* 8 B */
+#define DRT_INSIDE_PARITY  0
+#define DRT_INSIDE_WINDING 1
+int           drt_renderer_crossings(drt_renderer *r, const drt_scene *scene, const drt_ray *rays, drt_crossings *out, uint32_t n, void *hip_stream);
+int           drt_renderer_inside(drt_renderer *r, const drt_scene *scene, const drt_point *points, uint8_t *votes, uint32_t n, int32_t rule, void *hip_stream);
+int           drt_renderer_signed_distance(drt_renderer *r, const drt_scene *scene, const drt_point *points, drt_nearest *out, uint32_t n, int32_t rule, void *hip_stream);
 
 /* ---- first-hit guide buffers and the a-trous denoiser (new; the reference's TODO list, RayGen.cuh:13-21, starts with "DLSS 3.5
  * like features") ----
