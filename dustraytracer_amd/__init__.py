@@ -327,6 +327,7 @@ _sig("drt_renderer_trace_rays", C.c_int, _P, _P, _P, _P, C.c_uint32, _P)
 _sig("drt_renderer_occluded", C.c_int, _P, _P, _P, _P, C.c_uint32, _P)
 _sig("drt_renderer_nearest", C.c_int, _P, _P, _P, _P, C.c_uint32, _P)
 _sig("drt_renderer_crossings", C.c_int, _P, _P, _P, _P, C.c_uint32, _P)
+_sig("drt_renderer_list_hits", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P)
 _sig("drt_renderer_inside", C.c_int, _P, _P, _P, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_renderer_signed_distance", C.c_int, _P, _P, _P, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_renderer_render_guides", C.c_int, _P, C.POINTER(_CameraPOD), _P, C.c_uint32, _P, _P)
@@ -606,6 +607,8 @@ FLT_MAX = float(np.finfo(np.float32).max)
 RayHits = collections.namedtuple("RayHits", "t prim u v")     # closest-hit query results (Renderer.traceRays)
 Nearest = collections.namedtuple("Nearest", "point d2 prim u v side")   # nearest-surface query results (Renderer.nearest)
 Crossings = collections.namedtuple("Crossings", "count winding")       # crossing counts of rays (Renderer.crossings)
+FirstHits = collections.namedtuple("FirstHits", "t prim u v count")     # the first k hits of rays, in order (Renderer.firstHits)
+HitList = collections.namedtuple("HitList", "splits t prim u v")        # every hit of rays, in order, CSR (Renderer.listHits)
 INSIDE_RULES = {"parity": 0, "winding": 1}                              # Renderer.inside / signedDistance: drt.h DRT_INSIDE_*
 TemporalHistory = collections.namedtuple("TemporalHistory", "color length moments variance weight")  # Renderer.GetTemporalHistory
 Guides = collections.namedtuple("Guides", "albedo normal t prim")  # first-hit guide buffers (Renderer.renderGuides)
@@ -807,6 +810,65 @@ class Renderer:
             h = out.cpu().numpy()
             return Crossings(h[:, 0].copy().view(np.uint32), h[:, 1].copy())
         return Crossings(out[:, 0], out[:, 1])       # (torch has no uint32 arithmetic: count is an int32 tensor, < 2^31 triangles)
+
+    def firstHits(self, scene, origins, directions=None, tmin=0.0, tmax=float("inf"), k=4):
+        """The first k triangles each ray passes through within (tmin, tmax), in order of (t, prim) (drt_renderer_list_hits with
+        k slots per ray): FirstHits(t [N, k], prim [N, k] int32, u [N, k], v [N, k], count [N] int32).  Slots beyond a ray's hits hold
+        the miss record (t = tmax, prim = -1, u = v = 0); count is ALL the triangles the ray passes through, crossings' count, so
+        count > k tells a truncated row.  Alpha cut-outs are ignored.  Arguments as crossings."""
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+            raise DrtError(ERR_INVALID, "k = %r: a positive integer expected" % (k,))
+        k = int(k)
+        shape = getattr(origins, "shape", None)
+        if shape is not None and len(shape) >= 1 and int(shape[0]) * k >= 2 ** 31:
+            raise DrtError(ERR_INVALID, "%d rays x %d slots: fewer than 2^31 records expected" % (int(shape[0]), k))
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        if directions is None and tmin == 0.0 and tmax == float("inf"):
+            tmin = tmax = None
+        rays, from_numpy = _ray_batch(torch, dev, origins, directions, tmin, tmax)
+        n = rays.shape[0]
+        hits = torch.empty((n, k, 4), dtype=torch.float32, device=dev)
+        count = torch.empty(n, dtype=torch.int32, device=dev)
+        if n:
+            offsets = (torch.arange(n + 1, dtype=torch.int64, device=dev) * k).to(torch.int32)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(_lib.drt_renderer_list_hits(self._h, scene._h, rays.data_ptr(), offsets.data_ptr(), hits.data_ptr(), n * k,
+                                               count.data_ptr(), n, stream))
+        if from_numpy:
+            h = hits.cpu().numpy()
+            return FirstHits(h[..., 0].copy(), h.view(np.int32)[..., 1].copy(), h[..., 2].copy(), h[..., 3].copy(), count.cpu().numpy())
+        return FirstHits(hits[..., 0], hits.view(torch.int32)[..., 1], hits[..., 2], hits[..., 3], count)
+
+    def listHits(self, scene, origins, directions=None, tmin=0.0, tmax=float("inf")):
+        """Every triangle each ray passes through within (tmin, tmax), in order of (t, prim): HitList(splits [N + 1] int32, t, prim
+        int32, u, v), ray i's hits at [splits[i], splits[i + 1]).  Two passes: drt_renderer_crossings counts, a cumulative sum on the
+        device gives splits, and drt_renderer_list_hits fills.  The total is read back between them to size the result: that read is
+        this call's one synchronisation with the device.  Alpha cut-outs are ignored.  Arguments as crossings."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        if directions is None and tmin == 0.0 and tmax == float("inf"):
+            tmin = tmax = None
+        rays, from_numpy = _ray_batch(torch, dev, origins, directions, tmin, tmax)
+        n = rays.shape[0]
+        splits = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        total = 0
+        if n:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            crossed = torch.empty((n, 2), dtype=torch.int32, device=dev)
+            _check(_lib.drt_renderer_crossings(self._h, scene._h, rays.data_ptr(), crossed.data_ptr(), n, stream))
+            splits[1:] = torch.cumsum(crossed[:, 0].to(torch.int64), dim=0)
+            total = int(splits[-1].item())       # the one synchronisation: the result's size
+            if total >= 2 ** 31:
+                raise DrtError(ERR_INVALID, "%d hits in all: fewer than 2^31 expected (split the rays)" % total)
+        splits = splits.to(torch.int32)
+        hits = torch.empty((total, 4), dtype=torch.float32, device=dev)
+        if total:
+            _check(_lib.drt_renderer_list_hits(self._h, scene._h, rays.data_ptr(), splits.data_ptr(), hits.data_ptr(), total, None, n, stream))
+        if from_numpy:
+            h = hits.cpu().numpy()
+            return HitList(splits.cpu().numpy(), h[:, 0].copy(), h.view(np.int32)[:, 1].copy(), h[:, 2].copy(), h[:, 3].copy())
+        return HitList(splits, hits[:, 0], hits.view(torch.int32)[:, 1], hits[:, 2], hits[:, 3])
 
     @staticmethod
     def _inside_rule(rule):

@@ -16,6 +16,7 @@
 #include "ray_query.hpp"
 #include "nearest.hpp"
 #include "crossings.hpp"
+#include "list_hits.hpp"
 #include "bvh_build_device.hpp"
 #include "png_decode.hpp"
 
@@ -898,6 +899,40 @@ int drt_renderer_signed_distance(drt_renderer *r, const drt_scene *scene, const 
     if (rule != 0 && rule != 1) return bad_rule(rule);
     if (int rc = drt_renderer_nearest(r, scene, points, out, n, hip_stream)) return rc;
     return crossings_impl(r, scene, points, out, 16, n, rule, hip_stream, drt::CrossingsOut::side);
+}
+
+// ------------------------------------------------------------------ ordered hit lists of rays (kernel_list_hits.hip)
+// Validated in crossings_impl's order, ordered and given scratch as it is: the kernel shares the claim heads and the occlusion query's
+// HBM stack.  counts may be null; hits may be null iff hits_capacity == 0 (a pure count); not both.
+int drt_renderer_list_hits(drt_renderer *r, const drt_scene *scene, const drt_ray *rays, const uint32_t *offsets, drt_hit *hits,
+                           uint32_t hits_capacity, uint32_t *counts, uint32_t n, void *hip_stream) {
+    if (!r || !scene) return fail(DRT_ERR_INVALID, "null argument");
+    if (n == 0) return DRT_OK;
+    if (!rays || !offsets) return fail(DRT_ERR_INVALID, "null ray or offset pointer");
+    if (!hits && !counts) return fail(DRT_ERR_INVALID, "hits and counts are both null: nothing to write");
+    if ((hits == nullptr) != (hits_capacity == 0)) return fail(DRT_ERR_INVALID, "hits must be null if and only if hits_capacity is 0");
+    if (((uintptr_t)rays & 15u) != 0 || ((uintptr_t)hits & 15u) != 0 || ((uintptr_t)offsets & 3u) != 0 || ((uintptr_t)counts & 3u) != 0)
+        return fail(DRT_ERR_INVALID, "rays and hits must be 16-byte aligned, offsets and counts 4-byte aligned");
+    if (n > 0x7fffffffu) return fail(DRT_ERR_INVALID, "at most 2^31 - 1 rays per call");
+    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
+    HIP_TRY(hipSetDevice(r->device));
+    (void)hipGetLastError();                   // (see render_batch_impl: only this call's own errors count)
+    if (!on_renderer_device(r, rays) || !on_renderer_device(r, offsets) || (hits && !on_renderer_device(r, hits)) ||
+        (counts && !on_renderer_device(r, counts)))
+        return fail(DRT_ERR_INVALID, "rays, offsets, hits and counts must be device memory on the renderer's device");
+    if (int rc = upload_scene(r, scene)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : r->stream;
+    if (int rc = query_order(r, s)) return rc;
+    if (int rc = traversal_scratch(r, s, true, true)) return rc;
+    ListHitsArgs a;
+    a.rays = rays; a.offsets = offsets; a.hits = hits; a.counts = counts;
+    a.hits_capacity = hits_capacity; a.n = n;
+    a.stack_levels = (uint32_t)std::max(1, r->bvh_depth);
+    a.refill_min = (uint32_t)r->rq_refill_min;
+    a.heads = r->rq_heads.ptr;
+    a.stack_hbm = r->rq_stack.ptr;
+    HIP_TRY(launch_list_hits(r->view, a, r->num_cus, s));
+    return query_recorded(r, s);
 }
 
 // ------------------------------------------------------------------ camera rays and radiance queries (kernel_radiance.hip)

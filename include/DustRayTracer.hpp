@@ -308,6 +308,13 @@ public:
                         void *stream = nullptr) {
         drt::check(drt_renderer_signed_distance(handle, scene.handle, points, out, n, rule, stream));
     }
+    // new: the triangles each ray passes through, sorted by (t, prim) (drt_renderer_list_hits): ray i's records go to
+    // hits[offsets[i] .. offsets[i+1]), clamped to hits_capacity, miss records behind them; counts[i] = all of them, stored or not.
+    // counts may be null, hits may be null iff hits_capacity == 0.  Device arrays, enqueued on `stream`.
+    void ListHits(const Scene &scene, const drt_ray *rays, const uint32_t *offsets, drt_hit *hits, uint32_t hits_capacity, uint32_t *counts,
+                  uint32_t n, void *stream = nullptr) {
+        drt::check(drt_renderer_list_hits(handle, scene.handle, rays, offsets, hits, hits_capacity, counts, n, stream));
+    }
     // new: RayGen's primary rays of n_cams cameras for a width x height image, frame `frame_index` (drt_renderer_camera_rays): a device
     // drt_path_ray[n_cams * width * height], enqueued on `stream`
     void CameraRays(const drt_camera *cams, uint32_t n_cams, uint32_t width, uint32_t height, uint32_t frame_index, drt_path_ray *rays,

@@ -28,7 +28,8 @@ extern "C" {
 /* 2: drt_counters grew by sampler_tries; drt_group_* and drt_material_model entry points (round 2) are part of it; the ray-query
  * entry points (drt_renderer_trace_rays / _occluded), the guide / denoise entry points, the refit entry points and the camera-ray /
  * radiance entry points, the upscaling entry points, the adaptive-sampling entry points, the nearest-surface entry point
- * (drt_renderer_nearest) and the crossing-count entry points (drt_renderer_crossings / _inside / _signed_distance) are additions to it */
+ * (drt_renderer_nearest), the crossing-count entry points (drt_renderer_crossings / _inside / _signed_distance) and the hit-list entry
+ * point (drt_renderer_list_hits) are additions to it */
 #define DRT_ABI_VERSION 2
 
 typedef enum {
@@ -306,8 +307,8 @@ int           drt_renderer_nearest(drt_renderer *r, const drt_scene *scene, cons
  * Signed distance: drt_renderer_nearest's record for the point, unchanged in its first seven words; the last word, side, is
  * replaced by -1 (inside) or +1 (outside) from the vote, in miss records too.
  * What this is not: a point on the surface has no defined answer (t > 1e-6 decides, per ray); parity assumes a closed mesh; winding
- * assumes consistent orientation as well.  Angle-weighted pseudonormals, generalised winding numbers for open meshes and an ordered
- * list of the first K hits per ray are out of scope.
+ * assumes consistent orientation as well.  Angle-weighted pseudonormals and generalised winding numbers for open meshes are out of
+ * scope; an ordered list of the first K hits per ray is drt_renderer_list_hits, below.
  * Conventions and errors are drt_renderer_nearest's: device pointers on the renderer's device, rays / points / drt_nearest records
  * 16-byte aligned, drt_crossings 8-byte aligned, n < 2^31, n == 0 is a no-op, hip_stream NULL = the renderer's stream, the call only
  * enqueues, in order with the other queries, a refitted device copy is the one queried, legal on a sharded renderer,
@@ -320,6 +321,41 @@ typedef struct drt_crossings { uint32_t count; int32_t winding; } drt_crossings;
 int           drt_renderer_crossings(drt_renderer *r, const drt_scene *scene, const drt_ray *rays, drt_crossings *out, uint32_t n, void *hip_stream);
 int           drt_renderer_inside(drt_renderer *r, const drt_scene *scene, const drt_point *points, uint8_t *votes, uint32_t n, int32_t rule, void *hip_stream);
 int           drt_renderer_signed_distance(drt_renderer *r, const drt_scene *scene, const drt_point *points, drt_nearest *out, uint32_t n, int32_t rule, void *hip_stream);
+
+/* ---- ordered hit lists of rays (new; the triangles drt_renderer_crossings counts, handed out in order) ----
+ * Hit list of a ray (a drt_ray, read as drt_renderer_trace_rays reads it: dir as given, inv_dir = 1/dir): the triangles it passes
+ * through, sorted.  The triangle test is the renderer's (Intersection.cu, the arithmetic of the ray queries) on the stored
+ * (v0, e1, e2); t, u and v carry the bits drt_renderer_trace_rays reports for that ray and triangle.  A triangle is listed iff the
+ * test hits, t > tmin and t < tmax: exactly the rule of drt_renderer_crossings.  Alpha cut-outs are ignored (a geometric query), and
+ * the boxes cull as they do there: a triangle whose box the fp32 slab test misses is not listed.  Traversal is
+ * drt_renderer_crossings', unchanged: the root is skipped if d < 0 || d > tmax, a child is pushed iff d >= 0 && !(d > tmax), the
+ * farther child is pushed first, the same stack bound applies.  So the set of listed triangles is the set drt_renderer_crossings
+ * counts, and total == drt_crossings.count for the same ray.
+ * Order: ascending t; equal t by ascending prim.  a comes before b iff a.t < b.t || (a.t == b.t && a.prim < b.prim).  A listed t is
+ * never NaN and always > 1e-6, so the order is total and does not depend on the traversal.
+ * Segments: offsets holds n + 1 uint32 values; ray i owns hits[offsets[i] .. offsets[i+1]).  Its capacity is
+ * cap_i = offsets[i+1] > offsets[i] ? offsets[i+1] - offsets[i] : 0, then clamped so that offsets[i] + cap_i <= hits_capacity
+ * (offsets[i] >= hits_capacity gives 0).  The call writes hits[offsets[i] + j] for j < cap_i and nothing else in hits, whatever
+ * offsets contains (segments that overlap are written by more than one ray and hold no defined list).  Slot j < min(cap_i, total_i)
+ * holds the j-th listed triangle in order, a drt_hit {t, prim, u, v}; the slots from min(cap_i, total_i) to cap_i - 1 hold the miss
+ * record {tmax, -1, 0, 0}, tmax being the ray's own word, bit for bit, as in drt_renderer_trace_rays' miss.  counts[i] = total_i: all
+ * listed triangles, not just the stored ones, which is how a caller sees truncation.  A result depends on the ray, the scene and
+ * cap_i only, and the first K records of a longer list are the list at capacity K.  An empty scene or a NaN ray lists nothing.
+ * Two uses: offsets[i] = K * i gives the first K hits of every ray as an [n, K] table in one pass; drt_renderer_crossings, an
+ * exclusive scan of its counts into offsets and one pass give every hit of every ray (CSR) without a capacity guess.
+ * counts may be NULL; hits may be NULL iff hits_capacity == 0 (a pure count); both NULL is DRT_ERR_INVALID.
+ * What this is not: alpha-tested lists, per-hit normals or materials.  The boxes are NOT culled by the K-th distance once a list is
+ * full: counts[i] would no longer be the total, and fp32 box distances and triangle distances do not order consistently, so the
+ * stored records would depend on the traversal order.  Every ray traverses as drt_renderer_crossings does, whatever its capacity.
+ * The insert moves records one slot at a time: the cost of a hit that arrives out of order grows with the capacity, which suits a
+ * small K.
+ * Conventions and errors are drt_renderer_crossings': handles are checked before n == 0, n == 0 is a no-op, n < 2^31, all pointers
+ * are device pointers on the renderer's device, rays and hits 16-byte aligned, offsets and counts 4-byte aligned, hip_stream NULL =
+ * the renderer's stream, the call only enqueues, in order with the other queries, a refitted device copy is the one queried, legal on
+ * a sharded renderer, DRT_ERR_UNSUPPORTED beyond 64 levels, DRT_ERR_INVALID while an asynchronous batch is pending.  The framebuffer,
+ * accumulation, sample count, counters, kernel info and kernel span are not touched. */
+int           drt_renderer_list_hits(drt_renderer *r, const drt_scene *scene, const drt_ray *rays, const uint32_t *offsets, drt_hit *hits,
+                                     uint32_t hits_capacity, uint32_t *counts, uint32_t n, void *hip_stream);
 
 /* ---- first-hit guide buffers and the a-trous denoiser (new; the reference's TODO list, RayGen.cuh:13-21, starts with "DLSS 3.5
  * like features") ----
