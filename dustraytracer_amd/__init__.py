@@ -327,6 +327,7 @@ _sig("drt_renderer_trace_rays", C.c_int, _P, _P, _P, _P, C.c_uint32, _P)
 _sig("drt_renderer_occluded", C.c_int, _P, _P, _P, _P, C.c_uint32, _P)
 _sig("drt_renderer_nearest", C.c_int, _P, _P, _P, _P, C.c_uint32, _P)
 _sig("drt_renderer_crossings", C.c_int, _P, _P, _P, _P, C.c_uint32, _P)
+_sig("drt_renderer_sphere_cast", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P)
 _sig("drt_renderer_list_hits", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P)
 _sig("drt_renderer_inside", C.c_int, _P, _P, _P, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_renderer_signed_distance", C.c_int, _P, _P, _P, _P, C.c_uint32, C.c_int32, _P)
@@ -607,6 +608,7 @@ FLT_MAX = float(np.finfo(np.float32).max)
 RayHits = collections.namedtuple("RayHits", "t prim u v")     # closest-hit query results (Renderer.traceRays)
 Nearest = collections.namedtuple("Nearest", "point d2 prim u v side")   # nearest-surface query results (Renderer.nearest)
 Crossings = collections.namedtuple("Crossings", "count winding")       # crossing counts of rays (Renderer.crossings)
+SphereHits = collections.namedtuple("SphereHits", "t prim u v point feature")   # first contacts of moving spheres (Renderer.sphereCast)
 FirstHits = collections.namedtuple("FirstHits", "t prim u v count")     # the first k hits of rays, in order (Renderer.firstHits)
 HitList = collections.namedtuple("HitList", "splits t prim u v")        # every hit of rays, in order, CSR (Renderer.listHits)
 INSIDE_RULES = {"parity": 0, "winding": 1}                              # Renderer.inside / signedDistance: drt.h DRT_INSIDE_*
@@ -792,6 +794,42 @@ class Renderer:
             h = out.cpu().numpy()
             return Nearest(h[:, 0:3].copy(), h[:, 3].copy(), h.view(np.int32)[:, 4].copy(), h[:, 5].copy(), h[:, 6].copy(), h[:, 7].copy())
         return Nearest(out[:, 0:3], out[:, 3], out.view(torch.int32)[:, 4], out[:, 5], out[:, 6], out[:, 7])
+
+    def sphereCast(self, scene, origins, directions=None, radius=0.0, tmin=0.0, tmax=float("inf")):
+        """The first contact of a sphere moving along each ray with the mesh (drt_renderer_sphere_cast): SphereHits(t, prim, u, v,
+        point [N, 3], feature), prim -1 = no contact in [tmin, tmax) (then t = tmax, feature = -1).  The centre at t is origin +
+        direction t; feature 0 = face, 1..3 = edges, 4..6 = vertices, + 8 when the sphere already overlapped at tmin.  radius is a
+        scalar or [N].  Other arguments as crossings.  After refit(scene, positions) the moved geometry is the one queried."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        if directions is None and tmin == 0.0 and tmax == float("inf"):
+            tmin = tmax = None
+        rays, from_numpy = _ray_batch(torch, dev, origins, directions, tmin, tmax)
+        n = rays.shape[0]
+        if isinstance(radius, (int, float, np.floating, np.integer)):
+            radii = torch.full((n,), float(radius), dtype=torch.float32, device=dev)
+        else:
+            if not (isinstance(radius, np.ndarray) or torch.is_tensor(radius)):
+                raise DrtError(ERR_INVALID, "radius: a number, a numpy array or a torch tensor expected")
+            if isinstance(radius, np.ndarray) != from_numpy:
+                raise DrtError(ERR_INVALID, "mix of numpy arrays and device tensors")
+            if radius.dtype != (np.float32 if from_numpy else torch.float32):
+                raise DrtError(ERR_INVALID, "radius: dtype %s, float32 expected" % (radius.dtype,))
+            if not from_numpy and radius.device != dev:
+                raise DrtError(ERR_INVALID, "radius: on %s, the renderer is on %s" % (radius.device, dev))
+            if len(radius.shape) != 1 or radius.shape[0] != n:
+                raise DrtError(ERR_INVALID, "radius: shape %s for %d rays" % (tuple(radius.shape), n))
+            radii = torch.from_numpy(np.ascontiguousarray(radius)).to(dev) if from_numpy else radius.contiguous()
+        out = torch.empty((n, 8), dtype=torch.float32, device=dev)
+        if n:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(_lib.drt_renderer_sphere_cast(self._h, scene._h, rays.data_ptr(), radii.data_ptr(), out.data_ptr(), n, stream))
+        if from_numpy:
+            h = out.cpu().numpy()
+            i = h.view(np.int32)
+            return SphereHits(h[:, 0].copy(), i[:, 1].copy(), h[:, 2].copy(), h[:, 3].copy(), h[:, 4:7].copy(), i[:, 7].copy())
+        i = out.view(torch.int32)
+        return SphereHits(out[:, 0], i[:, 1], out[:, 2], out[:, 3], out[:, 4:7], i[:, 7])
 
     def crossings(self, scene, origins, directions=None, tmin=0.0, tmax=float("inf")):
         """Every triangle each ray passes through within (tmin, tmax) (drt_renderer_crossings): Crossings(count uint32 [N], winding

@@ -15,6 +15,7 @@
 
 #include "ray_query.hpp"
 #include "nearest.hpp"
+#include "sphere_cast.hpp"
 #include "crossings.hpp"
 #include "list_hits.hpp"
 #include "bvh_build_device.hpp"
@@ -846,6 +847,35 @@ int drt_renderer_nearest(drt_renderer *r, const drt_scene *scene, const drt_poin
     a.heads = r->rq_heads.ptr;
     a.stack_hbm = r->rq_stack.ptr;
     HIP_TRY(launch_nearest(r->view, a, r->num_cus, s));
+    return query_recorded(r, s);
+}
+
+// ------------------------------------------------------------------ sphere casts (kernel_sphere_cast.hip)
+// Validated, ordered and given scratch as drt_renderer_nearest is: the kernel shares the claim heads and the closest-hit HBM stack.
+int drt_renderer_sphere_cast(drt_renderer *r, const drt_scene *scene, const drt_ray *rays, const float *radii, drt_sweep_hit *out, uint32_t n,
+                             void *hip_stream) {
+    if (!r || !scene) return fail(DRT_ERR_INVALID, "null argument");
+    if (n == 0) return DRT_OK;
+    if (!rays || !radii || !out) return fail(DRT_ERR_INVALID, "null ray, radius or result pointer");
+    if (((uintptr_t)rays & 15u) != 0 || ((uintptr_t)out & 15u) != 0 || ((uintptr_t)radii & 3u) != 0)
+        return fail(DRT_ERR_INVALID, "rays and results must be 16-byte aligned, radii 4-byte aligned");
+    if (n > 0x7fffffffu) return fail(DRT_ERR_INVALID, "at most 2^31 - 1 casts per call");
+    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
+    HIP_TRY(hipSetDevice(r->device));
+    (void)hipGetLastError();                   // (see render_batch_impl: only this call's own errors count)
+    if (!on_renderer_device(r, rays) || !on_renderer_device(r, radii) || !on_renderer_device(r, out))
+        return fail(DRT_ERR_INVALID, "rays, radii and results must be device memory on the renderer's device");
+    if (int rc = upload_scene(r, scene)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : r->stream;
+    if (int rc = query_order(r, s)) return rc;
+    if (int rc = traversal_scratch(r, s, false, true)) return rc;
+    SphereCastArgs a;
+    a.rays = rays; a.radii = radii; a.out = out; a.n = n;
+    a.stack_levels = (uint32_t)std::max(1, r->bvh_depth);
+    a.refill_min = (uint32_t)r->rq_refill_min;
+    a.heads = r->rq_heads.ptr;
+    a.stack_hbm = r->rq_stack.ptr;
+    HIP_TRY(launch_sphere_cast(r->view, a, r->num_cus, s));
     return query_recorded(r, s);
 }
 

@@ -295,6 +295,11 @@ public:
     void Nearest(const Scene &scene, const drt_point *points, drt_nearest *out, uint32_t n, void *stream = nullptr) {
         drt::check(drt_renderer_nearest(handle, scene.handle, points, out, n, stream));
     }
+    // new: the first contact of a sphere of radius radii[i] moving along rays[i] with the mesh (drt_renderer_sphere_cast: device
+    // arrays, enqueued on `stream`); after Refit the moved geometry is the one queried
+    void SphereCast(const Scene &scene, const drt_ray *rays, const float *radii, drt_sweep_hit *out, uint32_t n, void *stream = nullptr) {
+        drt::check(drt_renderer_sphere_cast(handle, scene.handle, rays, radii, out, n, stream));
+    }
     // new: every triangle each ray passes through (drt_renderer_crossings), the inside vote of each point, 0..3 with 2 or more =
     // inside (drt_renderer_inside), and Nearest's records with side = -1 inside / +1 outside (drt_renderer_signed_distance);
     // rule = DRT_INSIDE_PARITY or DRT_INSIDE_WINDING.  Device arrays, enqueued on `stream`.

@@ -28,8 +28,8 @@ extern "C" {
 /* 2: drt_counters grew by sampler_tries; drt_group_* and drt_material_model entry points (round 2) are part of it; the ray-query
  * entry points (drt_renderer_trace_rays / _occluded), the guide / denoise entry points, the refit entry points and the camera-ray /
  * radiance entry points, the upscaling entry points, the adaptive-sampling entry points, the nearest-surface entry point
- * (drt_renderer_nearest), the crossing-count entry points (drt_renderer_crossings / _inside / _signed_distance) and the hit-list entry
- * point (drt_renderer_list_hits) are additions to it */
+ * (drt_renderer_nearest), the crossing-count entry points (drt_renderer_crossings / _inside / _signed_distance), the hit-list entry
+ * point (drt_renderer_list_hits) and the sphere-cast entry point (drt_renderer_sphere_cast) are additions to it */
 #define DRT_ABI_VERSION 2
 
 typedef enum {
@@ -356,6 +356,78 @@ int           drt_renderer_signed_distance(drt_renderer *r, const drt_scene *sce
  * accumulation, sample count, counters, kernel info and kernel span are not touched. */
 int           drt_renderer_list_hits(drt_renderer *r, const drt_scene *scene, const drt_ray *rays, const uint32_t *offsets, drt_hit *hits,
                                      uint32_t hits_capacity, uint32_t *counts, uint32_t n, void *hip_stream);
+
+/* ---- sphere casts (new; the first contact of a moving sphere with the mesh) ----
+ * One cast = a drt_ray (org o, tmin, dir d, tmax, read as drt_renderer_trace_rays reads it: dir as given, t in units of |d|,
+ * inv_dir = 1/dir) and a radius r.  The sphere's centre at parameter t is o + d t; the answer is the smallest t in [tmin, tmax) at
+ * which the sphere touches a triangle, with that triangle, the contact point on it and the feature touched.  r = 0 is a ray with a
+ * closed start (a centre that starts on the surface hits at tmin).
+ * All arithmetic is fp32 with one rounding per operation, in the order written; dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z, / is the
+ * correctly rounded division and sqrt the correctly rounded square root.  A NaN fails every test.
+ * The sphere touches a triangle where its centre enters the triangle's offset volume: the union of seven convex shapes, a prism over
+ * the face, a cylinder round each edge and a sphere at each vertex.  The shapes overlap on purpose: every edge cylinder is a whole
+ * cylinder and every vertex sphere a whole sphere, and no shape's test is restricted to its Voronoi region.  A centre that misses the
+ * prism's face by a rounding error enters the neighbouring cylinder an instant later; nothing slips through a seam.
+ * Per cast: s = o + d tmin (the start centre), dd = dot(d, d), r2 = r r.  Every entry time is tau >= 0, measured from s; a
+ * candidate's t = tmin + tau.
+ * Per triangle k: (v0, e1, e2) as drt_renderer_nearest reads them (the stored edges).  d11 = dot(e1, e1), d22 = dot(e2, e2),
+ * d12 = dot(e1, e2); the vertices p0 = v0, p1 = v0 + e1, p2 = v0 + e2 and, for j = 0, 1, 2, mj = s - pj, bj = dot(mj, d),
+ * cj = dot(mj, mj) - r2.  The triangle's candidate starts as t = +inf, feature -1; the seven shapes are taken in feature order and
+ * a later one replaces an earlier one only on a strict <.
+ *   Face (feature 0).  n = cross(e1, e2), k = r sqrt(dot(n, n)), h = dot(n, m0), dn = dot(n, d).  Containment branch: |h| <= k, the
+ *     centre starts inside the slab, tau = 0.  Otherwise the sphere must approach, (h > 0 && dn < 0) || (h < 0 && dn > 0), and
+ *     tau = (|h| - k) / |dn|.  The centre at tau, q = m0 + d tau, is projected onto the plane and must lie in the triangle:
+ *     q1 = dot(q, e1), q2 = dot(q, e2), nu = d22 q1 - d12 q2, nv = d11 q2 - d12 q1, den = d11 d22 - d12 d12, accepted iff
+ *     den > 0 && nu >= 0 && nv >= 0 && nu + nv <= den.  A zero-area triangle (den <= 0) has no face candidate; its edges and
+ *     vertices still count.
+ *   Edges (features 1, 2, 3).  (a, e, m, md, c, ee) = (p0, e1, m0, b0, c0, d11), (p0, e2, m0, b0, c0, d22) and, with e3 = e2 - e1,
+ *     (p1, e3, m1, b1, c1, dot(e3, e3)).  me = dot(m, e), de = dot(d, e), Cq = ee c - me me.  Containment branch: Cq <= 0, the centre
+ *     starts inside the infinite cylinder, tau = 0.  Otherwise x = cross(d, e), det = dot(m, x), A = dot(x, x), B = ee md - de me;
+ *     require A > 0 && B < 0 and disc = ee (A r2 - det det) >= 0; then tau = Cq / (sqrt(disc) - B).  Accepted iff the axial
+ *     coordinate ax = me + tau de satisfies ee > 0 && ax >= 0 && ax <= ee (an edge of length zero is its two vertices).
+ *   Vertices (features 4, 5, 6).  (m, b, c) = (m0, b0, c0), (m1, b1, c1), (m2, b2, c2).  Containment branch: c <= 0, tau = 0.
+ *     Otherwise require dd > 0 && b < 0 and, with x = cross(m, d), disc = dd r2 - dot(x, x) >= 0; then tau = c / (sqrt(disc) - b).
+ * These are the quadratics A tau^2 + 2 B tau + Cq = 0 (A = ee dd - de de) and dd tau^2 + 2 b tau + c = 0 with both cancellations
+ * taken out.  The discriminants B B - A Cq and b b - dd c are differences of two numbers that grow with the square of the start's
+ * distance and differ by a term of the radius' size; by Lagrange's identity they equal ee (|d x e|^2 r2 - (m . (d x e))^2) and
+ * dd r2 - |m x d|^2, whose rounding error grows with the distance only.  tau = Cq / (sqrt(disc) - B) is the smaller root
+ * (-B - sqrt(disc)) / A with numerator and denominator multiplied by -B + sqrt(disc): Cq > 0 and sqrt(disc) - B > 0, so every entry
+ * time is 0 (a containment branch) or a quotient of two positive numbers.  A sphere resting at distance r (1 +- eps) from a surface
+ * and pushed into it gets tau = 0 or a small positive tau, never a slightly negative root that is thrown away; there is no separate
+ * start-overlap test.  A tau = 0 found by a containment branch adds 8 to the feature (8 = face, 9..11 = edges, 12..14 = vertices):
+ * the sphere overlapped the triangle at tmin.
+ * Across triangles: a triangle's candidate (t, k) replaces the result iff t < best || (t == best && k < prim); best starts as tmax
+ * with prim = -1, so a candidate is valid iff t < tmax, and the answer does not depend on the tree.
+ * Traversal: a node's box is inflated by r on every side and slab-tested: per axis t0 = ((bmin - r) - o) inv_dir,
+ * t1 = ((bmax + r) - o) inv_dir, enter = the largest of fminf(t0, t1), exit = the smallest of fmaxf(t1, t0) (a NaN operand, 0 * inf,
+ * is dropped).  A node is visited iff enter <= exit && exit >= tmin && enter <= best.  The root is pushed iff it passes, r >= 0 and no
+ * component of o or d is NaN (a NaN tmin or tmax fails the test by itself), so such a cast visits nothing; a popped
+ * entry is dropped unless its enter <= best still holds; a leaf tests its triangles in order; an interior node pushes each child that
+ * passes, the farther one first (enter1 > enter2 -> child 1): drt_renderer_trace_rays' stack discipline and its 64-level limit.
+ * (The fp32 slab test culls as it does for the ray queries: a contact whose inflated box the test misses by a rounding is not found.)
+ * A zero direction gives the static overlap test that the containment branches are: inv_dir is +-inf, a box that contains o after
+ * inflation has enter = -inf and exit = +inf and is visited, no entry branch can pass (dn = 0, A = 0, dd = 0), so the result is the
+ * lowest-numbered triangle that the sphere at o overlaps, with t = tmin, or a miss.
+ * Result: one drt_sweep_hit {t, prim, u, v, point, feature}.  (u, v) and the point are computed once, after the traversal, from the
+ * winning (prim, feature, t): cc = o + d t, q = cc - v0, and by feature & 7
+ *   0: (nu / den, nv / den) with q1, q2, nu, nv, den as in the face test;   1: (w, 0), w = fminf(fmaxf(dot(q, e1) / d11, 0), 1);
+ *   2: (0, w), w = fminf(fmaxf(dot(q, e2) / d22, 0), 1);   3: (1 - w, w), w = fminf(fmaxf(dot(q - e1, e3) / dot(e3, e3), 0), 1);
+ *   4: (0, 0);   5: (1, 0);   6: (0, 1);
+ * point = (v0 + e1 u) + e2 v.  The contact normal is (o + d t) - point; the caller can form it.  For a containment feature the point
+ * is where the shape's axis is nearest the start centre, not the deepest point of the overlap.
+ * A miss -- nothing touched in [tmin, tmax), a negative or NaN radius, a NaN ray, an empty scene -- is {tmax, -1, 0, 0, 0, 0, 0, -1},
+ * tmax being the ray's own word.  A result depends on its cast and the scene only.
+ * What this is not: alpha cut-outs are ignored (a geometric query); capsules, boxes and rotating bodies are out of scope, as is the
+ * penetration depth of a sphere that starts in overlap.
+ * Conventions and errors are drt_renderer_nearest's, checked in its order: device pointers on the renderer's device, rays and results
+ * 16-byte aligned, radii a float[n] 4-byte aligned, n < 2^31, n == 0 is a no-op, hip_stream NULL = the renderer's stream, the call only
+ * enqueues, in order with the other queries (the same event), the scene is uploaded as for rendering and a refitted device copy
+ * (drt_renderer_refit) is the one queried.  Legal on a sharded renderer.  DRT_ERR_UNSUPPORTED beyond 64 levels, DRT_ERR_INVALID while
+ * an asynchronous batch is pending.  The framebuffer, accumulation, sample count, counters, kernel info and kernel span are not
+ * touched. */
+typedef struct drt_sweep_hit { float t; int32_t prim; float u, v; float point[3]; int32_t feature; } drt_sweep_hit;   /* 32 B */
+int           drt_renderer_sphere_cast(drt_renderer *r, const drt_scene *scene, const drt_ray *rays, const float *radii, drt_sweep_hit *out,
+                                       uint32_t n, void *hip_stream);
 
 /* ---- first-hit guide buffers and the a-trous denoiser (new; the reference's TODO list, RayGen.cuh:13-21, starts with "DLSS 3.5
  * like features") ----

@@ -39,7 +39,7 @@ def main():
     md = "--md" in sys.argv
     rows = []
     for src, extra in (("kernel_path_pool.hip", ()), ("kernel_path_pool.hip", ("-DDRT_POOL_EXT_TU",)), ("kernel_wave_queue.hip", ()),
-                       ("render_kernels.hip", ()), ("kernel_bvh_build.hip", ())):
+                       ("render_kernels.hip", ()), ("kernel_bvh_build.hip", ()), ("kernel_sphere_cast.hip", ())):
         for r in remarks(src, extra):
             if "VGPRs" in r and not (extra and "ILi" in r["name"] and int(re.search(r"ILi(\d+)E", r["name"]).group(1)) < 16):
                 rows.append(r)
