@@ -329,6 +329,7 @@ _sig("drt_renderer_nearest", C.c_int, _P, _P, _P, _P, C.c_uint32, _P)
 _sig("drt_renderer_crossings", C.c_int, _P, _P, _P, _P, C.c_uint32, _P)
 _sig("drt_renderer_sphere_cast", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P)
 _sig("drt_renderer_list_hits", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P)
+_sig("drt_renderer_nearest_list", C.c_int, _P, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_renderer_inside", C.c_int, _P, _P, _P, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_renderer_signed_distance", C.c_int, _P, _P, _P, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_renderer_render_guides", C.c_int, _P, C.POINTER(_CameraPOD), _P, C.c_uint32, _P, _P)
@@ -611,6 +612,9 @@ Crossings = collections.namedtuple("Crossings", "count winding")       # crossin
 SphereHits = collections.namedtuple("SphereHits", "t prim u v point feature")   # first contacts of moving spheres (Renderer.sphereCast)
 FirstHits = collections.namedtuple("FirstHits", "t prim u v count")     # the first k hits of rays, in order (Renderer.firstHits)
 HitList = collections.namedtuple("HitList", "splits t prim u v")        # every hit of rays, in order, CSR (Renderer.listHits)
+KNearest = collections.namedtuple("KNearest", "d2 prim u v point side count")   # the k nearest triangles of points (Renderer.kNearest)
+NearList = collections.namedtuple("NearList", "splits d2 prim u v point side")  # every triangle within a radius, CSR (Renderer.withinRadius)
+NEAR_GATHER, NEAR_K = 0, 1                                              # drt.h DRT_NEAR_*
 INSIDE_RULES = {"parity": 0, "winding": 1}                              # Renderer.inside / signedDistance: drt.h DRT_INSIDE_*
 TemporalHistory = collections.namedtuple("TemporalHistory", "color length moments variance weight")  # Renderer.GetTemporalHistory
 Guides = collections.namedtuple("Guides", "albedo normal t prim")  # first-hit guide buffers (Renderer.renderGuides)
@@ -907,6 +911,69 @@ class Renderer:
             h = hits.cpu().numpy()
             return HitList(splits.cpu().numpy(), h[:, 0].copy(), h.view(np.int32)[:, 1].copy(), h[:, 2].copy(), h[:, 3].copy())
         return HitList(splits, hits[:, 0], hits.view(torch.int32)[:, 1], hits[:, 2], hits[:, 3])
+
+    def kNearest(self, scene, points, k=4, max_dist=float("inf")):
+        """The k nearest triangles of every point within max_dist, in order of (d2, prim) (drt_renderer_nearest_list in mode
+        DRT_NEAR_K with k slots per point): KNearest(d2 [N, k], prim [N, k] int32, u [N, k], v [N, k], point [N, k, 3], side [N, k],
+        count [N] int32).  Slots beyond a point's list hold the miss record (d2 = max_dist^2, prim = -1, u = v = 0, point = 0,
+        side = 0); count is the number stored.  Alpha cut-outs are ignored.  Arguments as nearest."""
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+            raise DrtError(ERR_INVALID, "k = %r: a positive integer expected" % (k,))
+        k = int(k)
+        shape = getattr(points, "shape", None)
+        if shape is not None and len(shape) >= 1 and int(shape[0]) * k >= 2 ** 31:
+            raise DrtError(ERR_INVALID, "%d points x %d slots: fewer than 2^31 records expected" % (int(shape[0]), k))
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        packed, from_numpy = _point_batch(torch, dev, points, max_dist)
+        n = packed.shape[0]
+        near = torch.empty((n, k, 4), dtype=torch.float32, device=dev)
+        surf = torch.empty((n, k, 4), dtype=torch.float32, device=dev)
+        count = torch.empty(n, dtype=torch.int32, device=dev)
+        if n:
+            offsets = (torch.arange(n + 1, dtype=torch.int64, device=dev) * k).to(torch.int32)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(_lib.drt_renderer_nearest_list(self._h, scene._h, packed.data_ptr(), offsets.data_ptr(), near.data_ptr(), surf.data_ptr(),
+                                                  n * k, count.data_ptr(), n, NEAR_K, stream))
+        if from_numpy:
+            h, s = near.cpu().numpy(), surf.cpu().numpy()
+            return KNearest(h[..., 0].copy(), h.view(np.int32)[..., 1].copy(), h[..., 2].copy(), h[..., 3].copy(), s[..., 0:3].copy(),
+                            s[..., 3].copy(), count.cpu().numpy())
+        return KNearest(near[..., 0], near.view(torch.int32)[..., 1], near[..., 2], near[..., 3], surf[..., 0:3], surf[..., 3], count)
+
+    def withinRadius(self, scene, points, radius):
+        """Every triangle within `radius` of each point, in order of (d2, prim): NearList(splits [N + 1] int32, d2, prim int32, u, v,
+        point [M, 3], side), point i's triangles at [splits[i], splits[i + 1]).  Two passes of drt_renderer_nearest_list in mode
+        DRT_NEAR_GATHER: a count with capacity 0, a cumulative sum on the device gives splits, and a fill.  The total is read back
+        between them to size the result: that read is this call's one synchronisation with the device.  Alpha cut-outs are ignored.
+        points and radius as nearest's points and max_dist."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        packed, from_numpy = _point_batch(torch, dev, points, radius)
+        n = packed.shape[0]
+        splits = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        total = 0
+        if n:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            counts = torch.empty(n, dtype=torch.int32, device=dev)
+            no_room = torch.zeros(n + 1, dtype=torch.int32, device=dev)       # capacity 0: every segment is empty
+            _check(_lib.drt_renderer_nearest_list(self._h, scene._h, packed.data_ptr(), no_room.data_ptr(), None, None, 0, counts.data_ptr(),
+                                                  n, NEAR_GATHER, stream))
+            splits[1:] = torch.cumsum(counts.to(torch.int64), dim=0)
+            total = int(splits[-1].item())       # the one synchronisation: the result's size
+            if total >= 2 ** 31:
+                raise DrtError(ERR_INVALID, "%d triangles in all: fewer than 2^31 expected (split the points)" % total)
+        splits = splits.to(torch.int32)
+        near = torch.empty((total, 4), dtype=torch.float32, device=dev)
+        surf = torch.empty((total, 4), dtype=torch.float32, device=dev)
+        if total:
+            _check(_lib.drt_renderer_nearest_list(self._h, scene._h, packed.data_ptr(), splits.data_ptr(), near.data_ptr(), surf.data_ptr(),
+                                                  total, None, n, NEAR_GATHER, stream))
+        if from_numpy:
+            h, s = near.cpu().numpy(), surf.cpu().numpy()
+            return NearList(splits.cpu().numpy(), h[:, 0].copy(), h.view(np.int32)[:, 1].copy(), h[:, 2].copy(), h[:, 3].copy(),
+                            s[:, 0:3].copy(), s[:, 3].copy())
+        return NearList(splits, near[:, 0], near.view(torch.int32)[:, 1], near[:, 2], near[:, 3], surf[:, 0:3], surf[:, 3])
 
     @staticmethod
     def _inside_rule(rule):

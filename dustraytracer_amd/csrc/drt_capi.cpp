@@ -18,6 +18,7 @@
 #include "sphere_cast.hpp"
 #include "crossings.hpp"
 #include "list_hits.hpp"
+#include "near_list.hpp"
 #include "bvh_build_device.hpp"
 #include "png_decode.hpp"
 
@@ -962,6 +963,44 @@ int drt_renderer_list_hits(drt_renderer *r, const drt_scene *scene, const drt_ra
     a.heads = r->rq_heads.ptr;
     a.stack_hbm = r->rq_stack.ptr;
     HIP_TRY(launch_list_hits(r->view, a, r->num_cus, s));
+    return query_recorded(r, s);
+}
+
+// ------------------------------------------------------------------ nearest-triangle lists of points (kernel_near_list.hip)
+// Validated in drt_renderer_list_hits' order with the mode first after the handles, ordered and given scratch as drt_renderer_nearest
+// is: the kernel shares the claim heads and the closest-hit HBM stack.  counts and surf may be null; near may be null iff
+// near_capacity == 0 (a pure count); near and counts not both.
+int drt_renderer_nearest_list(drt_renderer *r, const drt_scene *scene, const drt_point *points, const uint32_t *offsets, drt_near *near,
+                              drt_near_surf *surf, uint32_t near_capacity, uint32_t *counts, uint32_t n, int32_t mode, void *hip_stream) {
+    if (!r || !scene) return fail(DRT_ERR_INVALID, "null argument");
+    if (mode != DRT_NEAR_GATHER && mode != DRT_NEAR_K)
+        return fail(DRT_ERR_INVALID, "mode " + std::to_string(mode) + ": 0 (gather) or 1 (k-nearest) expected");
+    if (n == 0) return DRT_OK;
+    if (!points || !offsets) return fail(DRT_ERR_INVALID, "null point or offset pointer");
+    if (!near && !counts) return fail(DRT_ERR_INVALID, "near and counts are both null: nothing to write");
+    if ((near == nullptr) != (near_capacity == 0)) return fail(DRT_ERR_INVALID, "near must be null if and only if near_capacity is 0");
+    if (((uintptr_t)points & 15u) != 0 || ((uintptr_t)near & 15u) != 0 || ((uintptr_t)surf & 15u) != 0 || ((uintptr_t)offsets & 3u) != 0 ||
+        ((uintptr_t)counts & 3u) != 0)
+        return fail(DRT_ERR_INVALID, "points, near and surf must be 16-byte aligned, offsets and counts 4-byte aligned");
+    if (n > 0x7fffffffu) return fail(DRT_ERR_INVALID, "at most 2^31 - 1 points per call");
+    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
+    HIP_TRY(hipSetDevice(r->device));
+    (void)hipGetLastError();                   // (see render_batch_impl: only this call's own errors count)
+    if (!on_renderer_device(r, points) || !on_renderer_device(r, offsets) || (near && !on_renderer_device(r, near)) ||
+        (surf && !on_renderer_device(r, surf)) || (counts && !on_renderer_device(r, counts)))
+        return fail(DRT_ERR_INVALID, "points, offsets, near, surf and counts must be device memory on the renderer's device");
+    if (int rc = upload_scene(r, scene)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : r->stream;
+    if (int rc = query_order(r, s)) return rc;
+    if (int rc = traversal_scratch(r, s, false, true)) return rc;
+    NearListArgs a;
+    a.points = points; a.offsets = offsets; a.near = near; a.surf = near_capacity ? surf : nullptr; a.counts = counts;
+    a.near_capacity = near_capacity; a.n = n;
+    a.stack_levels = (uint32_t)std::max(1, r->bvh_depth);
+    a.refill_min = (uint32_t)r->rq_refill_min;
+    a.heads = r->rq_heads.ptr;
+    a.stack_hbm = r->rq_stack.ptr;
+    HIP_TRY(launch_near_list(r->view, mode == DRT_NEAR_K, a, r->num_cus, s));
     return query_recorded(r, s);
 }
 

@@ -320,6 +320,15 @@ public:
                   uint32_t n, void *stream = nullptr) {
         drt::check(drt_renderer_list_hits(handle, scene.handle, rays, offsets, hits, hits_capacity, counts, n, stream));
     }
+    // new: the triangles nearest each point within its max_dist, sorted by (d2, prim) (drt_renderer_nearest_list): point i's records go
+    // to near[offsets[i] .. offsets[i+1]), clamped to near_capacity, miss records behind them.  mode DRT_NEAR_GATHER: every triangle
+    // within the radius, counts[i] = all of them, stored or not; mode DRT_NEAR_K: the cap_i nearest, counts[i] = the stored ones.
+    // surf (the closest points and sides, parallel to near) and counts may be null, near may be null iff near_capacity == 0.  Device
+    // arrays, enqueued on `stream`.
+    void NearestList(const Scene &scene, const drt_point *points, const uint32_t *offsets, drt_near *near, drt_near_surf *surf,
+                     uint32_t near_capacity, uint32_t *counts, uint32_t n, int32_t mode, void *stream = nullptr) {
+        drt::check(drt_renderer_nearest_list(handle, scene.handle, points, offsets, near, surf, near_capacity, counts, n, mode, stream));
+    }
     // new: RayGen's primary rays of n_cams cameras for a width x height image, frame `frame_index` (drt_renderer_camera_rays): a device
     // drt_path_ray[n_cams * width * height], enqueued on `stream`
     void CameraRays(const drt_camera *cams, uint32_t n_cams, uint32_t width, uint32_t height, uint32_t frame_index, drt_path_ray *rays,

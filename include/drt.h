@@ -29,7 +29,8 @@ extern "C" {
  * entry points (drt_renderer_trace_rays / _occluded), the guide / denoise entry points, the refit entry points and the camera-ray /
  * radiance entry points, the upscaling entry points, the adaptive-sampling entry points, the nearest-surface entry point
  * (drt_renderer_nearest), the crossing-count entry points (drt_renderer_crossings / _inside / _signed_distance), the hit-list entry
- * point (drt_renderer_list_hits) and the sphere-cast entry point (drt_renderer_sphere_cast) are additions to it */
+ * point (drt_renderer_list_hits), the sphere-cast entry point (drt_renderer_sphere_cast) and the nearest-list entry point
+ * (drt_renderer_nearest_list) are additions to it */
 #define DRT_ABI_VERSION 2
 
 typedef enum {
@@ -278,7 +279,8 @@ int           drt_renderer_occluded(drt_renderer *r, const drt_scene *scene, con
  * {0, 0, 0, max_dist * max_dist, -1, 0, 0, 0}.  A result depends on its point and the scene only.
  * What this is not: alpha cut-outs are ignored (a geometric query).  `side` is the side of the nearest triangle's plane, not an
  * inside / outside classification: at an edge or vertex of a non-convex mesh it can disagree with a parity test (a robust sign --
- * pseudonormals, ray parity -- is out of scope, as are k-nearest and radius-gather queries).
+ * pseudonormals, ray parity -- is out of scope).  One answer per point: k-nearest and radius-gather queries are
+ * drt_renderer_nearest_list, below.
  * Conventions are drt_renderer_trace_rays': device pointers on the renderer's device, 16-byte aligned, n < 2^31, n == 0 is a no-op,
  * hip_stream NULL = the renderer's stream, the call only enqueues, in order with the other queries (the same event), the scene is
  * uploaded as for rendering and a refitted device copy (drt_renderer_refit) is the one queried.  Legal on a sharded renderer.  The
@@ -356,6 +358,63 @@ int           drt_renderer_signed_distance(drt_renderer *r, const drt_scene *sce
  * accumulation, sample count, counters, kernel info and kernel span are not touched. */
 int           drt_renderer_list_hits(drt_renderer *r, const drt_scene *scene, const drt_ray *rays, const uint32_t *offsets, drt_hit *hits,
                                      uint32_t hits_capacity, uint32_t *counts, uint32_t n, void *hip_stream);
+
+/* ---- nearest-triangle lists of points (new; drt_renderer_nearest's candidates, handed out in order) ----
+ * Near list of a point (a drt_point, read as drt_renderer_nearest reads it): the triangles within max_dist of p, sorted by distance.
+ * Per triangle and per box the arithmetic is drt_renderer_nearest's own on the stored (v0, e1, e2): the Ericson case chain gives
+ * (u, v), c = (v0 + e1 u) + e2 v and dist2; box2 is its box distance.  d2, u and v carry the bits drt_renderer_nearest computes for
+ * that point and triangle.  r2 = max_dist * max_dist, the point's own product.  A triangle is listed iff dist2 < r2; a NaN dist2 (a NaN
+ * point, a zero-area triangle whose matching case divides 0 by 0) is never listed, and for a NaN max_dist r2 is some NaN and nothing is
+ * listed.  Alpha cut-outs are ignored (a geometric query).
+ * Order: ascending d2; equal d2 by ascending prim.  a comes before b iff a.d2 < b.d2 || (a.d2 == b.d2 && a.prim < b.prim).  A listed
+ * d2 is never NaN, so the order is total and independent of the traversal.
+ * Segments are drt_renderer_list_hits': offsets holds n + 1 uint32 values; point i owns near[offsets[i] .. offsets[i+1]).  Its capacity
+ * is cap_i = offsets[i+1] > offsets[i] ? offsets[i+1] - offsets[i] : 0, then clamped so that offsets[i] + cap_i <= near_capacity
+ * (offsets[i] >= near_capacity gives 0).  The call writes near[offsets[i] + j] for j < cap_i and nothing else in near, whatever
+ * offsets contains (segments that overlap are written by more than one point and hold no defined list).  Slot j < stored_i holds the
+ * j-th record of the list in order, a drt_near {d2, prim, u, v}; the slots from stored_i to cap_i - 1 hold the miss record
+ * {r2, -1, 0, 0}, r2 being the point's own product, bit for bit.
+ * surf may be NULL; otherwise it is a parallel array of near_capacity drt_near_surf records, written for the same slots and no others.
+ * For a stored slot point = (v0 + e1 u) + e2 v and side = dot(p - point, fn) < 0 ? -1 : 1 with fn the stored face normal: the same
+ * operations as drt_renderer_nearest's result, on the stored (prim, u, v).  For a miss slot {0, 0, 0, 0}.  It is filled when the point
+ * finishes, so the records that move while a list is being sorted stay 16 bytes.
+ * Search bound, evaluated at every pop and every push: keep(box2) = (mode == DRT_NEAR_K && stored == cap_i) ? box2 <= tail.d2
+ * : box2 < r2, tail being the last stored record.  The <= is deliberate: a node at exactly the tail's distance may hold a triangle of
+ * equal d2 and smaller prim, which comes before the tail.
+ * Traversal is drt_renderer_nearest's: the root is pushed with its box2; a popped entry is dropped unless keep(box2); a leaf tests its
+ * triangles in order, and a listed triangle enters the list if there is room or it comes before the tail (which then leaves); an
+ * interior node computes box2 of both children and pushes each child that passes keep, the farther one first
+ * (b1 > b2 -> child 1).  The same 64-level stack bound applies.
+ * Mode DRT_NEAR_GATHER (0): the bound never shrinks.  counts[i] = total_i, all listed triangles, not just the stored ones, which is how
+ * a caller sees truncation; stored_i = min(cap_i, total_i) and the stored records are the first cap_i of the full list.  Each triangle
+ * lies in one leaf and the bound is constant, so neither the set nor the list depends on the traversal order, and the first K
+ * records of a longer list are the list at capacity K.  (The boxes cull as they do for drt_renderer_nearest: a triangle whose box2 is
+ * not below r2 is not listed.)  near may be NULL iff near_capacity == 0: a pure count.  Two passes give every triangle within a
+ * radius without a capacity guess: a count with capacity 0, an exclusive scan of the counts into offsets, and a fill.
+ * Mode DRT_NEAR_K (1): the cap_i nearest.  counts[i] = stored_i = min(cap_i, listed), the number stored.  A point with cap_i == 0 visits
+ * nothing and counts 0.  offsets[i] = K * i gives the K nearest triangles of every point as an [n, K] table in one pass.  fp32 box
+ * distances are not exactly conservative: a box2 can round above the dist2 of a triangle inside the box.  The stored records are
+ * therefore defined by this traversal, as drt_renderer_nearest's answer is, not by a brute force over all triangles, although on
+ * every input tested they equal one.
+ * counts may be NULL; both near and counts NULL is DRT_ERR_INVALID.  A result depends on the point, the scene, cap_i and the mode only.
+ * An empty scene lists nothing.
+ * What this is not: point-to-point neighbours (the records are triangles of the mesh, not other query points); alpha-tested lists; a
+ * large-K structure -- the insert moves one record per step, so the cost of a triangle that arrives out of order grows with the
+ * capacity, which suits a small K.  Slot 0 of a mode-K list has drt_renderer_nearest's d2, but on an exact tie it holds the smaller
+ * prim, not the first one found.
+ * Conventions and errors are drt_renderer_list_hits', checked in its order: handles are checked before n == 0, then a mode outside
+ * {0, 1} is DRT_ERR_INVALID (checked first after the handles), n == 0 is a no-op, n < 2^31, all pointers are device pointers on the
+ * renderer's device, points, near and surf 16-byte aligned, offsets and counts 4-byte aligned, hip_stream NULL = the renderer's stream,
+ * the call only enqueues, in order with the other queries, a refitted device copy is the one queried, legal on a sharded renderer,
+ * DRT_ERR_UNSUPPORTED beyond 64 levels, DRT_ERR_INVALID while an asynchronous batch is pending.  The framebuffer, accumulation, sample
+ * count, counters, kernel info and kernel span are not touched. */
+typedef struct drt_near      { float d2; int32_t prim; float u, v; } drt_near;                           /* 16 B */
+typedef struct drt_near_surf { float point[3]; float side; } drt_near_surf;                              /* 16 B */
+#define DRT_NEAR_GATHER 0
+#define DRT_NEAR_K      1
+int           drt_renderer_nearest_list(drt_renderer *r, const drt_scene *scene, const drt_point *points, const uint32_t *offsets,
+                                        drt_near *near, drt_near_surf *surf, uint32_t near_capacity, uint32_t *counts, uint32_t n,
+                                        int32_t mode, void *hip_stream);
 
 /* ---- sphere casts (new; the first contact of a moving sphere with the mesh) ----
  * One cast = a drt_ray (org o, tmin, dir d, tmax, read as drt_renderer_trace_rays reads it: dir as given, t in units of |d|,

@@ -31,6 +31,9 @@ def pretty(name):
         f = int(m.group(1))
         what = VARIANT[f & 6].replace("lean", "materials" if f & 16 else "lean") + (", hbm-scene" if f & 8 else ", lds-scene") + (", deep stacks" if f & 32 else "") + (", statistics build" if f & 1 else "")
         return "path_pool<%d> (%s)" % (f, what)
+    m = re.search(r"near_list_kernelILb(\d)E", name)
+    if m:
+        return "near_list_kernel<%s>" % ("K" if m.group(1) == "1" else "GATHER")
     m = re.search(r"\d+(\w+_kernel)", name)
     return m.group(1) if m else name
 
@@ -39,7 +42,7 @@ def main():
     md = "--md" in sys.argv
     rows = []
     for src, extra in (("kernel_path_pool.hip", ()), ("kernel_path_pool.hip", ("-DDRT_POOL_EXT_TU",)), ("kernel_wave_queue.hip", ()),
-                       ("render_kernels.hip", ()), ("kernel_bvh_build.hip", ()), ("kernel_sphere_cast.hip", ())):
+                       ("render_kernels.hip", ()), ("kernel_bvh_build.hip", ()), ("kernel_sphere_cast.hip", ()), ("kernel_near_list.hip", ())):
         for r in remarks(src, extra):
             if "VGPRs" in r and not (extra and "ILi" in r["name"] and int(re.search(r"ILi(\d+)E", r["name"]).group(1)) < 16):
                 rows.append(r)
