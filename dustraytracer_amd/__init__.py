@@ -330,6 +330,7 @@ _sig("drt_renderer_crossings", C.c_int, _P, _P, _P, _P, C.c_uint32, _P)
 _sig("drt_renderer_sphere_cast", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P)
 _sig("drt_renderer_list_hits", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P)
 _sig("drt_renderer_nearest_list", C.c_int, _P, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_int32, _P)
+_sig("drt_renderer_overlap_boxes", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_renderer_inside", C.c_int, _P, _P, _P, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_renderer_signed_distance", C.c_int, _P, _P, _P, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_renderer_render_guides", C.c_int, _P, C.POINTER(_CameraPOD), _P, C.c_uint32, _P, _P)
@@ -615,6 +616,9 @@ HitList = collections.namedtuple("HitList", "splits t prim u v")        # every 
 KNearest = collections.namedtuple("KNearest", "d2 prim u v point side count")   # the k nearest triangles of points (Renderer.kNearest)
 NearList = collections.namedtuple("NearList", "splits d2 prim u v point side")  # every triangle within a radius, CSR (Renderer.withinRadius)
 NEAR_GATHER, NEAR_K = 0, 1                                              # drt.h DRT_NEAR_*
+BoxList = collections.namedtuple("BoxList", "splits prim")               # every triangle that touches boxes, CSR (Renderer.overlapBoxes)
+BoxTable = collections.namedtuple("BoxTable", "prim count")             # the first k triangles that touch boxes (Renderer.overlapBoxes, k=)
+OVERLAP_LIST, OVERLAP_ANY = 0, 1                                        # drt.h DRT_OVERLAP_*
 INSIDE_RULES = {"parity": 0, "winding": 1}                              # Renderer.inside / signedDistance: drt.h DRT_INSIDE_*
 TemporalHistory = collections.namedtuple("TemporalHistory", "color length moments variance weight")  # Renderer.GetTemporalHistory
 Guides = collections.namedtuple("Guides", "albedo normal t prim")  # first-hit guide buffers (Renderer.renderGuides)
@@ -726,6 +730,69 @@ def _point_batch(torch, dev, points, max_dist):
         packed = torch.empty((n, 4), dtype=torch.float32, device=dev)     # packed on the device, on the current stream
         packed[:, 0:3] = pts.to(dev) if from_numpy else pts
         packed[:, 3] = (md.to(dev) if from_numpy else md) if per_point else float(max_dist)
+    return packed, from_numpy
+
+
+def _box_batch(torch, dev, center, half, axes, lo, hi):
+    """(boxes [N, 16] float32 (drt_box: center, half, axis[3][3], pad) on `dev`, 16-byte aligned, came_from_numpy) from center [N, 3]
+    + half [N, 3] (+ axes [N, 3, 3], default the identity), from a packed [N, 16], or from lo [N, 3] + hi [N, 3]
+    (center = (lo + hi) / 2, half = (hi - lo) / 2 in float32).  Raises DrtError(ERR_INVALID) on a wrong dtype, shape or device."""
+    def bad(msg):
+        return DrtError(ERR_INVALID, msg)
+
+    def as_tensor(a, what, tail):
+        if isinstance(a, np.ndarray):
+            if a.dtype != np.float32:
+                raise bad("%s: dtype %s, float32 expected" % (what, a.dtype))
+            t = torch.from_numpy(np.ascontiguousarray(a))
+        elif torch.is_tensor(a):
+            if a.dtype != torch.float32:
+                raise bad("%s: dtype %s, torch.float32 expected" % (what, a.dtype))
+            if a.device != dev:
+                raise bad("%s: on %s, the renderer is on %s" % (what, a.device, dev))
+            t = a
+        else:
+            raise bad("%s: a numpy array or a torch tensor expected" % what)
+        if t.dim() != 1 + len(tail) or tuple(t.shape[1:]) != tail:
+            raise bad("%s: shape %s, [N%s] expected" % (what, tuple(t.shape), "".join(", %d" % d for d in tail)))
+        return t
+
+    corners = lo is not None or hi is not None
+    if corners and (lo is None or hi is None or center is not None or half is not None):
+        raise bad("boxes: lo= and hi= come together and without center / half")
+    if not corners and center is None:
+        raise bad("boxes: center and half, a packed [N, 16] or lo= and hi= expected")
+    given = [a for a in (center, half, axes, lo, hi) if a is not None]
+    if len({isinstance(a, np.ndarray) for a in given}) > 1:
+        raise bad("mix of numpy arrays and device tensors")
+    from_numpy = isinstance(given[0], np.ndarray)
+    up = (lambda t: t.to(dev)) if from_numpy else (lambda t: t)
+    if not corners and half is None:
+        packed = up(as_tensor(center, "boxes", (16,)))
+        if axes is not None:
+            raise bad("packed boxes carry their own axes")
+        if not packed.is_contiguous() or packed.data_ptr() % 16:
+            packed = packed.contiguous().clone()
+        return packed, from_numpy
+    if corners:
+        a, b = up(as_tensor(lo, "lo", (3,))), up(as_tensor(hi, "hi", (3,)))
+        if a.shape[0] != b.shape[0]:
+            raise bad("lo and hi hold %d and %d boxes" % (a.shape[0], b.shape[0]))
+        c, h = (a + b) / 2, (b - a) / 2
+    else:
+        c, h = up(as_tensor(center, "center", (3,))), up(as_tensor(half, "half", (3,)))
+        if c.shape[0] != h.shape[0]:
+            raise bad("center and half hold %d and %d boxes" % (c.shape[0], h.shape[0]))
+    n = c.shape[0]
+    packed = torch.zeros((n, 16), dtype=torch.float32, device=dev)        # packed on the device, on the current stream
+    packed[:, 0:3], packed[:, 3:6] = c, h
+    if axes is None:
+        packed[:, 6], packed[:, 10], packed[:, 14] = 1.0, 1.0, 1.0
+    else:
+        ax = up(as_tensor(axes, "axes", (3, 3)))
+        if ax.shape[0] != n:
+            raise bad("axes hold %d boxes, center %d" % (ax.shape[0], n))
+        packed[:, 6:15] = ax.reshape(n, 9)
     return packed, from_numpy
 
 
@@ -974,6 +1041,92 @@ class Renderer:
             return NearList(splits.cpu().numpy(), h[:, 0].copy(), h.view(np.int32)[:, 1].copy(), h[:, 2].copy(), h[:, 3].copy(),
                             s[:, 0:3].copy(), s[:, 3].copy())
         return NearList(splits, near[:, 0], near.view(torch.int32)[:, 1], near[:, 2], near[:, 3], surf[:, 0:3], surf[:, 3])
+
+    def overlapBoxes(self, scene, center=None, half=None, axes=None, k=None, lo=None, hi=None):
+        """The triangles that touch each query box, in ascending triangle index (drt_renderer_overlap_boxes in mode
+        DRT_OVERLAP_LIST).  Boxes: center [N, 3] + half [N, 3] (+ axes [N, 3, 3], axes[i, j] the world direction of box i's axis j,
+        used as given; default axis-aligned), or a packed [N, 16] (drt_box), or lo= / hi= [N, 3] corners
+        (center = (lo + hi) / 2, half = (hi - lo) / 2 in float32).  Touching counts; alpha cut-outs are ignored.
+        k=None: BoxList(splits [N + 1] int32, prim [M] int32), box i's triangles at [splits[i], splits[i + 1]) -- a count with
+        capacity 0, a cumulative sum on the device, and a fill; the total is read back between them to size the result: that read
+        is this call's one synchronisation with the device.  k=K: BoxTable(prim [N, K] int32, count [N] int32) in one pass: the
+        first K of each list, -1 behind a shorter one; count is the number listed, stored or not.  Device tensors in, device
+        tensors out (enqueued on the current torch stream); numpy in, numpy out."""
+        if k is not None and (isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1):
+            raise DrtError(ERR_INVALID, "k = %r: a positive integer or None expected" % (k,))
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        boxes, from_numpy = _box_batch(torch, dev, center, half, axes, lo, hi)
+        n = boxes.shape[0]
+        host = (lambda t: t.cpu().numpy()) if from_numpy else (lambda t: t)
+        if k is not None:
+            k = int(k)
+            if n * k >= 2 ** 31:
+                raise DrtError(ERR_INVALID, "%d boxes x %d slots: fewer than 2^31 records expected" % (n, k))
+            prim = torch.empty((n, k), dtype=torch.int32, device=dev)
+            count = torch.empty(n, dtype=torch.int32, device=dev)
+            if n:
+                offsets = (torch.arange(n + 1, dtype=torch.int64, device=dev) * k).to(torch.int32)
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                _check(_lib.drt_renderer_overlap_boxes(self._h, scene._h, boxes.data_ptr(), offsets.data_ptr(), prim.data_ptr(), n * k,
+                                                       count.data_ptr(), n, OVERLAP_LIST, stream))
+            return BoxTable(host(prim), host(count))
+        splits = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        total = 0
+        if n:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            counts = torch.empty(n, dtype=torch.int32, device=dev)
+            no_room = torch.zeros(n + 1, dtype=torch.int32, device=dev)       # capacity 0: every segment is empty
+            _check(_lib.drt_renderer_overlap_boxes(self._h, scene._h, boxes.data_ptr(), no_room.data_ptr(), None, 0, counts.data_ptr(), n,
+                                                   OVERLAP_LIST, stream))
+            splits[1:] = torch.cumsum(counts.to(torch.int64), dim=0)
+            total = int(splits[-1].item())       # the one synchronisation: the result's size
+            if total >= 2 ** 31:
+                raise DrtError(ERR_INVALID, "%d triangles in all: fewer than 2^31 expected (split the boxes)" % total)
+        splits = splits.to(torch.int32)
+        prim = torch.empty(total, dtype=torch.int32, device=dev)
+        if total:
+            _check(_lib.drt_renderer_overlap_boxes(self._h, scene._h, boxes.data_ptr(), splits.data_ptr(), prim.data_ptr(), total, None, n,
+                                                   OVERLAP_LIST, stream))
+        return BoxList(host(splits), host(prim))
+
+    def overlapsAny(self, scene, center=None, half=None, axes=None, lo=None, hi=None):
+        """Whether any triangle touches each query box: bool [N] (drt_renderer_overlap_boxes in mode DRT_OVERLAP_ANY, whose
+        traversal ends at the first triangle found).  Boxes and conventions as overlapBoxes."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        boxes, from_numpy = _box_batch(torch, dev, center, half, axes, lo, hi)
+        n = boxes.shape[0]
+        counts = torch.empty(n, dtype=torch.int32, device=dev)
+        if n:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(_lib.drt_renderer_overlap_boxes(self._h, scene._h, boxes.data_ptr(), None, None, 0, counts.data_ptr(), n, OVERLAP_ANY, stream))
+        res = counts > 0
+        return res.cpu().numpy() if from_numpy else res
+
+    def voxelize(self, scene, resolution, lo=None, hi=None):
+        """Conservative surface voxelisation: a bool [Z, Y, X] device tensor, true where a triangle touches the (closed) cell, over
+        the box (lo, hi), by default the scene's bounds.  resolution: an int or (X, Y, Z).  The cells are laid out as sdfGrid lays
+        out its centres -- cell i of axis k has the centre lo[k] + (i + 0.5) * step and the half extent step / 2, step =
+        (hi[k] - lo[k]) / resolution[k] -- and the boxes are made on the device and asked in mode DRT_OVERLAP_ANY."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        res = (int(resolution),) * 3 if isinstance(resolution, (int, np.integer)) else tuple(int(v) for v in resolution)
+        if len(res) != 3 or min(res) < 1:
+            raise DrtError(ERR_INVALID, "resolution: a positive int or three of them expected")
+        if lo is None or hi is None:
+            nodes = scene.m_BVHNodes
+            if len(nodes) == 0:
+                raise DrtError(ERR_INVALID, "voxelize: an empty scene has no bounds; give lo and hi")
+            lo = nodes[-1]["bmin"] if lo is None else lo                      # the root is the last node
+            hi = nodes[-1]["bmax"] if hi is None else hi
+        lo, hi = np.asarray(lo, np.float32).reshape(3), np.asarray(hi, np.float32).reshape(3)
+        step = [float(hi[k] - lo[k]) / res[k] for k in range(3)]
+        axes = [float(lo[k]) + (torch.arange(res[k], dtype=torch.float32, device=dev) + 0.5) * step[k] for k in range(3)]
+        z, y, x = torch.meshgrid(axes[2], axes[1], axes[0], indexing="ij")
+        center = torch.stack([x, y, z], dim=-1).reshape(-1, 3)
+        half = torch.tensor([0.5 * v for v in step], dtype=torch.float32, device=dev).expand(center.shape[0], 3)
+        return self.overlapsAny(scene, center, half).reshape(res[2], res[1], res[0])
 
     @staticmethod
     def _inside_rule(rule):

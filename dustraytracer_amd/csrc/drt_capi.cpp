@@ -19,6 +19,7 @@
 #include "crossings.hpp"
 #include "list_hits.hpp"
 #include "near_list.hpp"
+#include "overlap.hpp"
 #include "bvh_build_device.hpp"
 #include "png_decode.hpp"
 
@@ -1001,6 +1002,50 @@ int drt_renderer_nearest_list(drt_renderer *r, const drt_scene *scene, const drt
     a.heads = r->rq_heads.ptr;
     a.stack_hbm = r->rq_stack.ptr;
     HIP_TRY(launch_near_list(r->view, mode == DRT_NEAR_K, a, r->num_cus, s));
+    return query_recorded(r, s);
+}
+
+// ------------------------------------------------------------------ box overlap queries (kernel_overlap.hip)
+// Validated in drt_renderer_nearest_list's order with the mode first after the handles, ordered and given scratch as
+// drt_renderer_list_hits is: the kernel shares the claim heads and the occlusion query's HBM stack.  Mode LIST: counts may be null,
+// prims may be null iff prims_capacity == 0 (a pure count), not both.  Mode ANY: no prims, no capacity, offsets is not read.
+int drt_renderer_overlap_boxes(drt_renderer *r, const drt_scene *scene, const drt_box *boxes, const uint32_t *offsets, int32_t *prims,
+                               uint32_t prims_capacity, uint32_t *counts, uint32_t n, int32_t mode, void *hip_stream) {
+    if (!r || !scene) return fail(DRT_ERR_INVALID, "null argument");
+    if (mode != DRT_OVERLAP_LIST && mode != DRT_OVERLAP_ANY)
+        return fail(DRT_ERR_INVALID, "mode " + std::to_string(mode) + ": 0 (list) or 1 (any) expected");
+    if (n == 0) return DRT_OK;
+    const bool any = mode == DRT_OVERLAP_ANY;
+    if (!boxes || (!any && !offsets)) return fail(DRT_ERR_INVALID, "null box or offset pointer");
+    if (any) {
+        if (prims || prims_capacity != 0) return fail(DRT_ERR_INVALID, "mode any writes no list: prims must be null and prims_capacity 0");
+        if (!counts) return fail(DRT_ERR_INVALID, "mode any: counts is null: nothing to write");
+        offsets = nullptr;                     // (not read)
+    } else {
+        if (!prims && !counts) return fail(DRT_ERR_INVALID, "prims and counts are both null: nothing to write");
+        if ((prims == nullptr) != (prims_capacity == 0)) return fail(DRT_ERR_INVALID, "prims must be null if and only if prims_capacity is 0");
+    }
+    if (((uintptr_t)boxes & 15u) != 0 || ((uintptr_t)prims & 3u) != 0 || ((uintptr_t)offsets & 3u) != 0 || ((uintptr_t)counts & 3u) != 0)
+        return fail(DRT_ERR_INVALID, "boxes must be 16-byte aligned, offsets, prims and counts 4-byte aligned");
+    if (n > 0x7fffffffu) return fail(DRT_ERR_INVALID, "at most 2^31 - 1 boxes per call");
+    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
+    HIP_TRY(hipSetDevice(r->device));
+    (void)hipGetLastError();                   // (see render_batch_impl: only this call's own errors count)
+    if (!on_renderer_device(r, boxes) || (offsets && !on_renderer_device(r, offsets)) || (prims && !on_renderer_device(r, prims)) ||
+        (counts && !on_renderer_device(r, counts)))
+        return fail(DRT_ERR_INVALID, "boxes, offsets, prims and counts must be device memory on the renderer's device");
+    if (int rc = upload_scene(r, scene)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : r->stream;
+    if (int rc = query_order(r, s)) return rc;
+    if (int rc = traversal_scratch(r, s, true, true)) return rc;
+    OverlapArgs a;
+    a.boxes = boxes; a.offsets = offsets; a.prims = prims; a.counts = counts;
+    a.prims_capacity = prims_capacity; a.n = n;
+    a.stack_levels = (uint32_t)std::max(1, r->bvh_depth);
+    a.refill_min = (uint32_t)r->rq_refill_min;
+    a.heads = r->rq_heads.ptr;
+    a.stack_hbm = r->rq_stack.ptr;
+    HIP_TRY(launch_overlap(r->view, any, a, r->num_cus, s));
     return query_recorded(r, s);
 }
 

@@ -329,6 +329,15 @@ public:
                      uint32_t near_capacity, uint32_t *counts, uint32_t n, int32_t mode, void *stream = nullptr) {
         drt::check(drt_renderer_nearest_list(handle, scene.handle, points, offsets, near, surf, near_capacity, counts, n, mode, stream));
     }
+    // new: the triangles that touch each query box, an oriented box drt_box {center, half, axis[3]} (drt_renderer_overlap_boxes).  mode
+    // DRT_OVERLAP_LIST: box i's triangle indices in ascending order go to prims[offsets[i] .. offsets[i+1]), clamped to prims_capacity,
+    // -1 behind them, counts[i] = all listed, stored or not; counts may be null, prims may be null iff prims_capacity == 0.  mode
+    // DRT_OVERLAP_ANY: counts[i] = 0 or 1, offsets is not read, prims must be null and prims_capacity 0.  Device arrays, enqueued on
+    // `stream`.
+    void OverlapBoxes(const Scene &scene, const drt_box *boxes, const uint32_t *offsets, int32_t *prims, uint32_t prims_capacity,
+                      uint32_t *counts, uint32_t n, int32_t mode, void *stream = nullptr) {
+        drt::check(drt_renderer_overlap_boxes(handle, scene.handle, boxes, offsets, prims, prims_capacity, counts, n, mode, stream));
+    }
     // new: RayGen's primary rays of n_cams cameras for a width x height image, frame `frame_index` (drt_renderer_camera_rays): a device
     // drt_path_ray[n_cams * width * height], enqueued on `stream`
     void CameraRays(const drt_camera *cams, uint32_t n_cams, uint32_t width, uint32_t height, uint32_t frame_index, drt_path_ray *rays,

@@ -29,8 +29,8 @@ extern "C" {
  * entry points (drt_renderer_trace_rays / _occluded), the guide / denoise entry points, the refit entry points and the camera-ray /
  * radiance entry points, the upscaling entry points, the adaptive-sampling entry points, the nearest-surface entry point
  * (drt_renderer_nearest), the crossing-count entry points (drt_renderer_crossings / _inside / _signed_distance), the hit-list entry
- * point (drt_renderer_list_hits), the sphere-cast entry point (drt_renderer_sphere_cast) and the nearest-list entry point
- * (drt_renderer_nearest_list) are additions to it */
+ * point (drt_renderer_list_hits), the sphere-cast entry point (drt_renderer_sphere_cast), the nearest-list entry point
+ * (drt_renderer_nearest_list) and the box-overlap entry point (drt_renderer_overlap_boxes) are additions to it */
 #define DRT_ABI_VERSION 2
 
 typedef enum {
@@ -415,6 +415,65 @@ typedef struct drt_near_surf { float point[3]; float side; } drt_near_surf;     
 int           drt_renderer_nearest_list(drt_renderer *r, const drt_scene *scene, const drt_point *points, const uint32_t *offsets,
                                         drt_near *near, drt_near_surf *surf, uint32_t near_capacity, uint32_t *counts, uint32_t n,
                                         int32_t mode, void *hip_stream);
+
+/* ---- box overlap queries (new; the triangles that touch each query box -- the first query about a volume) ----
+ * One query = a drt_box: 64 bytes, 16-byte aligned, center[3], half[3], axis[3][3] and one pad word that is ignored.  axis[k] is the
+ * world direction of box axis k, used as given: not normalised, not orthogonalised.  An axis-aligned box is axis = identity; with
+ * identity axes every product below is exact, so the axis-aligned case needs no code path of its own.
+ * All arithmetic is fp32 with one rounding per operation, in the order written.  dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z;
+ * cross(a, b) = (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x).  fminf / fmaxf drop a NaN operand, as the box distance of
+ * drt_renderer_nearest does.  Alpha cut-outs are ignored (a geometric query).
+ * World bounds of the query, computed once per query: ext[j] = (|axis[0][j]| half[0] + |axis[1][j]| half[1]) + |axis[2][j]| half[2],
+ * qmin = center - ext, qmax = center + ext.  (They hold the box when the axes are orthonormal.  The box itself is the set of x with
+ * |dot(axis[k], x - center)| <= half[k]; axes shorter than 1 describe a box larger than these bounds, and the cull then decides.)
+ * Node cull: a box (bmin, bmax) passes iff, on all three axes, qmin[j] <= bmax[j] && bmin[j] <= qmax[j].  The comparisons are closed
+ * and no arithmetic is done on the node.  A NaN anywhere in the query makes some qmin / qmax NaN (an infinite half beside a zero axis
+ * component does too: 0 * inf); then the root fails, so a NaN query lists nothing.
+ * Traversal: the root is tested against the scene's root box; an interior node pushes each child that passes, child 2 first; a leaf
+ * tests its triangles in order.  The same 64-level stack bound applies.  Each triangle lies in one leaf and the cull never changes
+ * during a query, so the set of listed triangles does not depend on the traversal order.  The boxes cull as they do for the other
+ * queries: a triangle whose leaf the cull rejects is not listed, whatever the triangle test would say -- the stored triangle is
+ * (v0, e1, e2), and v0 + e1 can round one ulp outside a node box built from the real v1.
+ * Triangle test: the separating-axis test of Akenine-Moller (2001) in the box's frame, on the stored (v0, e1, e2).
+ * a = v0 - center; for k = 0..2: p0[k] = dot(axis[k], a), f1[k] = dot(axis[k], e1), f2[k] = dot(axis[k], e2); p1 = p0 + f1,
+ * p2 = p0 + f2, g = f2 - f1.  With min3(x, y, z) = fminf(fminf(x, y), z) and max3 the same with fmaxf:
+ *   box axes, for each k: ok iff min3(p0[k], p1[k], p2[k]) <= half[k] && max3(p0[k], p1[k], p2[k]) >= -half[k]
+ *   plane: n = cross(f1, f2), d = dot(n, p0), r = (|n.x| half[0] + |n.y| half[1]) + |n.z| half[2]; ok iff fabsf(d) <= r
+ *   nine edge axes L = cross(unit_k, E) for E in (f1, g, f2), k in 0..2, each with its two non-zero components only; s_i over
+ *   i = 0, 1, 2 (all three projections, not the two-value shortcut), left operand first:
+ *     k = 0, L = (0, -E.z, E.y): s_i = (-E.z) p_i.y + E.y p_i.z, r = half[1] |E.z| + half[2] |E.y|
+ *     k = 1, L = (E.z, 0, -E.x): s_i = E.z p_i.x + (-E.x) p_i.z, r = half[0] |E.z| + half[2] |E.x|
+ *     k = 2, L = (-E.y, E.x, 0): s_i = (-E.y) p_i.x + E.x p_i.y, r = half[0] |E.y| + half[1] |E.x|
+ *     ok iff min3(s0, s1, s2) <= r && max3(s0, s1, s2) >= -r
+ * The triangle is listed iff all 13 are ok.  Touching counts.  half = 0 is a point or a flat box, and it works.  A zero-area triangle
+ * passes its zero cross axes with 0 <= 0, and the other axes decide it.  Only the predicate leaves the kernel, so bit for bit here
+ * means that the 13 comparisons are made on the same rounded values.
+ * Mode DRT_OVERLAP_LIST (0): segments are exactly drt_renderer_list_hits': offsets holds n + 1 uint32 values; box i owns
+ * prims[offsets[i] .. offsets[i+1]).  Its capacity is cap_i = offsets[i+1] > offsets[i] ? offsets[i+1] - offsets[i] : 0, then clamped
+ * so that offsets[i] + cap_i <= prims_capacity (offsets[i] >= prims_capacity gives 0).  The call writes prims[offsets[i] + j] for
+ * j < cap_i and nothing else in prims, whatever offsets contains (segments that overlap are written by more than one box and hold no
+ * defined list).  The records are int32 triangle indices in ascending order; unused slots hold -1.  counts[i] is the total number
+ * listed, stored or not, which is how a caller sees truncation; the first K of a longer list are the list at capacity K.  prims may
+ * be NULL iff prims_capacity == 0: a pure count.  counts may be NULL; both prims and counts NULL is DRT_ERR_INVALID.  Two passes give
+ * every triangle of every box without a capacity guess: a count with capacity 0, an exclusive scan of the counts into offsets, a fill.
+ * Mode DRT_OVERLAP_ANY (1): the traversal ends at the first listed triangle, and counts[i] is 0 or 1.  prims must be NULL and
+ * prims_capacity 0; offsets is not read; counts NULL is DRT_ERR_INVALID.
+ * A result depends on the box, the scene, cap_i and the mode only.  An empty scene lists nothing.
+ * What this is not: box-versus-box (the other side is always the mesh's triangles); clipped polygons (a triangle is listed whole, by
+ * index); a large-list structure -- the insert is the one-record-per-step insert of drt_renderer_list_hits, so the cost of a triangle
+ * that arrives out of order grows with the capacity, and a box that lists thousands is better counted than stored.
+ * Conventions and errors are drt_renderer_nearest_list's, checked in its order: handles are checked before n == 0, then a mode outside
+ * {0, 1} is DRT_ERR_INVALID (checked first after the handles), n == 0 is a no-op, n < 2^31, all pointers are device pointers on the
+ * renderer's device, boxes 16-byte aligned, offsets, prims and counts 4-byte aligned, hip_stream NULL = the renderer's stream, the
+ * call only enqueues, in order with the other queries, a refitted device copy is the one queried, legal on a sharded renderer,
+ * DRT_ERR_UNSUPPORTED beyond 64 levels, DRT_ERR_INVALID while an asynchronous batch is pending.  The framebuffer, accumulation, sample
+ * count, counters, kernel info and kernel span are not touched. */
+typedef struct drt_box { float center[3]; float half[3]; float axis[3][3]; float pad; } drt_box;       /* 64 B */
+#define DRT_OVERLAP_LIST 0
+#define DRT_OVERLAP_ANY  1
+int           drt_renderer_overlap_boxes(drt_renderer *r, const drt_scene *scene, const drt_box *boxes, const uint32_t *offsets,
+                                         int32_t *prims, uint32_t prims_capacity, uint32_t *counts, uint32_t n, int32_t mode,
+                                         void *hip_stream);
 
 /* ---- sphere casts (new; the first contact of a moving sphere with the mesh) ----
  * One cast = a drt_ray (org o, tmin, dir d, tmax, read as drt_renderer_trace_rays reads it: dir as given, t in units of |d|,
