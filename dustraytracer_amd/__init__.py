@@ -331,6 +331,7 @@ _sig("drt_renderer_sphere_cast", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P)
 _sig("drt_renderer_list_hits", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P)
 _sig("drt_renderer_nearest_list", C.c_int, _P, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_renderer_overlap_boxes", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_int32, _P)
+_sig("drt_renderer_overlap_triangles", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_renderer_inside", C.c_int, _P, _P, _P, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_renderer_signed_distance", C.c_int, _P, _P, _P, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_renderer_render_guides", C.c_int, _P, C.POINTER(_CameraPOD), _P, C.c_uint32, _P, _P)
@@ -618,6 +619,8 @@ NearList = collections.namedtuple("NearList", "splits d2 prim u v point side")  
 NEAR_GATHER, NEAR_K = 0, 1                                              # drt.h DRT_NEAR_*
 BoxList = collections.namedtuple("BoxList", "splits prim")               # every triangle that touches boxes, CSR (Renderer.overlapBoxes)
 BoxTable = collections.namedtuple("BoxTable", "prim count")             # the first k triangles that touch boxes (Renderer.overlapBoxes, k=)
+TriList = collections.namedtuple("TriList", "splits prim")               # every triangle that query triangles touch, CSR (Renderer.overlapTriangles)
+TriTable = collections.namedtuple("TriTable", "prim count")             # the first k triangles that query triangles touch (Renderer.overlapTriangles, k=)
 OVERLAP_LIST, OVERLAP_ANY = 0, 1                                        # drt.h DRT_OVERLAP_*
 INSIDE_RULES = {"parity": 0, "winding": 1}                              # Renderer.inside / signedDistance: drt.h DRT_INSIDE_*
 TemporalHistory = collections.namedtuple("TemporalHistory", "color length moments variance weight")  # Renderer.GetTemporalHistory
@@ -730,6 +733,37 @@ def _point_batch(torch, dev, points, max_dist):
         packed = torch.empty((n, 4), dtype=torch.float32, device=dev)     # packed on the device, on the current stream
         packed[:, 0:3] = pts.to(dev) if from_numpy else pts
         packed[:, 3] = (md.to(dev) if from_numpy else md) if per_point else float(max_dist)
+    return packed, from_numpy
+
+
+def _tri_batch(torch, dev, tris):
+    """(triangles [N, 12] float32 (drt_tri: v[3][3], three pad words) on `dev`, 16-byte aligned, came_from_numpy) from vertices
+    [N, 3, 3] or a packed [N, 12].  Raises DrtError(ERR_INVALID) on a wrong dtype, shape or device, as _box_batch does."""
+    def bad(msg):
+        return DrtError(ERR_INVALID, msg)
+
+    if isinstance(tris, np.ndarray):
+        if tris.dtype != np.float32:
+            raise bad("tris: dtype %s, float32 expected" % tris.dtype)
+        t, from_numpy = torch.from_numpy(np.ascontiguousarray(tris)), True
+    elif torch.is_tensor(tris):
+        if tris.dtype != torch.float32:
+            raise bad("tris: dtype %s, torch.float32 expected" % tris.dtype)
+        if tris.device != dev:
+            raise bad("tris: on %s, the renderer is on %s" % (tris.device, dev))
+        t, from_numpy = tris, False
+    else:
+        raise bad("tris: a numpy array or a torch tensor expected")
+    shape = tuple(t.shape)
+    if len(shape) == 2 and shape[1] == 12:
+        packed = t.to(dev) if from_numpy else t
+        if not packed.is_contiguous() or packed.data_ptr() % 16:
+            packed = packed.contiguous().clone()
+        return packed, from_numpy
+    if len(shape) != 3 or shape[1:] != (3, 3):
+        raise bad("tris: shape %s, [N, 3, 3] or a packed [N, 12] expected" % (shape,))
+    packed = torch.zeros((shape[0], 12), dtype=torch.float32, device=dev)     # packed on the device, on the current stream
+    packed[:, 0:9] = (t.to(dev) if from_numpy else t).reshape(shape[0], 9)
     return packed, from_numpy
 
 
@@ -1103,6 +1137,105 @@ class Renderer:
             _check(_lib.drt_renderer_overlap_boxes(self._h, scene._h, boxes.data_ptr(), None, None, 0, counts.data_ptr(), n, OVERLAP_ANY, stream))
         res = counts > 0
         return res.cpu().numpy() if from_numpy else res
+
+    def overlapTriangles(self, scene, tris, k=None):
+        """The mesh triangles that each query triangle touches, in ascending triangle index (drt_renderer_overlap_triangles in mode
+        DRT_OVERLAP_LIST).  tris: vertices [N, 3, 3] float32, or a packed [N, 12] (drt_tri).  Touching counts: a shared vertex or
+        edge is a touch, and a triangle of the scene given as a query lists itself and its neighbours.  A query with a NaN or an
+        infinity lists nothing.  Alpha cut-outs are ignored.
+        k=None: TriList(splits [N + 1] int32, prim [M] int32), query i's triangles at [splits[i], splits[i + 1]) -- a count with
+        capacity 0, a cumulative sum on the device, and a fill; the total is read back between them to size the result: that read
+        is this call's one synchronisation with the device.  k=K: TriTable(prim [N, K] int32, count [N] int32) in one pass: the
+        first K of each list, -1 behind a shorter one; count is the number listed, stored or not.  Device tensors in, device
+        tensors out (enqueued on the current torch stream); numpy in, numpy out."""
+        if k is not None and (isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1):
+            raise DrtError(ERR_INVALID, "k = %r: a positive integer or None expected" % (k,))
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        packed, from_numpy = _tri_batch(torch, dev, tris)
+        n = packed.shape[0]
+        host = (lambda t: t.cpu().numpy()) if from_numpy else (lambda t: t)
+        if k is not None:
+            k = int(k)
+            if n * k >= 2 ** 31:
+                raise DrtError(ERR_INVALID, "%d triangles x %d slots: fewer than 2^31 records expected" % (n, k))
+            prim = torch.empty((n, k), dtype=torch.int32, device=dev)
+            count = torch.empty(n, dtype=torch.int32, device=dev)
+            if n:
+                offsets = (torch.arange(n + 1, dtype=torch.int64, device=dev) * k).to(torch.int32)
+                stream = torch.cuda.current_stream(dev).cuda_stream
+                _check(_lib.drt_renderer_overlap_triangles(self._h, scene._h, packed.data_ptr(), offsets.data_ptr(), prim.data_ptr(), n * k,
+                                                           count.data_ptr(), n, OVERLAP_LIST, stream))
+            return TriTable(host(prim), host(count))
+        splits = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        total = 0
+        if n:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            counts = torch.empty(n, dtype=torch.int32, device=dev)
+            no_room = torch.zeros(n + 1, dtype=torch.int32, device=dev)       # capacity 0: every segment is empty
+            _check(_lib.drt_renderer_overlap_triangles(self._h, scene._h, packed.data_ptr(), no_room.data_ptr(), None, 0, counts.data_ptr(), n,
+                                                       OVERLAP_LIST, stream))
+            splits[1:] = torch.cumsum(counts.to(torch.int64), dim=0)
+            total = int(splits[-1].item())       # the one synchronisation: the result's size
+            if total >= 2 ** 31:
+                raise DrtError(ERR_INVALID, "%d triangles in all: fewer than 2^31 expected (split the queries)" % total)
+        splits = splits.to(torch.int32)
+        prim = torch.empty(total, dtype=torch.int32, device=dev)
+        if total:
+            _check(_lib.drt_renderer_overlap_triangles(self._h, scene._h, packed.data_ptr(), splits.data_ptr(), prim.data_ptr(), total, None, n,
+                                                       OVERLAP_LIST, stream))
+        return TriList(host(splits), host(prim))
+
+    def intersectsAny(self, scene, tris):
+        """Whether each query triangle touches any triangle of the mesh: bool [N] (drt_renderer_overlap_triangles in mode
+        DRT_OVERLAP_ANY, whose traversal ends at the first triangle found).  Triangles and conventions as overlapTriangles."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        packed, from_numpy = _tri_batch(torch, dev, tris)
+        n = packed.shape[0]
+        counts = torch.empty(n, dtype=torch.int32, device=dev)
+        if n:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(_lib.drt_renderer_overlap_triangles(self._h, scene._h, packed.data_ptr(), None, None, 0, counts.data_ptr(), n, OVERLAP_ANY, stream))
+        res = counts > 0
+        return res.cpu().numpy() if from_numpy else res
+
+    def selfIntersections(self, scene, positions=None):
+        """Where the scene's mesh cuts itself: int32 [P, 2], the pairs i < j of triangle indices (tree order, as every query reports
+        them) that touch and share no vertex position, sorted by (i, j).  The queries are the scene's own triangles in tree order:
+        by default the positions of the host scene's m_PrimitivesBuffer; with positions= [n, 3, 3] float32 in load order, as refit
+        takes them (for a refitted device copy), mapped through triangleOrder().  It runs overlapTriangles, then on the device drops
+        j <= i and every pair in which any vertex of one triangle is bit-equal to a vertex of the other: neighbours always touch.
+        Two neighbours that also cut each other are therefore not reported.  Degenerate triangles are queried like any other.
+        positions as a device tensor: a device tensor comes back; else a numpy array."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        n = _lib.drt_scene_triangle_count(scene._h)
+        as_tensor = torch.is_tensor(positions)
+        if positions is None:
+            verts = torch.from_numpy(np.ascontiguousarray(scene.m_PrimitivesBuffer["vertex"]["position"], np.float32).reshape(n, 3, 3)).to(dev)
+        else:
+            if isinstance(positions, np.ndarray):
+                if positions.dtype != np.float32:
+                    raise DrtError(ERR_INVALID, "positions: dtype %s, float32 expected" % positions.dtype)
+                positions = torch.from_numpy(np.ascontiguousarray(positions)).to(dev)
+            elif not as_tensor:
+                raise DrtError(ERR_INVALID, "positions: a numpy array or a torch tensor expected")
+            if positions.dtype != torch.float32 or positions.device != dev or positions.numel() != 9 * n:
+                raise DrtError(ERR_INVALID, "positions: %s %s with %d values, float32 [%d, 3, 3] on %s expected"
+                               % (positions.dtype, positions.device, positions.numel(), n, dev))
+            order = torch.from_numpy(scene.triangleOrder().astype(np.int64)).to(dev)
+            verts = positions.reshape(n, 3, 3)[order]
+        found = self.overlapTriangles(scene, verts.contiguous())
+        counts = (found.splits[1:] - found.splits[:-1]).to(torch.int64)
+        i = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=dev), counts)
+        j = found.prim.to(torch.int64)
+        later = j > i
+        i, j = i[later], j[later]
+        bits = verts.contiguous().view(torch.int32)
+        shared = (bits[i][:, :, None, :] == bits[j][:, None, :, :]).all(dim=-1).any(dim=2).any(dim=1)
+        pairs = torch.stack([i[~shared], j[~shared]], dim=1).to(torch.int32)
+        return pairs if as_tensor else pairs.cpu().numpy()
 
     def voxelize(self, scene, resolution, lo=None, hi=None):
         """Conservative surface voxelisation: a bool [Z, Y, X] device tensor, true where a triangle touches the (closed) cell, over

@@ -20,6 +20,7 @@
 #include "list_hits.hpp"
 #include "near_list.hpp"
 #include "overlap.hpp"
+#include "tri_overlap.hpp"
 #include "bvh_build_device.hpp"
 #include "png_decode.hpp"
 
@@ -1046,6 +1047,49 @@ int drt_renderer_overlap_boxes(drt_renderer *r, const drt_scene *scene, const dr
     a.heads = r->rq_heads.ptr;
     a.stack_hbm = r->rq_stack.ptr;
     HIP_TRY(launch_overlap(r->view, any, a, r->num_cus, s));
+    return query_recorded(r, s);
+}
+
+// ------------------------------------------------------------------ triangle overlap queries (kernel_tri_overlap.hip)
+// drt_renderer_overlap_boxes' checks in its order, word for word, and its scratch: the kernel shares the claim heads and the occlusion
+// query's HBM stack.
+int drt_renderer_overlap_triangles(drt_renderer *r, const drt_scene *scene, const drt_tri *tris, const uint32_t *offsets, int32_t *prims,
+                                   uint32_t prims_capacity, uint32_t *counts, uint32_t n, int32_t mode, void *hip_stream) {
+    if (!r || !scene) return fail(DRT_ERR_INVALID, "null argument");
+    if (mode != DRT_OVERLAP_LIST && mode != DRT_OVERLAP_ANY)
+        return fail(DRT_ERR_INVALID, "mode " + std::to_string(mode) + ": 0 (list) or 1 (any) expected");
+    if (n == 0) return DRT_OK;
+    const bool any = mode == DRT_OVERLAP_ANY;
+    if (!tris || (!any && !offsets)) return fail(DRT_ERR_INVALID, "null triangle or offset pointer");
+    if (any) {
+        if (prims || prims_capacity != 0) return fail(DRT_ERR_INVALID, "mode any writes no list: prims must be null and prims_capacity 0");
+        if (!counts) return fail(DRT_ERR_INVALID, "mode any: counts is null: nothing to write");
+        offsets = nullptr;                     // (not read)
+    } else {
+        if (!prims && !counts) return fail(DRT_ERR_INVALID, "prims and counts are both null: nothing to write");
+        if ((prims == nullptr) != (prims_capacity == 0)) return fail(DRT_ERR_INVALID, "prims must be null if and only if prims_capacity is 0");
+    }
+    if (((uintptr_t)tris & 15u) != 0 || ((uintptr_t)prims & 3u) != 0 || ((uintptr_t)offsets & 3u) != 0 || ((uintptr_t)counts & 3u) != 0)
+        return fail(DRT_ERR_INVALID, "tris must be 16-byte aligned, offsets, prims and counts 4-byte aligned");
+    if (n > 0x7fffffffu) return fail(DRT_ERR_INVALID, "at most 2^31 - 1 triangles per call");
+    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
+    HIP_TRY(hipSetDevice(r->device));
+    (void)hipGetLastError();                   // (see render_batch_impl: only this call's own errors count)
+    if (!on_renderer_device(r, tris) || (offsets && !on_renderer_device(r, offsets)) || (prims && !on_renderer_device(r, prims)) ||
+        (counts && !on_renderer_device(r, counts)))
+        return fail(DRT_ERR_INVALID, "tris, offsets, prims and counts must be device memory on the renderer's device");
+    if (int rc = upload_scene(r, scene)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : r->stream;
+    if (int rc = query_order(r, s)) return rc;
+    if (int rc = traversal_scratch(r, s, true, true)) return rc;
+    TriOverlapArgs a;
+    a.tris = tris; a.offsets = offsets; a.prims = prims; a.counts = counts;
+    a.prims_capacity = prims_capacity; a.n = n;
+    a.stack_levels = (uint32_t)std::max(1, r->bvh_depth);
+    a.refill_min = (uint32_t)r->rq_refill_min;
+    a.heads = r->rq_heads.ptr;
+    a.stack_hbm = r->rq_stack.ptr;
+    HIP_TRY(launch_tri_overlap(r->view, any, a, r->num_cus, s));
     return query_recorded(r, s);
 }
 

@@ -338,6 +338,12 @@ public:
                       uint32_t *counts, uint32_t n, int32_t mode, void *stream = nullptr) {
         drt::check(drt_renderer_overlap_boxes(handle, scene.handle, boxes, offsets, prims, prims_capacity, counts, n, mode, stream));
     }
+    // new: the mesh triangles that each query triangle touches, a drt_tri {v[3][3]} (drt_renderer_overlap_triangles).  Modes, segments,
+    // counts and the null rules are OverlapBoxes'.  Device arrays, enqueued on `stream`.
+    void OverlapTriangles(const Scene &scene, const drt_tri *tris, const uint32_t *offsets, int32_t *prims, uint32_t prims_capacity,
+                          uint32_t *counts, uint32_t n, int32_t mode, void *stream = nullptr) {
+        drt::check(drt_renderer_overlap_triangles(handle, scene.handle, tris, offsets, prims, prims_capacity, counts, n, mode, stream));
+    }
     // new: RayGen's primary rays of n_cams cameras for a width x height image, frame `frame_index` (drt_renderer_camera_rays): a device
     // drt_path_ray[n_cams * width * height], enqueued on `stream`
     void CameraRays(const drt_camera *cams, uint32_t n_cams, uint32_t width, uint32_t height, uint32_t frame_index, drt_path_ray *rays,

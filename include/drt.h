@@ -30,7 +30,8 @@ extern "C" {
  * radiance entry points, the upscaling entry points, the adaptive-sampling entry points, the nearest-surface entry point
  * (drt_renderer_nearest), the crossing-count entry points (drt_renderer_crossings / _inside / _signed_distance), the hit-list entry
  * point (drt_renderer_list_hits), the sphere-cast entry point (drt_renderer_sphere_cast), the nearest-list entry point
- * (drt_renderer_nearest_list) and the box-overlap entry point (drt_renderer_overlap_boxes) are additions to it */
+ * (drt_renderer_nearest_list), the box-overlap entry point (drt_renderer_overlap_boxes) and the triangle-overlap entry point
+ * (drt_renderer_overlap_triangles) are additions to it */
 #define DRT_ABI_VERSION 2
 
 typedef enum {
@@ -474,6 +475,55 @@ typedef struct drt_box { float center[3]; float half[3]; float axis[3][3]; float
 int           drt_renderer_overlap_boxes(drt_renderer *r, const drt_scene *scene, const drt_box *boxes, const uint32_t *offsets,
                                          int32_t *prims, uint32_t prims_capacity, uint32_t *counts, uint32_t n, int32_t mode,
                                          void *hip_stream);
+
+/* ---- triangle overlap queries (new; the mesh triangles that each query triangle touches -- the first query about another mesh) ----
+ * One query = a drt_tri: 48 bytes, 16-byte aligned, v[3][3] (the vertices q0 = v[0], q1 = v[1], q2 = v[2]) and three pad words that
+ * are ignored.  A mesh is a batch of queries.
+ * Everything that is not stated here is drt_renderer_overlap_boxes', word for word, with "query" for "box" and tris for boxes: the
+ * modes DRT_OVERLAP_LIST and DRT_OVERLAP_ANY; the segments, the -1 fill and counts[i] as the total listed, stored or not; the NULL
+ * rules and the argument checks in that order; the error codes and the stream ordering; a refitted device copy is the one queried;
+ * the 64-level bound; and that the framebuffer, accumulation, sample count, counters, kernel info and kernel span are not touched.
+ * All arithmetic is fp32 with one rounding per operation, in the order written.  dot and cross are as the box overlap block defines
+ * them; min3(x, y, z) = fminf(fminf(x, y), z) and max3 the same with fmaxf.
+ * Validity: a query is valid iff all nine coordinates satisfy fabsf(x) <= FLT_MAX.  An invalid query (a NaN or an infinity anywhere
+ * in v) pushes nothing and lists nothing.  (fminf would otherwise drop a NaN vertex from the bounds, and the query would go on as
+ * if the vertex were not there.)
+ * Bounds, once per query: qmin[j] = min3(q0[j], q1[j], q2[j]), qmax[j] = max3(q0[j], q1[j], q2[j]).  They are exact.
+ * Node cull and traversal: the box query's, unchanged -- a box (bmin, bmax) passes iff, on all three axes, qmin[j] <= bmax[j] &&
+ * bmin[j] <= qmax[j], closed comparisons; the root is tested against the scene's root box; an interior node pushes each child that
+ * passes, child 2 first; a leaf tests its triangles in order.  The same remark applies: the stored triangle is (v0, e1, e2), v0 + e1
+ * can round one ulp outside a node box built from the real v1, and a triangle whose leaf the cull rejects is not listed, whatever the
+ * triangle test would say.
+ * Triangle test, on the query (q0, q1, q2) and the stored (v0, e1, e2), relative to q0:
+ *   a1 = q1 - q0, a2 = q2 - q0, g = a2 - a1; h = e2 - e1; p0 = v0 - q0, p1 = p0 + e1, p2 = p0 + e2;
+ *   nq = cross(a1, a2), nt = cross(e1, e2).
+ * Seventeen axes L, in this order:
+ *   1. nq
+ *   2. nt
+ *   3. cross(A, E) for A in (a1, g, a2) (outer) and E in (e1, h, e2) (inner): nine
+ *   4. cross(nq, A) for A in (a1, g, a2): three
+ *   5. cross(nt, E) for E in (e1, h, e2): three
+ * For each axis sq = (0, dot(L, a1), dot(L, a2)) and st = (dot(L, p0), dot(L, p1), dot(L, p2)); the axis is ok iff
+ * min3(st) <= max3(sq) && min3(sq) <= max3(st).  The triangle is listed iff all seventeen are ok.  Touching counts: a shared vertex
+ * or a shared edge is a touch, and a triangle of the scene given as a query lists itself.  Only the predicate leaves the kernel, so
+ * the kernel may evaluate the axes in any order and stop at the first failure; bit for bit means that the comparisons are made on the
+ * same rounded values.
+ * What the predicate is.  For two triangles of non-zero area it is, in real arithmetic, the exact intersection test of the two
+ * closed sets: the standard 11 axes (the two normals and the nine cross products of edges) decide the skew case, and the six
+ * in-plane edge normals (groups 4 and 5) decide the coplanar case, where the nine cross products vanish and pass with 0 <= 0.  For a
+ * zero-area triangle on either side (a segment or a point) it is conservative: it never misses, and it may list a near miss in the
+ * triangle's own plane.  In fp32 the products reach the fourth power of the coordinate differences.  Where that overflows, the
+ * projections are infinities and NaNs, a comparison on a NaN fails and the pair is not listed.  (fminf / fmaxf drop a NaN beside a
+ * finite projection, so the header promises no more about such a pair than that the call completes.)  Below that range the rounded
+ * predicate can differ from the real one only for pairs within rounding of touching.
+ * What this is not: the intersection segment is not returned -- no clipping, no contour; there is no pair exclusion at this level --
+ * the neighbours of a query taken from the same mesh are listed, because they touch; and it is not a large-list structure -- the
+ * insert is the one-record-per-step insert of drt_renderer_list_hits.
+ * tris is 16-byte aligned; offsets, prims and counts 4-byte aligned. */
+typedef struct drt_tri { float v[3][3]; float pad[3]; } drt_tri;                                        /* 48 B */
+int           drt_renderer_overlap_triangles(drt_renderer *r, const drt_scene *scene, const drt_tri *tris, const uint32_t *offsets,
+                                             int32_t *prims, uint32_t prims_capacity, uint32_t *counts, uint32_t n, int32_t mode,
+                                             void *hip_stream);
 
 /* ---- sphere casts (new; the first contact of a moving sphere with the mesh) ----
  * One cast = a drt_ray (org o, tmin, dir d, tmax, read as drt_renderer_trace_rays reads it: dir as given, t in units of |d|,
