@@ -332,6 +332,7 @@ _sig("drt_renderer_list_hits", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_
 _sig("drt_renderer_nearest_list", C.c_int, _P, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_renderer_overlap_boxes", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_renderer_overlap_triangles", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_int32, _P)
+_sig("drt_renderer_plane_sections", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_renderer_inside", C.c_int, _P, _P, _P, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_renderer_signed_distance", C.c_int, _P, _P, _P, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_renderer_render_guides", C.c_int, _P, C.POINTER(_CameraPOD), _P, C.c_uint32, _P, _P)
@@ -622,6 +623,8 @@ BoxTable = collections.namedtuple("BoxTable", "prim count")             # the fi
 TriList = collections.namedtuple("TriList", "splits prim")               # every triangle that query triangles touch, CSR (Renderer.overlapTriangles)
 TriTable = collections.namedtuple("TriTable", "prim count")             # the first k triangles that query triangles touch (Renderer.overlapTriangles, k=)
 OVERLAP_LIST, OVERLAP_ANY = 0, 1                                        # drt.h DRT_OVERLAP_*
+SectionList = collections.namedtuple("SectionList", "splits p q prim code")   # every segment where planes cut the mesh, CSR (Renderer.planeSections)
+SECTION_LIST, SECTION_ANY = 0, 1                                        # drt.h DRT_SECTION_*
 INSIDE_RULES = {"parity": 0, "winding": 1}                              # Renderer.inside / signedDistance: drt.h DRT_INSIDE_*
 TemporalHistory = collections.namedtuple("TemporalHistory", "color length moments variance weight")  # Renderer.GetTemporalHistory
 Guides = collections.namedtuple("Guides", "albedo normal t prim")  # first-hit guide buffers (Renderer.renderGuides)
@@ -764,6 +767,49 @@ def _tri_batch(torch, dev, tris):
         raise bad("tris: shape %s, [N, 3, 3] or a packed [N, 12] expected" % (shape,))
     packed = torch.zeros((shape[0], 12), dtype=torch.float32, device=dev)     # packed on the device, on the current stream
     packed[:, 0:9] = (t.to(dev) if from_numpy else t).reshape(shape[0], 9)
+    return packed, from_numpy
+
+
+def _plane_batch(torch, dev, normals, d):
+    """(planes [N, 4] float32 (drt_plane: n, d) on `dev`, 16-byte aligned, came_from_numpy) from normals [N, 3] + d [N] or a packed
+    [N, 4].  Raises DrtError(ERR_INVALID) on a wrong dtype, shape or device, as _box_batch does."""
+    def bad(msg):
+        return DrtError(ERR_INVALID, msg)
+
+    def as_tensor(a, what):
+        if isinstance(a, np.ndarray):
+            if a.dtype != np.float32:
+                raise bad("%s: dtype %s, float32 expected" % (what, a.dtype))
+            return torch.from_numpy(np.ascontiguousarray(a))
+        if torch.is_tensor(a):
+            if a.dtype != torch.float32:
+                raise bad("%s: dtype %s, torch.float32 expected" % (what, a.dtype))
+            if a.device != dev:
+                raise bad("%s: on %s, the renderer is on %s" % (what, a.device, dev))
+            return a
+        raise bad("%s: a numpy array or a torch tensor expected" % what)
+
+    from_numpy = isinstance(normals, np.ndarray)
+    nrm = as_tensor(normals, "normals")
+    if nrm.dim() != 2 or nrm.shape[1] not in (3, 4):
+        raise bad("normals: shape %s, [N, 3] or a packed [N, 4] expected" % (tuple(nrm.shape),))
+    if nrm.shape[1] == 4:
+        if d is not None:
+            raise bad("packed planes carry their own d")
+        packed = nrm.to(dev) if from_numpy else nrm
+        if not packed.is_contiguous() or packed.data_ptr() % 16:
+            packed = packed.contiguous().clone()
+        return packed, from_numpy
+    if d is None:
+        raise bad("planes: normals [N, 3] and d [N], or a packed [N, 4] expected")
+    if isinstance(d, np.ndarray) != from_numpy:
+        raise bad("mix of numpy arrays and device tensors")
+    dd = as_tensor(d, "d")
+    if dd.dim() != 1 or dd.shape[0] != nrm.shape[0]:
+        raise bad("d: shape %s for %d planes" % (tuple(dd.shape), nrm.shape[0]))
+    packed = torch.empty((nrm.shape[0], 4), dtype=torch.float32, device=dev)      # packed on the device, on the current stream
+    packed[:, 0:3] = nrm.to(dev) if from_numpy else nrm
+    packed[:, 3] = dd.to(dev) if from_numpy else dd
     return packed, from_numpy
 
 
@@ -1236,6 +1282,120 @@ class Renderer:
         shared = (bits[i][:, :, None, :] == bits[j][:, None, :, :]).all(dim=-1).any(dim=2).any(dim=1)
         pairs = torch.stack([i[~shared], j[~shared]], dim=1).to(torch.int32)
         return pairs if as_tensor else pairs.cpu().numpy()
+
+    def _sections(self, scene, planes):
+        """SectionList of device tensors for packed device planes [N, 4]: a count with capacity 0, a cumulative sum on the device, a
+        fill; the total is read back between them to size the result."""
+        import torch
+        dev = planes.device
+        n = planes.shape[0]
+        splits = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        total = 0
+        if n:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            counts = torch.empty(n, dtype=torch.int32, device=dev)
+            no_room = torch.zeros(n + 1, dtype=torch.int32, device=dev)       # capacity 0: every segment is empty
+            _check(_lib.drt_renderer_plane_sections(self._h, scene._h, planes.data_ptr(), no_room.data_ptr(), None, 0, counts.data_ptr(), n,
+                                                    SECTION_LIST, stream))
+            splits[1:] = torch.cumsum(counts.to(torch.int64), dim=0)
+            total = int(splits[-1].item())       # the one synchronisation: the result's size
+            if total >= 2 ** 31:
+                raise DrtError(ERR_INVALID, "%d segments in all: fewer than 2^31 expected (split the planes)" % total)
+        splits = splits.to(torch.int32)
+        rec = torch.empty((total, 8), dtype=torch.float32, device=dev)        # drt_section: p, prim, q, code
+        if total:
+            _check(_lib.drt_renderer_plane_sections(self._h, scene._h, planes.data_ptr(), splits.data_ptr(), rec.data_ptr(), total, None, n,
+                                                    SECTION_LIST, stream))
+        words = rec.view(torch.int32)
+        return SectionList(splits, rec[:, 0:3], rec[:, 4:7], words[:, 3], words[:, 7])
+
+    def planeSections(self, scene, normals, d=None):
+        """The segments where each plane dot(n, x) = d cuts the mesh (drt_renderer_plane_sections in mode DRT_SECTION_LIST).  Planes:
+        normals [N, 3] + d [N], or a packed [N, 4] (drt_plane: n, d); n is used as given, not normalised.  A plane with a NaN or an
+        infinity lists nothing, and neither does n = 0.  SectionList(splits [N + 1] int32, p [M, 3], q [M, 3] float32, prim [M],
+        code [M] int32): plane i's segments p -> q at [splits[i], splits[i + 1]), one per cut triangle in ascending triangle index;
+        on a closed mesh with outward faces they run counter-clockwise seen from the side n points to.  code = the apex vertex
+        (the one alone on its side) + 4 if it is above.  A vertex exactly on the plane counts as above; a triangle lying in the
+        plane is not cut.  Not chained into loops, and the endpoints of neighbouring triangles agree only as far as their stored
+        vertices do: weld with a tolerance.  No caps or filled polygons; alpha cut-outs are ignored.  A count with capacity 0, a
+        cumulative sum on the device, and a fill; the total is read back between them to size the result: that read is this
+        call's one synchronisation with the device.  Device tensors in, device tensors out (enqueued on the current torch
+        stream); numpy in, numpy out."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        planes, from_numpy = _plane_batch(torch, dev, normals, d)
+        res = self._sections(scene, planes)
+        if from_numpy:
+            return SectionList(*(x.cpu().numpy().copy() for x in res))
+        return res
+
+    def cutsAny(self, scene, normals, d=None):
+        """Whether each plane cuts any triangle: bool [N] (drt_renderer_plane_sections in mode DRT_SECTION_ANY, whose work ends at
+        the first cut triangle found).  Planes and conventions as planeSections."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        planes, from_numpy = _plane_batch(torch, dev, normals, d)
+        n = planes.shape[0]
+        counts = torch.empty(n, dtype=torch.int32, device=dev)
+        if n:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(_lib.drt_renderer_plane_sections(self._h, scene._h, planes.data_ptr(), None, None, 0, counts.data_ptr(), n, SECTION_ANY, stream))
+        res = counts > 0
+        return res.cpu().numpy() if from_numpy else res
+
+    def slices(self, scene, count, axis=2, lo=None, hi=None):
+        """`count` parallel sections along `axis` (0, 1 or 2): (heights [count] float32, SectionList), device tensors.  The planes
+        have the unit normal of the axis and sit at the cell centres of the range (lo, hi) along it, by default the scene's bounds,
+        laid out as sdfGrid lays out its cells: height i = lo + (i + 0.5) * ((hi - lo) / count).  The planes are made on the device."""
+        if isinstance(count, bool) or not isinstance(count, (int, np.integer)) or count < 1:
+            raise DrtError(ERR_INVALID, "count = %r: a positive integer expected" % (count,))
+        if axis not in (0, 1, 2):
+            raise DrtError(ERR_INVALID, "axis = %r: 0, 1 or 2 expected" % (axis,))
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        if lo is None or hi is None:
+            nodes = scene.m_BVHNodes
+            if len(nodes) == 0:
+                raise DrtError(ERR_INVALID, "slices: an empty scene has no bounds; give lo and hi")
+            lo = nodes[-1]["bmin"][axis] if lo is None else lo                # the root is the last node
+            hi = nodes[-1]["bmax"][axis] if hi is None else hi
+        lo, hi = np.float32(lo), np.float32(hi)
+        heights = float(lo) + (torch.arange(int(count), dtype=torch.float32, device=dev) + 0.5) * (float(hi - lo) / int(count))
+        planes = torch.zeros((int(count), 4), dtype=torch.float32, device=dev)
+        planes[:, axis] = 1.0
+        planes[:, 3] = heights
+        return heights, self._sections(scene, planes)
+
+    def sectionAreas(self, scene, normals, d=None):
+        """The signed area enclosed by each plane's contours: float64 [N], 0.5 * sum dot(n / |n|, cross(p, q)) over the plane's
+        segments -- positive on a closed mesh with outward faces, where it is the area of the cross-section (n = 0 gives 0).  It
+        is computed from planeSections' list on the device in float64 with a deterministic reduction: a cumulative sum over all
+        segments (with its rounding errors carried along) and differences at the splits, no atomics.  Planes and conventions as planeSections."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        planes, from_numpy = _plane_batch(torch, dev, normals, d)
+        n = planes.shape[0]
+        sec = self._sections(scene, planes)
+        nrm = planes[:, 0:3].to(torch.float64)
+        length = torch.sqrt((nrm * nrm).sum(dim=1, keepdim=True))
+        unit = torch.where(length > 0, nrm / torch.where(length > 0, length, torch.ones_like(length)), torch.zeros_like(nrm))
+        counts = (sec.splits[1:] - sec.splits[:-1]).to(torch.int64)
+        owner = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=dev), counts)
+        term = (unit[owner] * torch.linalg.cross(sec.p.to(torch.float64), sec.q.to(torch.float64), dim=1)).sum(dim=1)
+        # A running sum over ALL segments and its differences at the splits.  The running sum rounds relative to what the planes
+        # before have summed to, which would leave a small area behind large ones with few digits.  So the error of every step,
+        # (run[i] + term[i]) - run[i + 1], is computed with Knuth's two-sum and summed the same way: in exact arithmetic the two
+        # differences add up to the plane's own sum whatever values the scan left in `run` (a device scan does not add left to
+        # right), and in float64 the error terms are of the size of run's rounding, so theirs is second order.
+        run = torch.zeros(term.shape[0] + 1, dtype=torch.float64, device=dev)
+        run[1:] = torch.cumsum(term, dim=0)
+        before, after = run[:-1], run[1:]
+        took = after - before
+        lost = torch.zeros_like(run)
+        lost[1:] = torch.cumsum((before - (after - took)) + (term - took), dim=0)
+        at = sec.splits.to(torch.int64)
+        areas = 0.5 * ((run[at[1:]] - run[at[:-1]]) + (lost[at[1:]] - lost[at[:-1]]))
+        return areas.cpu().numpy() if from_numpy else areas
 
     def voxelize(self, scene, resolution, lo=None, hi=None):
         """Conservative surface voxelisation: a bool [Z, Y, X] device tensor, true where a triangle touches the (closed) cell, over

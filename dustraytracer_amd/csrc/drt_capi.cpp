@@ -21,6 +21,7 @@
 #include "near_list.hpp"
 #include "overlap.hpp"
 #include "tri_overlap.hpp"
+#include "section.hpp"
 #include "bvh_build_device.hpp"
 #include "png_decode.hpp"
 
@@ -75,6 +76,7 @@ static int copy_scene(drt_renderer *r, const drt_scene *scene) {
     std::memcpy(v.root_max, ps.root_max, 12);
     r->bvh_depth = ps.depth;
     r->scene_has_alpha = ps.any_alpha_texture;
+    r->leaves_ascending = section_leaves_ascending(ps);
     path_pool_leaf_classes(ps.leaves, r->pool_t_class);
     if (r->tune.t_class_set) std::memcpy(r->pool_t_class, r->tune.t_class, sizeof r->pool_t_class);
     if (r->tune.pool_verbose) std::fprintf(stderr, "path_pool leaf classes: %u %u %u\n", r->pool_t_class[0], r->pool_t_class[1], r->pool_t_class[2]);
@@ -470,6 +472,7 @@ drt_renderer *drt_renderer_create(int32_t device) {
     if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) == hipSuccess && khz > 0) r->wall_clock_khz = khz;
     r->rq_refill_min = std::min(64, std::max(1, env_int("DRT_RQ_REFILL", r->rq_refill_min)));
     r->rf_top_nodes = std::max(0, env_int("DRT_REFIT_TOP", r->rf_top_nodes));
+    r->section_waves = std::max(0, env_int("DRT_SECTION_WAVES", r->section_waves));
     if (r->ev_start.create() != hipSuccess || r->ev_stop.create() != hipSuccess ||
         r->ev_query.create(hipEventDisableTiming) != hipSuccess ||
         r->counters.alloc(sizeof(drt_counters) / sizeof(unsigned long long)) != hipSuccess ||

@@ -1,4 +1,4 @@
-// renderer_state.hpp -- what the translation units of the C ABI share (drt_capi.cpp, drt_capi_filters.cpp, drt_capi_adaptive.cpp): the renderer's state,
+// renderer_state.hpp -- what the translation units of the C ABI share (drt_capi.cpp, drt_capi_filters.cpp, drt_capi_adaptive.cpp, drt_capi_section.cpp): the renderer's state,
 // the owners of its device memory, pinned memory and events, error reporting, the steps several entry points take.  Not exported.
 #pragma once
 #include "../../include/drt.h"
@@ -157,6 +157,12 @@ struct drt_renderer {
     bool query_recorded = false;
     DeviceArray<unsigned int> rq_heads;
     DeviceArray<uint32_t> rq_stack;
+    // drt_renderer_plane_sections: the worklists of the wave-per-plane kernel (section.hpp: two lists of n_leaves words per wave of
+    // the grid), grown on demand as rq_stack is; leaves_ascending = the uploaded tree's leaves, child 1 first, hold ascending
+    // triangle ranges (the kernel's lists are sorted only then)
+    DeviceArray<uint32_t> section_work;
+    int section_waves = 0;                     // DRT_SECTION_WAVES: at most this many waves per launch (0 = no cap)
+    bool leaves_ascending = true;
     drt::FilterKernel filter_kernel = drt::FilterKernel::automatic;      // DRT_FILTER_KERNEL=lds / taps: one a-trous kernel for every pass (unset, or any other value: launch_atrous's rule)
     int rq_refill_min = 16;                    // DRT_RQ_REFILL: idle lanes that make a wave claim new rays (64 = only when all are)
     // drt_renderer_denoise: frame 1's guides and the two float4 buffers the passes ping-pong between, allocated by the first call,

@@ -344,6 +344,15 @@ public:
                           uint32_t *counts, uint32_t n, int32_t mode, void *stream = nullptr) {
         drt::check(drt_renderer_overlap_triangles(handle, scene.handle, tris, offsets, prims, prims_capacity, counts, n, mode, stream));
     }
+    // new: the segments where each query plane dot(n, x) = d cuts the mesh, a drt_plane {n[3], d} (drt_renderer_plane_sections): one
+    // drt_section {p[3], prim, q[3], code} per cut triangle in ascending triangle index, p -> q counter-clockwise about n on a closed
+    // mesh with outward faces; the miss record is zeros with prim = -1.  Modes (DRT_SECTION_LIST / DRT_SECTION_ANY), segments, counts
+    // and the null rules are OverlapBoxes', with 32-byte records.  Endpoints of neighbouring triangles agree only as far as their stored
+    // vertices do: weld with a tolerance.  Device arrays, planes and out 16-byte aligned, enqueued on `stream`.
+    void PlaneSections(const Scene &scene, const drt_plane *planes, const uint32_t *offsets, drt_section *out, uint32_t out_capacity,
+                       uint32_t *counts, uint32_t n, int32_t mode, void *stream = nullptr) {
+        drt::check(drt_renderer_plane_sections(handle, scene.handle, planes, offsets, out, out_capacity, counts, n, mode, stream));
+    }
     // new: RayGen's primary rays of n_cams cameras for a width x height image, frame `frame_index` (drt_renderer_camera_rays): a device
     // drt_path_ray[n_cams * width * height], enqueued on `stream`
     void CameraRays(const drt_camera *cams, uint32_t n_cams, uint32_t width, uint32_t height, uint32_t frame_index, drt_path_ray *rays,

@@ -30,8 +30,8 @@ extern "C" {
  * radiance entry points, the upscaling entry points, the adaptive-sampling entry points, the nearest-surface entry point
  * (drt_renderer_nearest), the crossing-count entry points (drt_renderer_crossings / _inside / _signed_distance), the hit-list entry
  * point (drt_renderer_list_hits), the sphere-cast entry point (drt_renderer_sphere_cast), the nearest-list entry point
- * (drt_renderer_nearest_list), the box-overlap entry point (drt_renderer_overlap_boxes) and the triangle-overlap entry point
- * (drt_renderer_overlap_triangles) are additions to it */
+ * (drt_renderer_nearest_list), the box-overlap entry point (drt_renderer_overlap_boxes), the triangle-overlap entry point
+ * (drt_renderer_overlap_triangles) and the plane-section entry point (drt_renderer_plane_sections) are additions to it */
 #define DRT_ABI_VERSION 2
 
 typedef enum {
@@ -524,6 +524,63 @@ typedef struct drt_tri { float v[3][3]; float pad[3]; } drt_tri;                
 int           drt_renderer_overlap_triangles(drt_renderer *r, const drt_scene *scene, const drt_tri *tris, const uint32_t *offsets,
                                              int32_t *prims, uint32_t prims_capacity, uint32_t *counts, uint32_t n, int32_t mode,
                                              void *hip_stream);
+
+/* ---- plane sections (new; the segments where each plane cuts the mesh -- the first query that returns the geometry of a cut) ----
+ * One query = a drt_plane: 16 bytes, 16-byte aligned, n[3] and d.  It is the set dot(n, x) = d.  n is used as given and is not
+ * normalised.  Slicing a mesh is a batch of parallel planes.
+ * Everything that is not stated here is drt_renderer_overlap_boxes', word for word, with "plane" for "box", planes for boxes and out
+ * for prims: the NULL rules and the argument checks in that order; the error codes and the stream ordering; a refitted device copy is
+ * the one queried; the 64-level bound; and that the framebuffer, accumulation, sample count, counters, kernel info and kernel span are
+ * not touched.
+ * All arithmetic is fp32 with one rounding per operation, in the order written.  dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z and cross
+ * are as the box overlap block defines them.  Alpha cut-outs are ignored (a geometric query).
+ * Validity: a plane is valid iff all four words satisfy fabsf(x) <= FLT_MAX.  An invalid plane (a NaN or an infinity in n or d) pushes
+ * nothing and lists nothing.  n = 0 is valid and cuts nothing.
+ * Signed value: s(x) = dot(n, x) - d.  A vertex is above iff s >= 0 (closed), otherwise below.  (-0.0 is above.)
+ * Node cull: per axis, cmin[j] = n[j] >= 0 ? bmin[j] : bmax[j] and cmax[j] is the other one.  A box (bmin, bmax) passes iff
+ * s(cmin) < 0 && s(cmax) >= 0.  The root is tested against the scene's root box; an interior node keeps each child that passes, child 1
+ * before child 2.  Every product and sum in s is monotone in each coordinate, and rounding is monotone, so
+ * s(cmin) <= s(v) <= s(cmax) holds in fp32 for every v inside the box: the cull never drops a cut triangle whose vertices lie in the
+ * box.  The known remark applies: the stored triangle is (v0, e1, e2), v0 + e1 can round one ulp outside a node box built from the
+ * real v1, and a triangle whose leaf the cull rejects is not listed.
+ * Triangle test, on the stored (v0, e1, e2): v1 = v0 + e1, v2 = v0 + e2; s0, s1, s2 = s(v0), s(v1), s(v2).  The triangle is cut iff
+ * its three vertices are not all in the same class.  A triangle lying in the plane is all above and is not cut.
+ * Segment: exactly one vertex k is alone in its class: the apex.  cut(a, b): let lo be the below one of the two and hi the above one;
+ * t = s_lo / (s_lo - s_hi), and the point is lo + (hi - lo) * t per component.  The canonical below-to-above direction makes the point
+ * of a shared edge depend on that edge's two vertices only.  P = cut(k, k+1) and Q = cut(k, k+2), indices mod 3.  Apex above: the
+ * segment is P -> Q.  Apex below: it is Q -> P.  So dot(q - p, cross(n, fn)) >= 0 with fn = cross(e1, e2): on a closed mesh with
+ * outward faces the contours run counter-clockwise seen from the side n points to, and 0.5 * sum dot(n / |n|, cross(p, q)) is the
+ * positive section area.  code = k + 4 * (apex above).  A vertex exactly on the plane is above; an apex on the plane with the other
+ * two below gives a zero-length segment, and it is listed.
+ * Record: a drt_section, 32 bytes: p[3], prim, q[3], code.  The miss record is all zeros with prim = -1.
+ * List: ascending triangle index.  Each triangle lies in one leaf and the cull never changes during a query, so the set of records
+ * does not depend on the traversal order.
+ * Mode DRT_SECTION_LIST (0): offsets / out / out_capacity / counts are exactly drt_renderer_overlap_boxes' segments, with 32-byte
+ * records in place of int32: offsets holds n + 1 uint32 values; plane i owns out[offsets[i] .. offsets[i+1]).  Its capacity is
+ * cap_i = offsets[i+1] > offsets[i] ? offsets[i+1] - offsets[i] : 0, then clamped so that offsets[i] + cap_i <= out_capacity
+ * (offsets[i] >= out_capacity gives 0).  The call writes out[offsets[i] + j] for j < cap_i and nothing else in out.  The first cap_i
+ * records of the list are stored; the rest of the cap_i slots hold the miss record.  counts[i] is the total, stored or not.  out is
+ * NULL iff out_capacity == 0: a pure count.  counts may be NULL; both out and counts NULL is DRT_ERR_INVALID.  Two passes give every
+ * segment of every plane without a capacity guess: a count with capacity 0, an exclusive scan of the counts into offsets, a fill.
+ * Mode DRT_SECTION_ANY (1): the work ends at the first cut triangle found, and counts[i] is 0 or 1.  (An implementation may finish
+ * the group of leaves it is testing before it stops; counts[i] is the same.)  out must be NULL and out_capacity 0; offsets is not
+ * read; counts NULL is DRT_ERR_INVALID.
+ * A result depends on the plane, the scene, cap_i and the mode only.  An empty scene lists nothing.
+ * The lists are ascending because the builder splits a range [first, last) into [first, mid) and [mid, last): the leaves, child 1
+ * first, hold ascending triangle ranges.  The library checks that when it packs a scene and returns DRT_ERR_UNSUPPORTED for a tree
+ * where it is false, instead of handing out an unsorted list.
+ * What this is not: no chaining into loops -- the records of a plane are separate segments in triangle order; endpoints of neighbouring
+ * triangles agree only as far as their stored vertices do (v0 + e1 of one against v0' + e2' of the other), so a caller welds with a
+ * tolerance; no caps or filled polygons; alpha cut-outs are ignored; and it is not built for millions of planes with near-empty lists
+ * -- it works there, one wave each.
+ * planes and out are 16-byte aligned; offsets and counts 4-byte aligned. */
+typedef struct drt_plane { float n[3]; float d; } drt_plane;                                            /* 16 B */
+typedef struct drt_section { float p[3]; int32_t prim; float q[3]; int32_t code; } drt_section;         /* 32 B */
+#define DRT_SECTION_LIST 0
+#define DRT_SECTION_ANY  1
+int           drt_renderer_plane_sections(drt_renderer *r, const drt_scene *scene, const drt_plane *planes, const uint32_t *offsets,
+                                          drt_section *out, uint32_t out_capacity, uint32_t *counts, uint32_t n, int32_t mode,
+                                          void *hip_stream);
 
 /* ---- sphere casts (new; the first contact of a moving sphere with the mesh) ----
  * One cast = a drt_ray (org o, tmin, dir d, tmax, read as drt_renderer_trace_rays reads it: dir as given, t in units of |d|,
