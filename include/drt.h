@@ -654,6 +654,42 @@ typedef struct drt_sweep_hit { float t; int32_t prim; float u, v; float point[3]
 int           drt_renderer_sphere_cast(drt_renderer *r, const drt_scene *scene, const drt_ray *rays, const float *radii, drt_sweep_hit *out,
                                        uint32_t n, void *hip_stream);
 
+/* ---- working range of the mesh queries (what the rules above assume of the scale of a mesh; no rule is changed here) ----
+ * Scaling a mesh and its queries by a power of two changes nothing while every intermediate value stays a normal fp32 number: every
+ * product and sum is the plain one with another exponent, so every field of every answer is the plain answer scaled, bit for bit, and
+ * every index, count, u, v and (with the direction scaled too) t is the same.  The ranges below were measured in steps of 2^2 on a mesh
+ * with edges of 2^-2 to 2^4 and queries up to 2^7 from it, zero-area triangles, slivers and needles included
+ * (tests/test_hostile_meshes_ref.py asserts these figures); a mesh that far from the origin, at (4096, -8192, 16384), keeps the
+ * nearest distance within one unit of 2^-23 times its largest coordinate.
+ * The ray family -- drt_renderer_trace_rays, _occluded, _crossings, _inside, the sign of _signed_distance, _list_hits -- inherits two
+ * ABSOLUTE constants of the renderer's triangle test, in scene units: a triangle with |det| < 1e-6 is dropped, det = dot(e1, cross(dir,
+ * e2)), and a hit counts only if t > 1e-6.  det is the product of two edge lengths and |dir|, so with a unit direction triangles with
+ * edges of about 1e-3 and below disappear: a millimetre tessellation of a mesh kept in metres.  drt_renderer_inside and
+ * drt_renderer_signed_distance always cast the fixed unit directions D0, D1, D2: on such a mesh crossings are lost one by one, every
+ * lost crossing turns a parity vote, and once all are lost every point is called outside, silently.  On the test mesh, with the
+ * directions scaled as well (det is then a third power), the first crossing is lost at 2^-4 and the first vote changes there too; at
+ * 2^-20 every count is 0, every vote is 0 and drt_renderer_trace_rays misses.  Going up nothing is lost, but grazing triangles that
+ * were below 1e-6 come back, and a vote can change.  Rescale such a mesh before it is loaded.
+ * drt_renderer_nearest, _nearest_list: vc, vb, va are products of four lengths (two edges and two offsets of the query), and
+ * den = 1 / ((va + vb) + vc).  They keep their digits while those products stay normal numbers, 2^-126 to 2^128: lengths of about 2^-31
+ * to 2^32 when all four are alike, less where a query lies close to a short edge.  Measured: unchanged for 2^-22 to 2^30; beyond, the
+ * products overflow to infinities and NaNs or lose bits as subnormals, and answers go wrong (a NaN dist2 never wins, so triangles
+ * vanish).
+ * drt_renderer_overlap_boxes: the cross axes are third powers and only comparisons leave the test: unchanged for 2^-32 to 2^42.
+ * drt_renderer_overlap_triangles: fourth powers: unchanged for 2^-30 to 2^30; beyond, pairs are no longer listed.
+ * drt_renderer_sphere_cast: disc = ee (A r2 - det det) with A = |cross(d, e)|^2 is an EIGHTH power of the lengths when the direction is
+ * scaled with the mesh (t stays), a sixth with a direction of fixed length: unchanged for 2^-4 to 2^10 only.  Give a large or a tiny mesh
+ * directions of about unit length, or rescale it.  Apart from scale, a sliver (three vertices collinear to the last bit) has a face test
+ * whose den, nu and nv are all rounding errors: where den comes out positive the face can be reported for a sphere that passes the sliver
+ * at a distance of thousands of units of 2^-23 of the scene's size.  Exactly zero-area triangles have den = 0 and no face, as stated.
+ * drt_renderer_plane_sections: s = dot(n, x) - d, t and the cut points are linear in the lengths; there is no such limit (unchanged at
+ * 2^-40 and at 2^50), short of overflow of the coordinates themselves.
+ * Outside these ranges every call still completes and still equals the rule as written, operation by operation, infinities, NaNs and
+ * subnormals included -- tests/test_gpu_hostile_meshes.py compares the kernels there too -- but the rule no longer says anything useful.
+ * (drt_renderer_overlap_triangles' predicate is conservative for zero-area triangles in a stronger sense than "a near miss in the
+ * triangle's own plane": a segment or point query passes all seventeen axes against a POINT of the scene wherever it is, and only the
+ * node cull keeps such a pair out of the list.) */
+
 /* ---- first-hit guide buffers and the a-trous denoiser (new; the reference's TODO list, RayGen.cuh:13-21, starts with "DLSS 3.5
  * like features") ----
  * drt_renderer_render_guides writes one drt_guide per pixel x + y * width (row 0 = bottom, as the framebuffer) for frame
