@@ -74,6 +74,24 @@ DRT_DEV float exact_sqrt(float x) {
 
 DRT_DEV float length(f3 v) { return sqrtf(dot(v, v)); }                                           // helper_math.cuh:1307
 DRT_DEV f3 normalize(f3 v) { float inv_len = exact_rcp(exact_sqrt(dot(v, v))); return v * inv_len; }   // helper_math.cuh:1325 (1/sqrtf, exact)
+// 1 / sqrtf(dd) for dd = dot(v, v) of a vector whose components lie in [-1, 1]: the value normalize() computes, under ONE
+// range test instead of exact_sqrt's and exact_rcp's two-sided pairs.  0 <= dd <= 3, so only the lower end can leave the
+// fast paths; and dd >= 2^-100 puts sqrt(dd) in [2^-50, 1.74], inside exact_rcp's fast range too.  Both fast paths equal
+// the plain operators over their whole ranges (drt_debug_check_rcp / _sqrt, every bit pattern), which is what the slow
+// path uses -- as exact_rcp(exact_sqrt(dd)) does there, one way or the other.
+DRT_DEV float inv_length_unit_cube(float dd) {
+    const float s = __builtin_amdgcn_sqrtf(dd);
+    const float s_dn = __uint_as_float(__float_as_uint(s) - 1u), s_up = __uint_as_float(__float_as_uint(s) + 1u);
+    const float r_dn = __builtin_fmaf(-s_dn, s, dd), r_up = __builtin_fmaf(-s_up, s, dd);
+    float y = (r_dn <= 0.0f) ? s_dn : s;
+    y = (r_up > 0.0f) ? s_up : y;
+    const float r = __builtin_amdgcn_rcpf(y);
+    const float rem = __builtin_fmaf(-y, r, 1.0f);
+    float q = __builtin_fmaf(rem, r, r);
+    if (__builtin_expect(!(dd >= 0x1p-100f), 0)) q = 1.0f / sqrtf(dd);
+    return q;
+}
+DRT_DEV f3 normalize_unit_cube(f3 v) { return v * inv_length_unit_cube(dot(v, v)); }
 
 // ---- CudaMath/Random.cu ----
 DRT_DEV uint32_t pcg_hash(uint32_t input) {                                                       // :6-11
@@ -112,7 +130,7 @@ DRT_DEV bool random_unit_sphere_try(uint32_t &seed, f3 &p) {
     seed = pcg_hash(seed); float x = (float)seed * 0x1p-31f - 1.f;
     seed = pcg_hash(seed); float y = (float)seed * 0x1p-31f - 1.f;
     seed = pcg_hash(seed); float z = (float)seed * 0x1p-31f - 1.f;
-    p = normalize(mk3(x, y, z));
+    p = normalize_unit_cube(mk3(x, y, z));        // |x|, |y|, |z| <= 1
     return dot(p, p) < 1.0f;
 }
 // randomUnitSphereVec3 (Random.cu:50-58) as a loop over random_unit_sphere_try, with the cycle guard

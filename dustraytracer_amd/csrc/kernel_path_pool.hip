@@ -143,6 +143,7 @@ DRT_DEV float u2f(uint32_t u) { return __uint_as_float(u); }
 DRT_DEV uint32_t f2u(float f) { return __float_as_uint(f); }
 
 // LDS map of a workgroup (byte offsets from the start of its dynamic LDS; host and device compute it the same way)
+constexpr uint32_t kScenePad = 144u;                 // three TriHot records behind the staged triangles
 struct PoolLayout {
     uint32_t ctrl, rings, quads, words, stack, scene, cold, total;      // byte offsets; total = bytes needed
 };
@@ -158,7 +159,9 @@ __host__ __device__ inline PoolLayout pool_layout(uint32_t P, uint32_t ring_cap,
     l.words = l.quads + 2u * P * 16u;
     l.stack = l.words + P * word_bytes;
     l.scene = (l.stack + stack_entries * P * stack_entry_bytes + 15u) & ~15u;
-    l.cold = l.scene + scene_bytes + (scene_bytes ? 48u : 0u);      // (T reads pairs of triangles: the partner of the last one is one record past the end)
+    // (T reads pairs of triangles, and a lane that is through with its leaf keeps reading the pair behind it while the batch's other
+    // lanes finish: behind the last leaf that is up to three records past the end -- kScenePad bytes, zeroed by the prologue)
+    l.cold = l.scene + scene_bytes + (scene_bytes ? kScenePad : 0u);
     l.total = l.cold + cold_bytes;
     return l;
 }
@@ -250,23 +253,33 @@ __global__ __launch_bounds__(pool_max_threads(FLAGS)) __attribute__((amdgpu_wave
     float4 *const aux_light = PA().aux_light + (size_t)blockIdx.x * P;
     float4 *const aux_next = EXT ? PA().aux_next + (size_t)blockIdx.x * P * 2u : nullptr;
 
+    // (lds-scene build) the self-describing form of a leaf reference: kLeafBit | T class << 24 | count << 12 | first triangle --
+    // reaching a leaf then costs no LeafRange load, and its T queue is a bit field, not three compares: the class belongs to the
+    // leaf, not to the visit (n_tris < 4096 is what path_pool_supports guarantees and launch_path_pool checks)
+    auto staged_leaf_ref = [&](uint32_t ref) -> uint32_t {
+        const LeafRange lr = SC().leaves[ref & ~kLeafBit];
+        const uint32_t steps = ((uint32_t)lr.count + 1u) >> 1;
+        const uint32_t t_class = steps <= k_t_class0 ? 0u : (steps <= k_t_class1 ? 1u : (steps <= k_t_class2 ? 2u : 3u));
+        return kLeafBit | (t_class << 24) | ((uint32_t)lr.count << 12) | (uint32_t)lr.start;
+    };
+
     if (FP().span && lane == 0) atomicMax(&FP().span[0], ~(unsigned long long)wall_clock64());
 
     // ---- prologue: scene copy, empty rings, every pool slot waits in E without a sample ----
     {
         const uint4 *g_inner = reinterpret_cast<const uint4 *>(SC().inner);
         const uint4 *g_hot = reinterpret_cast<const uint4 *>(SC().tri_hot);
-        // (leaf references are rewritten while the records are staged: kLeafBit | count << 12 | first triangle -- reaching a leaf
-        // then costs no LeafRange load; n_tris < 4096 is what path_pool_supports guarantees)
+        // (leaf references are rewritten while the records are staged: staged_leaf_ref)
         for (uint32_t i = tid; !HBM && i < SC().n_inner * 4u; i += wg) {
             uint4 v = g_inner[i];
             if ((i & 3u) == 3u) {
-                if (v.x & kLeafBit) { const LeafRange lr = SC().leaves[v.x & ~kLeafBit]; v.x = kLeafBit | ((uint32_t)lr.count << 12) | (uint32_t)lr.start; }
-                if (v.y & kLeafBit) { const LeafRange lr = SC().leaves[v.y & ~kLeafBit]; v.y = kLeafBit | ((uint32_t)lr.count << 12) | (uint32_t)lr.start; }
+                if (v.x & kLeafBit) v.x = staged_leaf_ref(v.x);
+                if (v.y & kLeafBit) v.y = staged_leaf_ref(v.y);
             }
             st4(lds_inner + i * 16u, v);
         }
         for (uint32_t i = tid; !HBM && i < SC().n_tris * 3u; i += wg) st4(lds_hot + i * 16u, g_hot[i]);
+        for (uint32_t i = tid; !HBM && i < kScenePad / 16u; i += wg) st4(lds_hot + (SC().n_tris * 3u + i) * 16u, make_uint4(0u, 0u, 0u, 0u));
         if (cold_lds) {
             const uint4 *g_cold = reinterpret_cast<const uint4 *>(SC().tri_cold);
             const uint4 *g_mats = reinterpret_cast<const uint4 *>(SC().mats);
@@ -282,7 +295,7 @@ __global__ __launch_bounds__(pool_max_threads(FLAGS)) __attribute__((amdgpu_wave
             else st1(qW + i * 4u, kNoPrim);
         }
         __syncthreads();
-        for (uint32_t i = tid; i < P; i += wg) st_id(rings + ((uint32_t)QE * k_ring_cap + i) * 2u, i);
+        for (uint32_t i = tid; i < P; i += wg) st_id(rings + ((((uint32_t)QE << k_ring_shift) + i) << 1), i);
         if (tid == 0) { st1(ctrl + QE * 8u + 4u, P); st1(ctrl + kCtrlLive, P); }
         __syncthreads();
     }
@@ -397,12 +410,17 @@ __global__ __launch_bounds__(pool_max_threads(FLAGS)) __attribute__((amdgpu_wave
         const float alpha = tex_get_alpha<true>(SC(), tex, interp_uv(cold, uvw));
         return !(alpha < 1);
     };
-    // leaf -> its triangles [cur, end) and the T queue of its size class.  leaf_ref: count << 12 | first triangle in the lds-scene
-    // build (the staged records carry it), the leaf's index in the hbm-scene build
+    // leaf -> its triangles [cur, end) and the T queue of its size class.  leaf_ref: T class << 24 | count << 12 | first triangle
+    // in the lds-scene build (the staged records carry it: staged_leaf_ref), the leaf's index in the hbm-scene build
     auto leaf_state = [&](uint32_t leaf_ref, uint32_t &cur, uint32_t &end) -> int {
-        uint32_t count;
-        if (HBM) { const LeafRange lr = SC().leaves[checked(leaf_ref, SC().n_leaves, 0x400u)]; cur = (uint32_t)lr.start; count = (uint32_t)lr.count; }
-        else { cur = leaf_ref & 0xFFFu; count = leaf_ref >> 12; }
+        if (!HBM) {
+            cur = leaf_ref & 0xFFFu;
+            end = cur + ((leaf_ref >> 12) & 0xFFFu);
+            return QT0 + (int)((leaf_ref >> 24) & 3u);
+        }
+        const LeafRange lr = SC().leaves[checked(leaf_ref, SC().n_leaves, 0x400u)];
+        cur = (uint32_t)lr.start;
+        const uint32_t count = (uint32_t)lr.count;
         end = cur + count;
         const uint32_t steps = (count + 1u) >> 1;
         return QT0 + (steps <= k_t_class0 ? 0 : (steps <= k_t_class1 ? 1 : (steps <= k_t_class2 ? 2 : 3)));
@@ -472,28 +490,19 @@ __global__ __launch_bounds__(pool_max_threads(FLAGS)) __attribute__((amdgpu_wave
     auto spill_top = [&](int &sp, uint32_t id, const uint2 &top, bool &have_top) {
         if (have_top) { stack_store(sp, id, top); ++sp; have_top = false; }
     };
-    // Push every lane's path id (dest >= 0) to its destination queue: one atomic add per destination present in the wave
-    // (issued together by the first lane of each group), then the ids go to consecutive ring positions.
+    // Push every lane's path id (dest >= 0) to its destination queue: each lane reserves its ring position with an atomic add on
+    // the queue's tail -- one ds_add_rtn_u32 for the wave, whose lanes the LDS pipe serialises per address (tools/microbench/
+    // lds_same_address_atomic.hip: 44 cycles for 64 lanes on 3 tails, 128 on one) while the vector ALU, the port this kernel
+    // fills, issues one instruction for it.  Sharing one add per destination among the lanes (a ballot, a readlane and two
+    // mbcnt per destination, a bpermute for the base) cost ~35 vector instructions per batch.  Nothing reads the order in which
+    // the lanes of a batch land in the ring.
     auto push_group = [&](int dest, uint32_t id) {
-        unsigned long long todo = pp_ballot(dest >= 0);
-        uint32_t add_count = 0, my_rank = 0;
-        int my_leader = 0;
-        while (todo) {
-            const int first = __builtin_ctzll(todo);
-            const int d = __builtin_amdgcn_readlane(dest, first);
-            const unsigned long long m = pp_ballot(dest == d);
-            if (dest == d) { my_rank = (uint32_t)pp_rank(m); my_leader = first; add_count = (uint32_t)__popcll(m); }
-            todo &= ~m;
-        }
-        uint32_t base = 0;
-        if (dest >= 0 && lane == my_leader) base = lds_add(ctrl + (uint32_t)dest * 8u + 4u, add_count);
-        base = (uint32_t)__builtin_amdgcn_ds_bpermute(my_leader << 2, (int)base);
         if (dest >= 0) {
+            const uint32_t pos = lds_add(ctrl + (uint32_t)dest * 8u + 4u, 1u);
             // The slot may still hold the entry of the previous lap: its consumer has claimed it (at most P <= ring_cap ids are ever
             // outstanding, so the head is past it) but may not have read and cleared it yet -- at the start, when E's ring holds
             // all P ids, a path that goes straight back to E lands on exactly such a slot.  Wait for the slot to be empty.
-            const uint32_t pos = base + my_rank;
-            const uint32_t at = rings + ((uint32_t)dest * k_ring_cap + (pos & ring_mask)) * 2u;
+            const uint32_t at = rings + ((((uint32_t)dest << k_ring_shift) + (pos & ring_mask)) << 1);
             if (__builtin_expect(ld_id(at) != kEmptyId, 0)) {             // (rare: kept out of the straight path)
                 uint32_t spins = 0;
 #pragma nounroll
@@ -506,7 +515,7 @@ __global__ __launch_bounds__(pool_max_threads(FLAGS)) __attribute__((amdgpu_wave
     const f3 root_min = ld3(SC().root_min), root_max = ld3(SC().root_max);
     // TraceRay.cu:15-20 + BVHTraversal.cuh:22-26,38: the root goes on the stack with its slab distance when -1 < d < FLT_MAX
     uint32_t root_ref = SC().root_ref;                      // (a one-leaf scene: the same self-describing form as the staged records)
-    if (!HBM && root_ref != kNoNode && (root_ref & kLeafBit)) { const LeafRange lr = SC().leaves[root_ref & ~kLeafBit]; root_ref = kLeafBit | ((uint32_t)lr.count << 12) | (uint32_t)lr.start; }
+    if (!HBM && root_ref != kNoNode && (root_ref & kLeafBit)) root_ref = staged_leaf_ref(root_ref);
     auto begin_closest = [&](const Ray &ray, uint2 &top) -> bool {
         if (SC().root_ref == kNoNode) return false;
         const float d = slab_intersect(root_min, root_max, ray);
@@ -635,7 +644,7 @@ __global__ __launch_bounds__(pool_max_threads(FLAGS)) __attribute__((amdgpu_wave
             // another lap's tag = the entry of the position one lap earlier, which its own consumer (a wave that has claimed it and
             // not got round to reading it) is still to take -- taking that one would put a path in two hands
             const uint32_t pos = head + (uint32_t)lane;
-            const uint32_t at = rings + ((uint32_t)q * k_ring_cap + (pos & ring_mask)) * 2u;
+            const uint32_t at = rings + ((((uint32_t)q << k_ring_shift) + (pos & ring_mask)) << 1);
             const uint32_t my_lap = (pos >> k_ring_shift) & 15u;
             uint32_t e = ld_id(at);
             if (__builtin_expect(e == kEmptyId || (e >> 12) != my_lap, 0)) {          // (rare: kept out of the straight path)
@@ -767,9 +776,11 @@ __global__ __launch_bounds__(pool_max_threads(FLAGS)) __attribute__((amdgpu_wave
             }
             if (!HBM) {
                 // One LDS address per lane walks the leaf: a pair is at [addr, addr + 96), the second triangle at the constant
-                // offset 48.  A lane whose leaf is used up stays where it is and tests its last pair again, result ignored: no
-                // exec-mask bookkeeping and no loop-carried copies inside the loop (the lanes of a batch are on leaves of one size
-                // class, so they nearly all run to the end together anyway).
+                // offset 48.  A lane whose leaf is used up stays where its last step left it -- one pair past its last one -- and
+                // tests that pair again and again, result ignored: no exec-mask bookkeeping and no loop-carried copies inside
+                // the loop (the lanes of a batch are on leaves of one size class, so they nearly all run to the end together
+                // anyway).  The pair it reads belongs to the next leaf, or behind the last leaf to the zeroed pad of pool_layout
+                // (kScenePad).  (Not advancing on a lane's last step instead costs a compare per step: measured 0.3-0.6 % slower.)
                 int left = end - cur;                                     // triangles still to test (<= 0: through)
                 uint32_t addr = lds_hot + __umul24((uint32_t)cur, 48u);
                 for (;;) {
@@ -1153,6 +1164,7 @@ hipError_t launch_path_pool(const SceneView &sc, const FrameParams &fp, int bvh_
     if (fp.width == 0 || fp.local_rows == 0 || fp.n_frames == 0) return hipSuccess;
     const int flags = choice.pool_flags;           // (+ 32 below when the stacks' upper levels go to HBM)
     const bool hbm_scene = (flags & 8) != 0, material_model = (flags & 16) != 0;
+    if (!hbm_scene && sc.n_tris >= 4096u) return hipErrorInvalidValue;      // the staged leaf references hold `first triangle` and `count` in 12 bits each
     const int env_threads = tune.threads, env_paths = tune.paths, env_fill = tune.min_fill, env_patience = tune.patience;
     const uint32_t tiles_x = (fp.width + 7) / 8, tiles_y = (fp.local_rows + 7) / 8;
     const uint64_t n_chunks = (uint64_t)tiles_x * tiles_y * fp.n_frames;

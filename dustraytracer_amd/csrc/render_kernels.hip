@@ -293,6 +293,12 @@ __global__ __launch_bounds__(256) void kat_kernel(int which, const uint32_t *in,
         const bool front = closest_hit_frame(ray, r[6], mk3(r[7], r[8], r[9]), position, normal);
         fout[7 * i] = position.x; fout[7 * i + 1] = position.y; fout[7 * i + 2] = position.z;
         fout[7 * i + 3] = normal.x; fout[7 * i + 4] = normal.y; fout[7 * i + 5] = normal.z; out[7 * i + 6] = front ? 1u : 0u;
+    } else if (which == 7) {                    // in: vec3 with components in [-1, 1] -> out: normalize, normalize_unit_cube
+        const f3 v = mk3(fin[3 * i], fin[3 * i + 1], fin[3 * i + 2]);
+        const f3 a = normalize(v), b = normalize_unit_cube(v);
+        fout[6 * i] = a.x; fout[6 * i + 1] = a.y; fout[6 * i + 2] = a.z; fout[6 * i + 3] = b.x; fout[6 * i + 4] = b.y; fout[6 * i + 5] = b.z;
+    } else if (which == 8) {                    // in: dd in [0, 3] -> out: exact_rcp(exact_sqrt(dd)), inv_length_unit_cube(dd)
+        fout[2 * i] = exact_rcp(exact_sqrt(fin[i])); fout[2 * i + 1] = inv_length_unit_cube(fin[i]);
     }
 }
 

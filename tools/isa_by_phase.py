@@ -175,7 +175,7 @@ def cold_lines():
     if COLD_LINES is None:
         COLD_LINES = set()
         for i, l in enumerate(open(os.path.join(CSRC, "device_math.hpp")).read().split("\n"), 1):
-            if re.search(r"__builtin_expect\(.*\) q = 1\.0f / x;|return sqrtf\(x\);", l):
+            if re.search(r"__builtin_expect\(.*\) (?:\{ )?q(?:\.x)? = 1\.0f / |return sqrtf\(x\);", l):
                 COLD_LINES.add(i)
     return COLD_LINES
 
