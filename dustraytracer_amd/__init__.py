@@ -333,6 +333,8 @@ _sig("drt_renderer_nearest_list", C.c_int, _P, _P, _P, _P, _P, _P, C.c_uint32, _
 _sig("drt_renderer_overlap_boxes", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_renderer_overlap_triangles", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_renderer_plane_sections", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_int32, _P)
+_sig("drt_scene_edge_adjacency", C.c_int, _P, _P, C.c_uint32)
+_sig("drt_renderer_chain_sections", C.c_int, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _P)
 _sig("drt_renderer_inside", C.c_int, _P, _P, _P, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_renderer_signed_distance", C.c_int, _P, _P, _P, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_renderer_render_guides", C.c_int, _P, C.POINTER(_CameraPOD), _P, C.c_uint32, _P, _P)
@@ -484,6 +486,15 @@ class Scene:
         """int32 [n]: the load index (setGeometry / file order) of each triangle of m_PrimitivesBuffer (drt_scene_get_triangle_order)."""
         return self._copy(_lib.drt_scene_get_triangle_order, _lib.drt_scene_triangle_count(self._h), np.int32)
 
+    def edgeAdjacency(self):
+        """int32 [n, 3]: the twin half-edge 3 * t' + e' of edge e (vertex e to vertex (e + 1) % 3) of each triangle of
+        m_PrimitivesBuffer, by bit-equal positions; -1 on a boundary edge, -2 where the edge is non-manifold, flipped or of zero
+        length (drt_scene_edge_adjacency).  Needs a BVH: the table is in tree order."""
+        n = _lib.drt_scene_triangle_count(self._h)
+        out = np.zeros((n, 3), np.int32)
+        _check(_lib.drt_scene_edge_adjacency(self._h, out.ctypes.data, 3 * n))
+        return out
+
     def _refit_arrays(self, positions, normals):
         n = _lib.drt_scene_triangle_count(self._h)
         out = []
@@ -625,6 +636,58 @@ TriTable = collections.namedtuple("TriTable", "prim count")             # the fi
 OVERLAP_LIST, OVERLAP_ANY = 0, 1                                        # drt.h DRT_OVERLAP_*
 SectionList = collections.namedtuple("SectionList", "splits p q prim code")   # every segment where planes cut the mesh, CSR (Renderer.planeSections)
 SECTION_LIST, SECTION_ANY = 0, 1                                        # drt.h DRT_SECTION_*
+CHAIN_LINKED, CHAIN_BOUNDARY, CHAIN_NON_MANIFOLD, CHAIN_NOT_LISTED, CHAIN_OTHER_EDGES, CHAIN_MISS = range(6)   # drt.h: a record's exit status
+
+
+def _segment_sums(torch, term, at):
+    """The sums of the float64 `term` over the ranges at[i]:at[i + 1], on the device, deterministic, no atomics: a running sum over ALL
+    terms and its differences at the ends of the ranges.  The running sum rounds relative to what the ranges before have summed to,
+    which would leave a small sum behind large ones with few digits.  So the error of every step, (run[i] + term[i]) - run[i + 1],
+    is computed with Knuth's two-sum and summed the same way: in exact arithmetic the two differences add up to the range's own sum
+    whatever values the scan left in `run` (a device scan does not add left to right), and in float64 the error terms are of the
+    size of run's rounding, so theirs is second order."""
+    run = torch.zeros(term.shape[0] + 1, dtype=torch.float64, device=term.device)
+    run[1:] = torch.cumsum(term, dim=0)
+    before, after = run[:-1], run[1:]
+    took = after - before
+    lost = torch.zeros_like(run)
+    lost[1:] = torch.cumsum((before - (after - took)) + (term - took), dim=0)
+    return (run[at[1:]] - run[at[:-1]]) + (lost[at[1:]] - lost[at[:-1]])
+
+
+class ContourList(collections.namedtuple("ContourList", "splits chain_splits closed p q prim code end")):
+    """The contours where planes cut the mesh (Renderer.chainSections / contours): the chains of plane i are splits[i]:splits[i + 1];
+    chain c is the records chain_splits[c]:chain_splits[c + 1] of p, q, prim, code and end, in chained order: its vertices are the p
+    of its records, plus the last q when it is open.  closed [C] bool; end [M] is each record's exit status (0 = linked to the next
+    record of its chain, or, for the last record of a closed chain, to the first; CHAIN_*).  normals: the planes' normals [N, 3]
+    where the list came from Renderer.contours, else None."""
+    normals = None
+
+    def areas(self, normals=None):
+        """float64 [C]: 0.5 * sum dot(n / |n|, cross(p, q)) over each closed chain with the normal n of its plane, NaN for an open
+        one.  On a mesh with outward faces a positive area is an outer contour and a negative one a hole.  normals [N, 3] (or
+        packed planes [N, 4]): the planes the list was made with; Renderer.contours remembers them.  Summed on the device in
+        float64 as Renderer.sectionAreas sums.  Device tensors in the list: a device tensor comes back; else a numpy array."""
+        import torch
+        nrm = self.normals if normals is None else normals
+        if nrm is None:
+            raise DrtError(ERR_INVALID, "areas: the list does not know its planes; give their normals [N, 3]")
+        as_numpy = isinstance(self.p, np.ndarray)
+        dev = torch.device("cuda", torch.cuda.current_device()) if as_numpy else self.p.device
+        dev_of = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev) if isinstance(a, np.ndarray) else a.to(dev)
+        nrm = dev_of(nrm)[:, 0:3].to(torch.float64)
+        splits, chain_splits = dev_of(self.splits).to(torch.int64), dev_of(self.chain_splits).to(torch.int64)
+        if nrm.shape[0] != splits.shape[0] - 1:
+            raise DrtError(ERR_INVALID, "areas: %d normals for %d planes" % (nrm.shape[0], splits.shape[0] - 1))
+        length = torch.sqrt((nrm * nrm).sum(dim=1, keepdim=True))
+        unit = torch.where(length > 0, nrm / torch.where(length > 0, length, torch.ones_like(length)), torch.zeros_like(nrm))
+        n_chains = chain_splits.shape[0] - 1
+        plane_of_chain = torch.repeat_interleave(torch.arange(nrm.shape[0], dtype=torch.int64, device=dev), splits[1:] - splits[:-1])
+        owner = torch.repeat_interleave(plane_of_chain, chain_splits[1:] - chain_splits[:-1])
+        term = (unit[owner] * torch.linalg.cross(dev_of(self.p).to(torch.float64), dev_of(self.q).to(torch.float64), dim=1)).sum(dim=1)
+        areas = 0.5 * _segment_sums(torch, term, chain_splits)
+        areas = torch.where(dev_of(self.closed).to(torch.bool), areas, torch.full((n_chains,), float("nan"), dtype=torch.float64, device=dev))
+        return areas.cpu().numpy() if as_numpy else areas
 INSIDE_RULES = {"parity": 0, "winding": 1}                              # Renderer.inside / signedDistance: drt.h DRT_INSIDE_*
 TemporalHistory = collections.namedtuple("TemporalHistory", "color length moments variance weight")  # Renderer.GetTemporalHistory
 Guides = collections.namedtuple("Guides", "albedo normal t prim")  # first-hit guide buffers (Renderer.renderGuides)
@@ -1382,20 +1445,92 @@ class Renderer:
         counts = (sec.splits[1:] - sec.splits[:-1]).to(torch.int64)
         owner = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=dev), counts)
         term = (unit[owner] * torch.linalg.cross(sec.p.to(torch.float64), sec.q.to(torch.float64), dim=1)).sum(dim=1)
-        # A running sum over ALL segments and its differences at the splits.  The running sum rounds relative to what the planes
-        # before have summed to, which would leave a small area behind large ones with few digits.  So the error of every step,
-        # (run[i] + term[i]) - run[i + 1], is computed with Knuth's two-sum and summed the same way: in exact arithmetic the two
-        # differences add up to the plane's own sum whatever values the scan left in `run` (a device scan does not add left to
-        # right), and in float64 the error terms are of the size of run's rounding, so theirs is second order.
-        run = torch.zeros(term.shape[0] + 1, dtype=torch.float64, device=dev)
-        run[1:] = torch.cumsum(term, dim=0)
-        before, after = run[:-1], run[1:]
-        took = after - before
-        lost = torch.zeros_like(run)
-        lost[1:] = torch.cumsum((before - (after - took)) + (term - took), dim=0)
-        at = sec.splits.to(torch.int64)
-        areas = 0.5 * ((run[at[1:]] - run[at[:-1]]) + (lost[at[1:]] - lost[at[:-1]]))
+        areas = 0.5 * _segment_sums(torch, term, sec.splits.to(torch.int64))      # (a compensated running sum: see there)
         return areas.cpu().numpy() if from_numpy else areas
+
+    def _chain(self, scene, sec):
+        """(ContourList of device tensors, slots [M, 4] int32, chains [N, 2] int32) for a SectionList of device tensors: the records
+        packed again as drt_section, drt_renderer_chain_sections, and the lists read off the slots."""
+        import torch
+        dev = torch.device("cuda", self._device)
+        splits = sec.splits.to(torch.int32).contiguous()
+        n, total = splits.shape[0] - 1, sec.prim.shape[0]
+        if n < 0 or sec.p.shape != (total, 3) or sec.q.shape != (total, 3) or sec.code.shape != (total,):
+            raise DrtError(ERR_INVALID, "a SectionList expected: splits [N + 1], p and q [M, 3], prim and code [M]")
+        if total >= 2 ** 31:
+            raise DrtError(ERR_INVALID, "%d segments in all: fewer than 2^31 expected (split the planes)" % total)
+        rec = torch.empty((total, 8), dtype=torch.float32, device=dev)         # drt_section: p, prim, q, code
+        words = rec.view(torch.int32)
+        rec[:, 0:3], rec[:, 4:7] = sec.p, sec.q
+        words[:, 3], words[:, 7] = sec.prim, sec.code
+        slots = torch.empty((total, 4), dtype=torch.int32, device=dev)
+        chains = torch.zeros((max(n, 0), 2), dtype=torch.int32, device=dev)
+        if n > 0 and total:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(_lib.drt_renderer_chain_sections(self._h, scene._h, rec.data_ptr(), splits.data_ptr(), slots.data_ptr(), chains.data_ptr(),
+                                                    n, total, stream))
+        # what the slots say: a chain starts where first == position; miss records (a list with spare capacity) are in no chain
+        status = slots[:, 3] >> 1
+        kept = status != CHAIN_MISS
+        starts = (slots[:, 1] == torch.arange(total, dtype=torch.int32, device=dev)) & kept
+        seg = slots[:, 0][kept].to(torch.int64)
+        kept_before = torch.cumsum(kept.to(torch.int64), dim=0) - kept.to(torch.int64)
+        m = seg.shape[0]
+        chain_splits = torch.cat([kept_before[starts], torch.full((1,), m, dtype=torch.int64, device=dev)]).to(torch.int32)
+        plane_splits = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        plane_splits[1:] = torch.cumsum(chains[:, 0].to(torch.int64), dim=0)
+        chained = rec[seg]                                                     # the records in chained order
+        chained_words = chained.view(torch.int32)
+        out = ContourList(plane_splits.to(torch.int32), chain_splits, (slots[:, 3][starts] & 1).to(torch.bool), chained[:, 0:3], chained[:, 4:7],
+                          chained_words[:, 3], chained_words[:, 7], status[kept])
+        return out, slots, chains
+
+    def chainSections(self, scene, sections):
+        """The segments of a SectionList (planeSections, slices) chained into contours: open polylines and closed loops per plane
+        (drt_renderer_chain_sections).  The successor of a segment is the segment of the triangle across the edge it leaves
+        through, looked up in the scene's edge adjacency (Scene.edgeAdjacency): integers only, no welding, no tolerance, and the
+        result is the same bit for bit on every run.  A path starts at its record without a predecessor, a cycle at its record of
+        smallest index; a plane's chains are ordered by their first record.  ContourList(splits [N + 1], chain_splits [C + 1],
+        closed [C], p [M, 3], q [M, 3], prim [M], code [M], end [M]): the chains of plane i are splits[i]:splits[i + 1], chain c
+        is the records chain_splits[c]:chain_splits[c + 1], gathered into chained order; end is each record's exit status (0 =
+        linked, 1 = boundary edge, 2 = non-manifold or flipped edge, 3 = the neighbour is not in the list, 4 = the neighbour is cut
+        through other edges).  A contour is closed exactly where neighbouring triangles agree on which of their shared vertices
+        are above the plane.  No caps or filled polygons.  Device tensors in, device tensors out (enqueued on the current torch
+        stream); numpy in, numpy out."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        if not isinstance(sections, tuple) or len(sections) != 5:
+            raise DrtError(ERR_INVALID, "a SectionList expected")
+        from_numpy = isinstance(sections[0], np.ndarray)
+        want = (("splits", np.int32, torch.int32), ("p", np.float32, torch.float32), ("q", np.float32, torch.float32),
+                ("prim", np.int32, torch.int32), ("code", np.int32, torch.int32))
+        parts = []
+        for a, (what, np_type, torch_type) in zip(sections, want):
+            if isinstance(a, np.ndarray) != from_numpy or not (from_numpy or torch.is_tensor(a)):
+                raise DrtError(ERR_INVALID, "%s: numpy arrays or device tensors expected, not a mix" % what)
+            if from_numpy:
+                if a.dtype != np_type:
+                    raise DrtError(ERR_INVALID, "%s: dtype %s, %s expected" % (what, a.dtype, np.dtype(np_type)))
+                a = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+            elif a.dtype != torch_type or a.device != dev:
+                raise DrtError(ERR_INVALID, "%s: %s on %s, %s on %s expected" % (what, a.dtype, a.device, torch_type, dev))
+            parts.append(a)
+        res = self._chain(scene, SectionList(*parts))[0]
+        if from_numpy:
+            return ContourList(*(x.cpu().numpy().copy() for x in res))
+        return res
+
+    def contours(self, scene, normals, d=None):
+        """planeSections followed by chainSections: the ContourList of the planes dot(n, x) = d, which remembers their normals for
+        ContourList.areas().  Planes and conventions as planeSections."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        planes, from_numpy = _plane_batch(torch, dev, normals, d)
+        res = self._chain(scene, self._sections(scene, planes))[0]
+        if from_numpy:
+            res = ContourList(*(x.cpu().numpy().copy() for x in res))
+        res.normals = planes[:, 0:3].cpu().numpy().copy() if from_numpy else planes[:, 0:3].clone()
+        return res
 
     def voxelize(self, scene, resolution, lo=None, hi=None):
         """Conservative surface voxelisation: a bool [Z, Y, X] device tensor, true where a triangle touches the (closed) cell, over

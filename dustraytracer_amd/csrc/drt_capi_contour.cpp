@@ -1,0 +1,65 @@
+// drt_capi_contour.cpp -- the section-contour entry points of include/drt.h: drt_scene_edge_adjacency (the host table) and
+// drt_renderer_chain_sections (kernel_contour.hip): the plane-section query's argument checks in its order, the scene upload, the
+// device copy of the adjacency beside it, the scratch and the launches.
+#include "renderer_state.hpp"
+
+#include "contour.hpp"
+
+using namespace drt;
+
+extern "C" {
+
+int drt_scene_edge_adjacency(const drt_scene *scene, int32_t *out, uint32_t capacity) {
+    if (!scene) return fail(DRT_ERR_INVALID, "null scene");
+    const size_t words = 3 * scene->host.triangles.size();
+    if (capacity < words) return fail(DRT_ERR_INVALID, "destination too small: 3 values per triangle");
+    if (!out && words) return fail(DRT_ERR_INVALID, "null destination");
+    try {
+        const std::vector<int32_t> adj = scene->host.edge_adjacency();
+        if (words) std::memcpy(out, adj.data(), words * sizeof(int32_t));
+        return DRT_OK;
+    } catch (const std::invalid_argument &e) { return fail(DRT_ERR_INVALID, e.what());
+    } catch (const std::exception &e) { return fail(DRT_ERR_INVALID, e.what()); }
+}
+
+// drt_renderer_plane_sections' checks in its order (segs for planes, splits for offsets, slots for out, chains for counts; there is no
+// mode).  The adjacency is uploaded with the first call after a scene upload and dropped with that upload.
+int drt_renderer_chain_sections(drt_renderer *r, const drt_scene *scene, const drt_section *segs, const uint32_t *splits, drt_chain_slot *slots,
+                                uint32_t *chains, uint32_t n, uint32_t total, void *hip_stream) {
+    if (!r || !scene) return fail(DRT_ERR_INVALID, "null argument");
+    if (n == 0 || total == 0) return DRT_OK;
+    if (!segs || !splits || !slots) return fail(DRT_ERR_INVALID, "null segment, split or slot pointer");
+    if (((uintptr_t)segs & 15u) != 0 || ((uintptr_t)slots & 15u) != 0 || ((uintptr_t)splits & 3u) != 0 || ((uintptr_t)chains & 3u) != 0)
+        return fail(DRT_ERR_INVALID, "segs and slots must be 16-byte aligned, splits and chains 4-byte aligned");
+    if (n > 0x7fffffffu) return fail(DRT_ERR_INVALID, "at most 2^31 - 1 planes per call");
+    if (total > 0x7fffffffu) return fail(DRT_ERR_INVALID, "at most 2^31 - 1 records per call");
+    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
+    HIP_TRY(hipSetDevice(r->device));
+    (void)hipGetLastError();                   // (see render_batch_impl: only this call's own errors count)
+    if (!on_renderer_device(r, segs) || !on_renderer_device(r, splits) || !on_renderer_device(r, slots) || (chains && !on_renderer_device(r, chains)))
+        return fail(DRT_ERR_INVALID, "segs, splits, slots and chains must be device memory on the renderer's device");
+    if (int rc = upload_scene(r, scene)) return rc;
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : r->stream;
+    if (int rc = query_order(r, s)) return rc;
+    if (!r->adj_built) {                       // the host scene's table: a device refit keeps the order and what is shared
+        std::vector<int32_t> adj;
+        try { adj = scene->host.edge_adjacency(); } catch (const std::exception &e) { return fail(DRT_ERR_INVALID, e.what()); }
+        HIP_TRY(r->d_adj.upload(adj));
+        r->adj_built = true;
+    }
+    // scratch: grown only once the query in flight is over
+    const size_t words = contour_scratch_words(total);
+    if (words > r->contour_work.count) {
+        if (r->query_recorded) HIP_TRY(hipEventSynchronize(r->ev_query));
+        HIP_TRY(r->contour_work.alloc(words));
+    }
+    ContourArgs a;
+    a.segs = segs; a.splits = splits; a.slots = slots; a.chains = chains;
+    a.adj = r->d_adj.ptr;
+    a.n = n; a.total = total; a.n_tris = r->view.n_tris;
+    contour_carve(a, r->contour_work.ptr);
+    HIP_TRY(launch_contour(a, s));
+    return query_recorded(r, s);
+}
+
+}  // extern "C"

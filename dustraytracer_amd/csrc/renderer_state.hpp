@@ -1,4 +1,4 @@
-// renderer_state.hpp -- what the translation units of the C ABI share (drt_capi.cpp, drt_capi_filters.cpp, drt_capi_adaptive.cpp, drt_capi_section.cpp): the renderer's state,
+// renderer_state.hpp -- what the translation units of the C ABI share (drt_capi.cpp, drt_capi_filters.cpp, drt_capi_adaptive.cpp, drt_capi_section.cpp, drt_capi_contour.cpp): the renderer's state,
 // the owners of its device memory, pinned memory and events, error reporting, the steps several entry points take.  Not exported.
 #pragma once
 #include "../../include/drt.h"
@@ -163,6 +163,11 @@ struct drt_renderer {
     DeviceArray<uint32_t> section_work;
     int section_waves = 0;                     // DRT_SECTION_WAVES: at most this many waves per launch (0 = no cap)
     bool leaves_ascending = true;
+    // drt_renderer_chain_sections: the uploaded scene's edge adjacency (made by the first call after an upload, dropped with the scene
+    // copy) and the scratch of kernel_contour.hip (contour.hpp: contour_scratch_words), grown on demand as section_work is
+    DeviceArray<int32_t> d_adj;
+    bool adj_built = false;
+    DeviceArray<uint32_t> contour_work;
     drt::FilterKernel filter_kernel = drt::FilterKernel::automatic;      // DRT_FILTER_KERNEL=lds / taps: one a-trous kernel for every pass (unset, or any other value: launch_atrous's rule)
     int rq_refill_min = 16;                    // DRT_RQ_REFILL: idle lanes that make a wave claim new rays (64 = only when all are)
     // drt_renderer_denoise: frame 1's guides and the two float4 buffers the passes ping-pong between, allocated by the first call,
@@ -230,6 +235,8 @@ struct drt_renderer {
         rf_built = false;
         mv_snap.release();
         mv_armed = false;
+        d_adj.release();
+        adj_built = false;
         uploaded_scene = nullptr;
     }
     void free_upscale() {

@@ -59,6 +59,10 @@ public:
     // order kept.  Throws std::invalid_argument (no BVH, a non-finite value) before anything is written.
     void refit(const float *pos, const float *nrm);
 
+    // Edge adjacency (drt_scene_edge_adjacency): adj[3 t + e] for half-edge e of triangle t in tree order: its twin, -1 on a
+    // boundary edge, -2 where the edge is non-manifold, flipped or of zero length.  Throws std::invalid_argument without a BVH.
+    std::vector<int32_t> edge_adjacency() const;
+
     // Device-layout image of the scene (see device_scene.hpp); throws when there is no BVH.
     PackedScene pack() const;
 };

@@ -152,6 +152,13 @@ struct Scene {
         if (!v.empty()) drt::check(drt_scene_get_triangle_order(handle, v.data(), (int32_t)v.size()));
         return v;
     }
+    // new: the twin of every half-edge 3 t + e of primitives(), -1 on a boundary edge, -2 where the edge is non-manifold, flipped or
+    // of zero length, by bit-equal positions (drt_scene_edge_adjacency); needs a BVH: the table is in tree order
+    std::vector<int32_t> EdgeAdjacency() const {
+        std::vector<int32_t> v(3 * trianglesCount());
+        drt::check(drt_scene_edge_adjacency(handle, v.data(), (uint32_t)v.size()));
+        return v;
+    }
     // new: refit the BVH to moved vertices, float[n][3][3] in load order; normals nullptr = keep them (drt_scene_refit)
     void Refit(const float *positions, const float *normals = nullptr) { drt::check(drt_scene_refit(handle, positions, normals)); }
     void refresh() {                                                      // after anything that changes the scene
@@ -352,6 +359,15 @@ public:
     void PlaneSections(const Scene &scene, const drt_plane *planes, const uint32_t *offsets, drt_section *out, uint32_t out_capacity,
                        uint32_t *counts, uint32_t n, int32_t mode, void *stream = nullptr) {
         drt::check(drt_renderer_plane_sections(handle, scene.handle, planes, offsets, out, out_capacity, counts, n, mode, stream));
+    }
+    // new: the records of PlaneSections chained into contours by the mesh's edge adjacency, integers only (drt_renderer_chain_sections):
+    // plane i owns segs and slots [splits[i], splits[i + 1]); slots[pos] = {seg, first, length, flags} in canonical order -- a path from
+    // its record without a predecessor, a cycle from its smallest record, chains by their first record, miss records last; flags bit 0 =
+    // closed, bits 1..3 = the record's exit status.  chains (may be null) = per plane {chains, closed ones}.  Device arrays, segs and
+    // slots 16-byte aligned, enqueued on `stream`.
+    void ChainSections(const Scene &scene, const drt_section *segs, const uint32_t *splits, drt_chain_slot *slots, uint32_t *chains, uint32_t n,
+                       uint32_t total, void *stream = nullptr) {
+        drt::check(drt_renderer_chain_sections(handle, scene.handle, segs, splits, slots, chains, n, total, stream));
     }
     // new: RayGen's primary rays of n_cams cameras for a width x height image, frame `frame_index` (drt_renderer_camera_rays): a device
     // drt_path_ray[n_cams * width * height], enqueued on `stream`

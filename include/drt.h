@@ -582,6 +582,53 @@ int           drt_renderer_plane_sections(drt_renderer *r, const drt_scene *scen
                                           drt_section *out, uint32_t out_capacity, uint32_t *counts, uint32_t n, int32_t mode,
                                           void *hip_stream);
 
+/* ---- section contours (new; a plane's segments chained into open polylines and closed loops, by integers only) ----
+ * The records of a plane are separate segments in triangle order.  prim and code of a record say which two edges of which triangle
+ * the segment enters and leaves through, so with a table of the mesh's edge adjacency the successor of a segment is an integer
+ * question: no coordinate is compared, no tolerance is chosen, and nothing is welded.
+ * Edge adjacency, drt_scene_edge_adjacency: out receives 3 * n_triangles host values; capacity is the room in values.  Half-edge
+ * h = 3 * t + e, with t in tree order (the index every query reports) and e in {0, 1, 2}, runs from vertex e to vertex (e + 1) % 3
+ * of the positions the host scene holds (drt_scene_get_triangles; not the packed v0 + e1).  Two positions are the same iff their
+ * three words are bit-equal (-0.0 is not +0.0).  The half-edges are grouped by their unordered pair of endpoint positions.  A group
+ * of exactly two half-edges that run in opposite directions is a pair of twins: adj[h] = h' and adj[h'] = h.  A group of one is a
+ * boundary edge: adj[h] = -1.  Everything else is -2: three or more half-edges, two that run the same way, and an edge whose two
+ * ends are the same position.  DRT_ERR_INVALID: a NULL scene, capacity below 3 * n_triangles, no BVH (the table is in tree order).
+ * A renderer keeps a device copy of the table beside its copy of the scene: made by the first drt_renderer_chain_sections after an
+ * upload, dropped with that upload.  After a device-only drt_renderer_refit the table is still the host scene's: a refit keeps the
+ * triangle order, and a deformation keeps shared positions shared.
+ * drt_renderer_chain_sections: segs, splits, slots and chains are device pointers on the renderer's device; the call is enqueued on
+ * hip_stream (NULL = the renderer's) and orders with the other queries as they do.
+ * Inputs: splits holds n + 1 values; plane i owns segs[splits[i] .. splits[i+1]) and slots[splits[i] .. splits[i+1]).  The range
+ * is clamped as drt_renderer_plane_sections clamps cap_i: a decreasing pair is an empty range, and nothing beyond total is read or
+ * written.  A range is what a fill wrote: records in ascending prim, followed by any miss records (prim < 0).  Unsorted input gives
+ * unspecified links, but the call completes and every index it writes is inside the plane's own range.  Records outside every
+ * range belong to no chain and their slots are not written.
+ * Link: for a record j, k = code & 3 and up = code >> 2.  It is entered through edge in_j = up ? k : (k + 2) % 3 and left
+ * through edge out_j = up ? (k + 2) % 3 : k (P lies on edge k, Q lies on edge (k + 2) % 3, and the segment runs P -> Q iff the
+ * apex is above).  Let a = adj[3 * prim_j + out_j].  succ(j) = m iff a >= 0, m is the record of the same plane with
+ * prim_m == a / 3 (found by binary search in the ascending prefix), and 3 * prim_m + in_m == a.  Otherwise j has no successor and
+ * its exit status says why: 1 = boundary edge (a == -1), 2 = non-manifold or flipped (a == -2), 3 = the neighbour is not in the
+ * list, 4 = the neighbour is cut through other edges, 5 = j is a miss record.  0 = linked.  adj pairs half-edges one to one, so
+ * succ is injective: every record has at most one predecessor, and the components are simple paths and simple cycles.
+ * Canonical order: a path starts at its record without a predecessor; a cycle starts at its record of smallest index, and is
+ * closed.  The chains of a plane are ordered by the ascending index of their first record.  Miss records stay where they are, after
+ * all chains.  Position pos runs over the plane's range in that order, and slots[pos] holds: seg = the index into segs of the
+ * record that stands there; first = the position of its chain's first record; length = its chain's length; flags: bit 0 = the
+ * chain is closed, bits 1..3 = that record's exit status.  A miss record is {own index, own position, 1, 5 << 1}.
+ * chains[2 * i] is the number of chains of plane i, misses not counted; chains[2 * i + 1] is how many of them are closed.  chains
+ * may be NULL.  The result depends on segs, splits and the adjacency only.
+ * What it is not: no welding and no new points -- a contour's vertices are the p of its records, plus the last q of an open
+ * chain; a contour is closed exactly where neighbouring triangles agree on which of their shared vertices are above the plane, and
+ * statuses 3 and 4 mark the places where they do not; no caps or filled polygons; no RendererGroup; nothing on the command line.
+ * Checks, in drt_renderer_plane_sections' order: NULL r or scene; n == 0 or total == 0 is DRT_OK with no launch; NULL segs, splits
+ * or slots; segs and slots 16-byte aligned, splits and chains 4-byte aligned; n < 2^31 and total < 2^31; no pending asynchronous
+ * batch; device memory on the renderer's device; the scene's upload (DRT_ERR_UNSUPPORTED beyond 64 levels).  All DRT_ERR_INVALID
+ * but the last.  The framebuffer, accumulation, sample count, counters, kernel info and kernel span are not touched. */
+typedef struct drt_chain_slot { uint32_t seg; uint32_t first; uint32_t length; uint32_t flags; } drt_chain_slot;   /* 16 B */
+int           drt_scene_edge_adjacency(const drt_scene *scene, int32_t *out, uint32_t capacity);
+int           drt_renderer_chain_sections(drt_renderer *r, const drt_scene *scene, const drt_section *segs, const uint32_t *splits,
+                                          drt_chain_slot *slots, uint32_t *chains, uint32_t n, uint32_t total, void *hip_stream);
+
 /* ---- sphere casts (new; the first contact of a moving sphere with the mesh) ----
  * One cast = a drt_ray (org o, tmin, dir d, tmax, read as drt_renderer_trace_rays reads it: dir as given, t in units of |d|,
  * inv_dir = 1/dir) and a radius r.  The sphere's centre at parameter t is o + d t; the answer is the smallest t in [tmin, tmax) at
