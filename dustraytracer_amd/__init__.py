@@ -335,6 +335,11 @@ _sig("drt_renderer_overlap_triangles", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, 
 _sig("drt_renderer_plane_sections", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_scene_edge_adjacency", C.c_int, _P, _P, C.c_uint32)
 _sig("drt_renderer_chain_sections", C.c_int, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _P)
+_sig("drt_renderer_shell_labels", C.c_int, _P, _P, _P, _P, _P)
+_sig("drt_renderer_boundary_loops", C.c_int, _P, _P, _P, C.c_uint32, _P, _P)
+_sig("drt_renderer_shell_terms", C.c_int, _P, _P, _P, _P)
+_sig("drt_renderer_edge_adjacency", C.c_int, _P, _P, _P, _P)
+_sig("drt_renderer_topology_steps", C.c_int, _P, _P)
 _sig("drt_renderer_inside", C.c_int, _P, _P, _P, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_renderer_signed_distance", C.c_int, _P, _P, _P, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_renderer_render_guides", C.c_int, _P, C.POINTER(_CameraPOD), _P, C.c_uint32, _P, _P)
@@ -688,7 +693,11 @@ class ContourList(collections.namedtuple("ContourList", "splits chain_splits clo
         areas = 0.5 * _segment_sums(torch, term, chain_splits)
         areas = torch.where(dev_of(self.closed).to(torch.bool), areas, torch.full((n_chains,), float("nan"), dtype=torch.float64, device=dev))
         return areas.cpu().numpy() if as_numpy else areas
-INSIDE_RULES = {"parity": 0, "winding": 1}                              # Renderer.inside / signedDistance: drt.h DRT_INSIDE_*
+# Mesh topology (drt.h "mesh topology"), everything in tree order (Scene.triangleOrder() maps it to load order)
+Shells = collections.namedtuple("Shells", "label index count triangles open_edges bad_edges watertight")   # Renderer.shells
+LoopList = collections.namedtuple("LoopList", "splits closed half_edge prim edge shell end")              # Renderer.boundaryLoops
+ShellMeasures = collections.namedtuple("ShellMeasures", "area volume area_vector")                        # Renderer.shellMeasures
+INSIDE_RULES = {"parity": 0, "winding": 1}                             # Renderer.inside / signedDistance: drt.h DRT_INSIDE_*
 TemporalHistory = collections.namedtuple("TemporalHistory", "color length moments variance weight")  # Renderer.GetTemporalHistory
 Guides = collections.namedtuple("Guides", "albedo normal t prim")  # first-hit guide buffers (Renderer.renderGuides)
 AdaptiveState = collections.namedtuple("AdaptiveState", "sum count m1 m2 last_q last_count")  # Renderer.GetAdaptiveState
@@ -1531,6 +1540,107 @@ class Renderer:
             res = ContourList(*(x.cpu().numpy().copy() for x in res))
         res.normals = planes[:, 0:3].cpu().numpy().copy() if from_numpy else planes[:, 0:3].clone()
         return res
+
+    def _shells(self, scene):
+        """Shells of device tensors (count a Python int): drt_renderer_shell_labels, and the per-shell arrays made with torch."""
+        import torch
+        dev = torch.device("cuda", self._device)
+        n = _lib.drt_scene_triangle_count(scene._h)
+        label = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+        adj = torch.empty((max(n, 1), 3), dtype=torch.int32, device=dev)
+        counts = torch.zeros(3, dtype=torch.int32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _check(_lib.drt_renderer_shell_labels(self._h, scene._h, label.data_ptr(), counts.data_ptr(), stream))
+        _check(_lib.drt_renderer_edge_adjacency(self._h, scene._h, adj.data_ptr(), stream))
+        label, adj = label[:n], adj[:n]
+        count = int(counts[0])
+        root = label == torch.arange(n, dtype=torch.int32, device=dev)
+        dense = torch.cumsum(root.to(torch.int64), dim=0) - 1                  # a root's shell number: roots ascend with their labels
+        index = dense[label.to(torch.int64)]
+        per_shell = lambda per_tri: torch.zeros(count, dtype=torch.int64, device=dev).index_add_(0, index, per_tri.to(torch.int64)).to(torch.int32)
+        triangles = per_shell(torch.ones(n, dtype=torch.int64, device=dev))
+        open_edges, bad_edges = per_shell((adj == -1).sum(dim=1)), per_shell((adj == -2).sum(dim=1))
+        return Shells(label, index.to(torch.int32), count, triangles, open_edges, bad_edges, (open_edges == 0) & (bad_edges == 0))
+
+    def shells(self, scene, as_torch=False):
+        """The shells of the mesh (drt_renderer_shell_labels): triangles joined through twin half-edges of Scene.edgeAdjacency();
+        boundary edges and non-manifold, flipped or zero-length edges join nothing, nor does a shared vertex.  Shells(label [n],
+        index [n], count, triangles [S], open_edges [S], bad_edges [S], watertight [S]) in tree order (Scene.triangleOrder() maps
+        it to load order): label = the smallest triangle index of the triangle's shell, index = its dense shell number in ascending
+        order of label, and per shell the number of triangles, of half-edges on the boundary (adjacency -1) and of bad ones (-2); a
+        shell is watertight iff it has neither.  Integers only, the same bit for bit on every run.  The labels depend on the
+        adjacency alone: the first call after a scene upload computes them (and waits for the device), later ones copy; a device
+        refit keeps them.  as_torch=True: device tensors; else numpy arrays."""
+        res = self._shells(scene)
+        if as_torch:
+            return res
+        return Shells(*(x if isinstance(x, int) else x.cpu().numpy().copy() for x in res))
+
+    def boundaryLoops(self, scene, as_torch=False):
+        """The boundary of the mesh as loops (drt_renderer_boundary_loops): the half-edges without a twin, each followed by the one
+        that leaves its end vertex on the boundary, found by rotating about that vertex through the adjacency -- integers only.
+        LoopList(splits [L + 1], closed [L], half_edge [M], prim [M], edge [M], shell [L], end [M]): loop i is the records
+        splits[i]:splits[i + 1] in walking order; half_edge = 3 * prim + edge runs from vertex `edge` to vertex (edge + 1) % 3 of
+        triangle prim (tree order); shell = the dense shell number (Shells.index) of the loop's triangles; end = a record's exit
+        status (CHAIN_LINKED, or CHAIN_NON_MANIFOLD where the rotation meets a bad edge: that loop stays open).  A path starts at
+        its record without a predecessor, a cycle at its smallest half-edge; the loops are ordered by their first record."""
+        import torch
+        dev = torch.device("cuda", self._device)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        sh = self._shells(scene)
+        counts = torch.zeros(3, dtype=torch.int32, device=dev)
+        _check(_lib.drt_renderer_boundary_loops(self._h, scene._h, None, 0, counts.data_ptr(), stream))
+        m = int(counts[0])
+        slots = torch.empty((m, 4), dtype=torch.int32, device=dev)
+        if m:
+            _check(_lib.drt_renderer_boundary_loops(self._h, scene._h, slots.data_ptr(), m, counts.data_ptr(), stream))
+        # what the slots say: a loop starts where first == position
+        starts = slots[:, 1] == torch.arange(m, dtype=torch.int32, device=dev)
+        first = torch.nonzero(starts).reshape(-1)
+        splits = torch.cat([first, torch.full((1,), m, dtype=torch.int64, device=dev)]).to(torch.int32)
+        half_edge = slots[:, 0]
+        prim = torch.div(half_edge, 3, rounding_mode="floor")
+        res = LoopList(splits, (slots[:, 3][first] & 1).to(torch.bool), half_edge, prim, half_edge - 3 * prim,
+                       sh.index[prim[first].to(torch.int64)], slots[:, 3] >> 1)
+        if as_torch:
+            return res
+        return LoopList(*(x.cpu().numpy().copy() for x in res))
+
+    def shellTerms(self, scene):
+        """float64 [n, 4] on the device: per triangle {c.x, c.y, c.z, w} with c = cross(e1, e2) and w = dot(v0, c) of the device's
+        positions -- the refitted ones after Renderer.refit (drt_renderer_shell_terms; drt.h states the rounding)."""
+        import torch
+        dev = torch.device("cuda", self._device)
+        n = _lib.drt_scene_triangle_count(scene._h)
+        terms = torch.empty((max(n, 1), 4), dtype=torch.float64, device=dev)
+        _check(_lib.drt_renderer_shell_terms(self._h, scene._h, terms.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        return terms[:n]
+
+    def shellMeasures(self, scene, as_torch=False):
+        """Area, enclosed volume and area vector of every shell, float64: ShellMeasures(area [S], volume [S], area_vector [S, 3])
+        in the order of Shells.index.  From shellTerms, sorted by shell (a stable sort) and summed on the device as sectionAreas
+        sums: area = 0.5 * sum sqrt(dot(c, c)), volume = sum w / 6, area_vector = 0.5 * sum c.  The volume is signed (positive
+        for outward faces) and means something for a watertight shell, whose area vector is near zero.  After Renderer.refit
+        these are the measures of the refitted mesh."""
+        import torch
+        sh = self._shells(scene)
+        terms = self.shellTerms(scene)
+        index = sh.index.to(torch.int64)
+        terms = terms[torch.sort(index, stable=True).indices]
+        at = torch.zeros(sh.count + 1, dtype=torch.int64, device=terms.device)
+        at[1:] = torch.cumsum(sh.triangles.to(torch.int64), dim=0)
+        c = terms[:, 0:3]
+        area = 0.5 * _segment_sums(torch, torch.sqrt((c[:, 0] * c[:, 0] + c[:, 1] * c[:, 1]) + c[:, 2] * c[:, 2]), at)
+        volume = _segment_sums(torch, terms[:, 3].contiguous(), at) / 6.0
+        vector = 0.5 * torch.stack([_segment_sums(torch, c[:, k].contiguous(), at) for k in range(3)], dim=1)
+        res = ShellMeasures(area, volume, vector)
+        return res if as_torch else ShellMeasures(*(x.cpu().numpy().copy() for x in res))
+
+    def topologySteps(self):
+        """(enqueued, busy, hooks): the labelling steps of this renderer's last shell labelling (drt_renderer_topology_steps)."""
+        out = (C.c_uint32 * 3)()
+        _check(_lib.drt_renderer_topology_steps(self._h, out))
+        return tuple(int(v) for v in out)
 
     def voxelize(self, scene, resolution, lo=None, hi=None):
         """Conservative surface voxelisation: a bool [Z, Y, X] device tensor, true where a triangle touches the (closed) cell, over

@@ -1,4 +1,4 @@
-// renderer_state.hpp -- what the translation units of the C ABI share (drt_capi.cpp, drt_capi_filters.cpp, drt_capi_adaptive.cpp, drt_capi_section.cpp, drt_capi_contour.cpp): the renderer's state,
+// renderer_state.hpp -- what the translation units of the C ABI share (drt_capi.cpp, drt_capi_filters.cpp, drt_capi_adaptive.cpp, drt_capi_section.cpp, drt_capi_contour.cpp, drt_capi_topology.cpp): the renderer's state,
 // the owners of its device memory, pinned memory and events, error reporting, the steps several entry points take.  Not exported.
 #pragma once
 #include "../../include/drt.h"
@@ -168,6 +168,16 @@ struct drt_renderer {
     DeviceArray<int32_t> d_adj;
     bool adj_built = false;
     DeviceArray<uint32_t> contour_work;
+    // mesh topology (drt_capi_topology.cpp): what depends on the adjacency alone is made by the first call after an upload and lives as
+    // long as d_adj does -- the shell labels, the counts {shells, open, bad half-edges} on the device and on the host, the ascending
+    // list of boundary half-edges -- and the scratch of kernel_topology.hip (topology.hpp), grown on demand as contour_work is;
+    // topo_steps = labelling steps {enqueued, that did something, that hooked} of the last labelling
+    bool topo_built = false;
+    DeviceArray<int32_t> topo_labels;
+    DeviceArray<uint32_t> topo_counts, topo_boundary;
+    uint32_t topo_counts_host[3] = { 0, 0, 0 };
+    uint32_t topo_steps[3] = { 0, 0, 0 };
+    DeviceArray<uint32_t> topo_work;
     drt::FilterKernel filter_kernel = drt::FilterKernel::automatic;      // DRT_FILTER_KERNEL=lds / taps: one a-trous kernel for every pass (unset, or any other value: launch_atrous's rule)
     int rq_refill_min = 16;                    // DRT_RQ_REFILL: idle lanes that make a wave claim new rays (64 = only when all are)
     // drt_renderer_denoise: frame 1's guides and the two float4 buffers the passes ping-pong between, allocated by the first call,
@@ -237,6 +247,8 @@ struct drt_renderer {
         mv_armed = false;
         d_adj.release();
         adj_built = false;
+        topo_labels.release(); topo_counts.release(); topo_boundary.release();
+        topo_built = false;
         uploaded_scene = nullptr;
     }
     void free_upscale() {

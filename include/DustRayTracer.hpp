@@ -369,6 +369,21 @@ public:
                        uint32_t total, void *stream = nullptr) {
         drt::check(drt_renderer_chain_sections(handle, scene.handle, segs, splits, slots, chains, n, total, stream));
     }
+    // new: mesh topology (drt.h "mesh topology"), all in tree order and on device arrays, enqueued on `stream`.  ShellLabels: labels[t] =
+    // the smallest triangle index of t's shell (triangles joined by twin half-edges), counts (may be null) = {shells, open half-edges,
+    // bad half-edges}.  BoundaryLoops: the boundary half-edges chained into loops by rotation about their end vertices, one 16-byte
+    // slot per record, truncated at `capacity` (slots null and capacity 0: a pure count); counts = {records, loops, closed loops}.
+    // ShellTerms: per triangle {c.x, c.y, c.z, w} in float64 from the device's positions, c = cross(e1, e2) and w = dot(v0, c): the sum
+    // of w / 6 over a shell is its volume, |c| / 2 a triangle's area.  terms and slots 16-byte aligned.
+    void ShellLabels(const Scene &scene, int32_t *labels, uint32_t *counts = nullptr, void *stream = nullptr) {
+        drt::check(drt_renderer_shell_labels(handle, scene.handle, labels, counts, stream));
+    }
+    void BoundaryLoops(const Scene &scene, drt_loop_slot *slots, uint32_t capacity, uint32_t *counts, void *stream = nullptr) {
+        drt::check(drt_renderer_boundary_loops(handle, scene.handle, slots, capacity, counts, stream));
+    }
+    void ShellTerms(const Scene &scene, double *terms, void *stream = nullptr) {
+        drt::check(drt_renderer_shell_terms(handle, scene.handle, terms, stream));
+    }
     // new: RayGen's primary rays of n_cams cameras for a width x height image, frame `frame_index` (drt_renderer_camera_rays): a device
     // drt_path_ray[n_cams * width * height], enqueued on `stream`
     void CameraRays(const drt_camera *cams, uint32_t n_cams, uint32_t width, uint32_t height, uint32_t frame_index, drt_path_ray *rays,

@@ -629,6 +629,61 @@ int           drt_scene_edge_adjacency(const drt_scene *scene, int32_t *out, uin
 int           drt_renderer_chain_sections(drt_renderer *r, const drt_scene *scene, const drt_section *segs, const uint32_t *splits,
                                           drt_chain_slot *slots, uint32_t *chains, uint32_t n, uint32_t total, void *hip_stream);
 
+/* ---- mesh topology (new; shells, boundary loops, per-triangle area and volume terms) ----
+ * How many pieces a mesh is, which triangle belongs to which, whether a piece is watertight, where its holes are, and what area and
+ * volume it has.  Everything is in tree order, the order of drt_scene_get_triangles and of drt_scene_edge_adjacency
+ * (drt_scene_get_triangle_order maps it to load order), and adj is the table of drt_scene_edge_adjacency, exactly as it stands: the
+ * labels and the loops are a property of that table alone, and any correct method gives the same bytes.
+ * Shells: triangles t and t' are joined iff adj[3 * t + e] >= 0 and adj[3 * t + e] / 3 == t' for some e: a pair of twins.  A
+ * boundary edge (-1) and a non-manifold, flipped or zero-length edge (-2) join nothing: the three leaves of a book are three shells, and
+ * triangles that share only a vertex are separate shells.  label[t] is the smallest triangle index of t's connected component.
+ * counts = {shells, open half-edges, bad half-edges}: the triangles with label[t] == t, the half-edges with adj == -1 and those
+ * with adj == -2.  Per shell, open_edges[s] and bad_edges[s] count the same over the half-edges of its triangles, and a shell is
+ * watertight iff both are zero.
+ * Boundary loops: the records are the half-edges h = 3 * t + e with adj[h] == -1, in ascending h.  Half-edge h runs from vertex e
+ * to vertex b = (e + 1) % 3 of t.  Its successor is found by rotating about b through the adjacency; no coordinate is read.  Start
+ * with g = 3 * t + (e + 1) % 3.  While adj[g] >= 0: g' = adj[g], t' = g' / 3, e' = g' % 3, g = 3 * t' + (e' + 1) % 3.  If
+ * adj[g] == -1 then succ(h) = g.  If adj[g] == -2 the record has no successor and its exit status is 2; the statuses are the section
+ * contours': 0 = linked, 2 = non-manifold or flipped.  The walk ends: twins pair half-edges one to one, so the half-edges around b
+ * that the steps visit form a path of degree at most 2, the walk starts at an end of it and cannot cycle, and it ends within the
+ * valence of b.  An implementation still carries a step guard of 3 * n_triangles and treats its expiry as status 2.  succ is
+ * injective, so the components are simple paths and simple cycles.  Canonical order, the contours' rule: a path starts at its record
+ * without a predecessor; a cycle starts at its smallest h, and is closed; the loops are ordered by their first record.  All
+ * half-edges of a loop lie in one shell: a loop carries that shell's label.
+ * Position pos runs over the records in that order, and slots[pos] holds: half_edge = the h that stands there; first = the position
+ * of its loop's first record; length = its loop's length; flags: bit 0 = the loop is closed, bits 1..3 = that record's exit status.
+ * counts = {records, loops, closed loops}.  slots[pos] is written for pos < capacity and nothing else is: a too small capacity
+ * truncates, and counts still holds the true numbers.  slots is NULL iff capacity == 0: a pure count.
+ * Measure terms: one 32-byte record per triangle, computed from the device's packed (v0, e1, e2) -- after a device-only
+ * drt_renderer_refit these are the refitted positions.  With v0, e1, e2 converted to float64: c = cross(e1, e2), each component as
+ * a * b - c * d (c.x = e1.y e2.z - e1.z e2.y, c.y = e1.z e2.x - e1.x e2.z, c.z = e1.x e2.y - e1.y e2.x), and
+ * w = (v0.x * c.x + v0.y * c.y) + v0.z * c.z.  Every product and sum is rounded on its own, no contraction, no square root.  The
+ * record is {c.x, c.y, c.z, w}.  dot(v0, cross(v0 + e1, v0 + e2)) == dot(v0, cross(e1, e2)) in exact arithmetic, so w / 6 summed
+ * over a shell is its signed volume, |c| / 2 is a triangle's area, and sum c / 2 is near zero for a watertight shell.
+ * The calls: labels (n_triangles int32), counts, slots and terms (4 float64 per triangle) are device pointers on the renderer's
+ * device; the work is enqueued on hip_stream (NULL = the renderer's) and orders with the other queries as they do.  The labels, the
+ * counts and the list of records depend on adj only: a renderer makes them with the first call after a scene upload (that call
+ * waits for the stream while it labels), keeps them beside its copy of adj across device refits, and drops them with that upload.
+ * drt_renderer_edge_adjacency copies the renderer's device copy of adj (3 * n_triangles int32) to a device array, for work on
+ * the table that stays on the device.  drt_renderer_topology_steps: out receives 3 host values about that labelling: the steps enqueued, those that did something and
+ * those that hooked.
+ * What it is not: no joining across non-manifold edges or by shared vertices; no Euler characteristic, genus or vertex welding; no
+ * orientation repair; the other queries are not filtered by shell; no RendererGroup; nothing on the command line.
+ * Checks, in drt_renderer_chain_sections' order: NULL r or scene; NULL labels, counts of drt_renderer_boundary_loops or terms (the
+ * counts of drt_renderer_shell_labels may be NULL), slots NULL with a capacity or not NULL without one; labels and counts 4-byte
+ * aligned, slots and terms 16-byte aligned; capacity < 2^31; no pending asynchronous batch; device memory on the renderer's device;
+ * the scene's upload (DRT_ERR_UNSUPPORTED beyond 64 levels); no BVH as drt_scene_edge_adjacency.  All DRT_ERR_INVALID but the upload's.
+ * DRT_ERR_DEVICE if the labelling does not settle within its bound on steps.  A scene without triangles is DRT_OK with zero counts.
+ * The framebuffer, accumulation, sample count, counters, kernel info and kernel span are not touched. */
+typedef struct drt_loop_slot { uint32_t half_edge; uint32_t first; uint32_t length; uint32_t flags; } drt_loop_slot;   /* 16 B */
+typedef struct drt_shell_term { double c[3]; double w; } drt_shell_term;                                              /* 32 B */
+int           drt_renderer_shell_labels(drt_renderer *r, const drt_scene *scene, int32_t *labels, uint32_t *counts, void *hip_stream);
+int           drt_renderer_boundary_loops(drt_renderer *r, const drt_scene *scene, drt_loop_slot *slots, uint32_t capacity,
+                                          uint32_t *counts, void *hip_stream);
+int           drt_renderer_shell_terms(drt_renderer *r, const drt_scene *scene, double *terms, void *hip_stream);
+int           drt_renderer_edge_adjacency(drt_renderer *r, const drt_scene *scene, int32_t *adj, void *hip_stream);
+int           drt_renderer_topology_steps(const drt_renderer *r, uint32_t *out);
+
 /* ---- sphere casts (new; the first contact of a moving sphere with the mesh) ----
  * One cast = a drt_ray (org o, tmin, dir d, tmax, read as drt_renderer_trace_rays reads it: dir as given, t in units of |d|,
  * inv_dir = 1/dir) and a radius r.  The sphere's centre at parameter t is o + d t; the answer is the smallest t in [tmin, tmax) at
