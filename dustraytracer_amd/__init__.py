@@ -2092,7 +2092,8 @@ class Renderer:
 
     def setFramesInFlight(self, n):
         """Hint that n launches are kept in flight on this device (other renderers on other streams): small launches get
-        smaller grids so that they overlap.  Does not change results."""
+        smaller grids so that they overlap -- a share of 1/n while n is below the runtime's hardware queue count, else of one over half
+        that count (drt.h).  Does not change results."""
         _check(_lib.drt_renderer_set_frames_in_flight(self._h, int(n)))
 
     def waveQueuePlans(self):

@@ -461,6 +461,13 @@ drt_renderer *drt_renderer_create(int32_t device) {
     t.n_fuse_loop = env_int("DRT_POOL_N_FUSE_LOOP", t.n_fuse_loop); t.n_fuse_min = env_int("DRT_POOL_N_FUSE_MIN", t.n_fuse_min);
     t.cold_lds_kb = env_int("DRT_POOL_COLD_KB", t.cold_lds_kb); t.share_grid = env_int("DRT_POOL_SHARE_GRID", t.share_grid);
     t.dir_tries = env_int("DRT_POOL_DIR_TRIES", t.dir_tries);
+    // launches of different streams that reliably run side by side (pool_share.hpp): the HIP runtime spreads a process's streams over
+    // GPU_MAX_HW_QUEUES hardware queues (4 unless the environment says otherwise) and reads that variable once, when it starts -- so
+    // it is read once per process here too, by the first renderer (the device count above has started the runtime by then): a change
+    // made later reaches neither.  DRT_POOL_HW_QUEUES (tests) stands in for it per renderer; DRT_POOL_SHARE_MAX sets the result itself.
+    static const int process_hw_queues = env_int("GPU_MAX_HW_QUEUES", 0);
+    t.hw_queues = env_int("DRT_POOL_HW_QUEUES", process_hw_queues);
+    t.share_max = std::max(0, env_int("DRT_POOL_SHARE_MAX", 0));
     if (env_int("DRT_POOL_STATS", 0) != 0 && hipMalloc((void **)&t.stats, 40 * sizeof(unsigned long long)) == hipSuccess)
         (void)hipMemset(t.stats, 0, 40 * sizeof(unsigned long long));
     t.wq_only_small = env_int("DRT_WG_THREADS", 0) == 256; t.wq_only_wide = env_int("DRT_STACK_REF16", 1) == 0; t.wq_tris_wide = env_int("DRT_TRIS_WIDE", 1) != 0;

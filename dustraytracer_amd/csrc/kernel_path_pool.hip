@@ -42,6 +42,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <utility>
 
@@ -1276,8 +1277,20 @@ hipError_t launch_path_pool(const SceneView &sc, const FrameParams &fp, int bvh_
     // per step on a third of the grid each against 694 with full grids)
     // (DRT_POOL_SHARE_GRID = the number of pool refills below which a launch shares; 1 = the default of 160, 0 = never)
     const uint64_t share_refills = tune.share_grid == 1 ? 160ull : (uint64_t)std::max(0, tune.share_grid);
+    // The hint says how many launches the caller keeps in flight, not how many run side by side: the runtime multiplexes the
+    // process's streams onto its hardware queues, and two streams on one queue run one after the other.  Sharing by four while
+    // only three launches run leaves a quarter of the chip idle, and more while the host waits for the queued one -- cornell
+    // 1080p / 8 spp with four frames in flight on four hardware queues: at most three launches open, one alone 41 % of the time,
+    // 3.87 ms per step against 2.70 for one launch at a time on the full grid.  So the share is cut by what reliably runs side by
+    // side (pool_share.hpp has the rule and the measurements; DRT_POOL_SHARE_MAX overrides): the hint while it is below the number
+    // of hardware queues, else half of them -- 2.68 ms on four queues, and the quarter each as before, 2.46 ms, on eight.  A launch
+    // too many for its neighbours' shares waits in the dispatcher, where waiting costs nothing.
+    const int share_max = tune.share_max > 0 ? tune.share_max : pool_share_max(fp.frames_in_flight, tune.hw_queues);
     if (fp.frames_in_flight > 1 && share_refills > 0 && n_chunks * 64ull < share_refills * (uint64_t)num_cus * per_cu * P)
-        want = std::min<uint64_t>(want, std::max<uint64_t>(1, ((uint64_t)num_cus * per_cu + fp.frames_in_flight - 1) / (uint64_t)fp.frames_in_flight));
+        want = pool_shared_grid(want, (uint64_t)num_cus * per_cu, fp.frames_in_flight, share_max);
+    if (tune.pool_verbose)
+        std::fprintf(stderr, "path_pool launch: %llu workgroups of %llu slots (frames in flight %d, share max %d)\n", (unsigned long long)want,
+                     (unsigned long long)num_cus * per_cu, fp.frames_in_flight, share_max);
     // the part of the path state that lives in HBM: 36 bytes per pool slot of every workgroup (16 of them used by sunlight only)
     const size_t slots = (size_t)num_cus * per_cu * P;
     if (slots > scratch.slots) {

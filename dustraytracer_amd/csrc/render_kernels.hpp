@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "device_scene.hpp"
+#include "pool_share.hpp"
 
 namespace drt {
 
@@ -35,6 +36,7 @@ struct Tuning {
     uint32_t t_class[3] = { 0, 0, 0 };
     int threads = 0, paths = 0, stack_lds = 0, min_fill = 48, patience = 8, n_loop = 8, n_min_lanes = 16, n_fuse_loop = 8, n_fuse_min = 24,
         cold_lds_kb = -1, share_grid = 1, dir_tries = 4;                        // DRT_POOL_THREADS / _PATHS / _STACK_LDS / ...: path_pool's shape
+    int share_max = 0, hw_queues = 4;                                           // DRT_POOL_SHARE_MAX: launches that run side by side (0 = pool_share_max of the hint and hw_queues: GPU_MAX_HW_QUEUES as the process started with it, or DRT_POOL_HW_QUEUES)
     unsigned long long *stats = nullptr;                                        // DRT_POOL_STATS=1: device u64[40] of path_pool's statistics builds
     bool wq_only_small = false, wq_only_wide = false, wq_tris_wide = true;      // DRT_WG_THREADS=256, DRT_STACK_REF16=0, DRT_TRIS_WIDE=0: wave_queue's packagings
     int max_blocks_per_cu = 1 << 30, chunks_per_wg = 0;                         // DRT_MAX_BLOCKS_PER_CU, DRT_CHUNKS_PER_WG (0: by frames in flight)

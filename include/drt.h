@@ -1128,8 +1128,13 @@ int           drt_renderer_set_counting(drt_renderer *r, int32_t enable);     /*
 int           drt_renderer_get_counters(drt_renderer *r, drt_counters *out);
 int           drt_renderer_kernel_info(const drt_renderer *r, char *buf, size_t cap);  /* name/variant of the last kernel */
 /* Hint: the caller keeps n launches in flight on this device (several renderers, each on its own stream, driven through
- * drt_renderer_render_batch_async).  Small launches are then given fewer workgroups so that they overlap instead of
- * queueing behind each other.  Default 1 = every launch sized to fill the GPU on its own.  Results do not depend on it. */
+ * drt_renderer_render_batch_async).  Small launches are then given a share of the workgroup slots so that they overlap instead
+ * of queueing behind each other: 1/n while n is below the number of the runtime's hardware queues (GPU_MAX_HW_QUEUES, 4 by
+ * default), else one over half that number -- streams that share a queue take turns -- or 1 / min(n, DRT_POOL_SHARE_MAX) with
+ * that variable in the environment.  GPU_MAX_HW_QUEUES is read once per process, by the first drt_renderer_create, as the
+ * runtime reads it once when it starts: set it before the first HIP call or not at all.  Default 1 = every launch sized to
+ * fill the GPU on its own.  Results do not depend on it: every sample is
+ * handed out exactly once whatever the grid, and the image is bit for bit the one a lone launch computes. */
 int           drt_renderer_set_frames_in_flight(drt_renderer *r, int32_t n);
 /* Execution time of the tracing kernel(s) of the last batch that drt_renderer_wait / a blocking render completed, as
  * the kernel itself measured it (first wave in .. last wave out on the device's constant-rate clock).  Unlike the stream
