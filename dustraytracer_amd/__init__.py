@@ -333,6 +333,7 @@ _sig("drt_renderer_nearest_list", C.c_int, _P, _P, _P, _P, _P, _P, C.c_uint32, _
 _sig("drt_renderer_overlap_boxes", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_renderer_overlap_triangles", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_renderer_plane_sections", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_int32, _P)
+_sig("drt_renderer_intersect_triangles", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P)
 _sig("drt_scene_edge_adjacency", C.c_int, _P, _P, C.c_uint32)
 _sig("drt_renderer_chain_sections", C.c_int, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _P)
 _sig("drt_renderer_shell_labels", C.c_int, _P, _P, _P, _P, _P)
@@ -641,6 +642,8 @@ TriTable = collections.namedtuple("TriTable", "prim count")             # the fi
 OVERLAP_LIST, OVERLAP_ANY = 0, 1                                        # drt.h DRT_OVERLAP_*
 SectionList = collections.namedtuple("SectionList", "splits p q prim code")   # every segment where planes cut the mesh, CSR (Renderer.planeSections)
 SECTION_LIST, SECTION_ANY = 0, 1                                        # drt.h DRT_SECTION_*
+CutList = collections.namedtuple("CutList", "splits p q prim code")     # every segment where query triangles cut the mesh, CSR (Renderer.intersectTriangles)
+SelfCuts = collections.namedtuple("SelfCuts", "pairs p q code")         # the segments where the mesh cuts itself (Renderer.selfIntersectionSegments)
 CHAIN_LINKED, CHAIN_BOUNDARY, CHAIN_NON_MANIFOLD, CHAIN_NOT_LISTED, CHAIN_OTHER_EDGES, CHAIN_MISS = range(6)   # drt.h: a record's exit status
 
 
@@ -1327,6 +1330,21 @@ class Renderer:
         Two neighbours that also cut each other are therefore not reported.  Degenerate triangles are queried like any other.
         positions as a device tensor: a device tensor comes back; else a numpy array."""
         import torch                             # (only here: importing the package does not import torch)
+        verts, as_tensor = self._own_triangles(torch, scene, positions)
+        n, dev = verts.shape[0], verts.device
+        found = self.overlapTriangles(scene, verts)
+        counts = (found.splits[1:] - found.splits[:-1]).to(torch.int64)
+        i = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=dev), counts)
+        j = found.prim.to(torch.int64)
+        later = j > i
+        i, j = i[later], j[later]
+        shared = self._share_a_vertex(torch, verts, i, j)
+        pairs = torch.stack([i[~shared], j[~shared]], dim=1).to(torch.int32)
+        return pairs if as_tensor else pairs.cpu().numpy()
+
+    def _own_triangles(self, torch, scene, positions):
+        """(the scene's own triangles in tree order as contiguous device vertices [n, 3, 3], positions was a tensor): the host scene's
+        m_PrimitivesBuffer, or positions= [n, 3, 3] float32 in load order mapped through triangleOrder()."""
         dev = torch.device("cuda", self._device)
         n = _lib.drt_scene_triangle_count(scene._h)
         as_tensor = torch.is_tensor(positions)
@@ -1344,16 +1362,80 @@ class Renderer:
                                % (positions.dtype, positions.device, positions.numel(), n, dev))
             order = torch.from_numpy(scene.triangleOrder().astype(np.int64)).to(dev)
             verts = positions.reshape(n, 3, 3)[order]
-        found = self.overlapTriangles(scene, verts.contiguous())
+        return verts.contiguous(), as_tensor
+
+    @staticmethod
+    def _share_a_vertex(torch, verts, i, j):
+        """bool per pair (i, j) of triangles of verts [n, 3, 3]: some vertex of one is bit-equal to a vertex of the other."""
+        bits = verts.view(torch.int32)
+        return (bits[i][:, :, None, :] == bits[j][:, None, :, :]).all(dim=-1).any(dim=2).any(dim=1)
+
+    def _cuts(self, scene, packed):
+        """CutList of device tensors for packed device triangles [N, 12]: a count with capacity 0, a cumulative sum on the device, a
+        fill; the total is read back between them to size the result."""
+        import torch
+        dev = packed.device
+        n = packed.shape[0]
+        splits = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        total = 0
+        if n:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            counts = torch.empty(n, dtype=torch.int32, device=dev)
+            no_room = torch.zeros(n + 1, dtype=torch.int32, device=dev)       # capacity 0: every segment is empty
+            _check(_lib.drt_renderer_intersect_triangles(self._h, scene._h, packed.data_ptr(), no_room.data_ptr(), None, 0, counts.data_ptr(), n,
+                                                         stream))
+            splits[1:] = torch.cumsum(counts.to(torch.int64), dim=0)
+            total = int(splits[-1].item())       # the one synchronisation: the result's size
+            if total >= 2 ** 31:
+                raise DrtError(ERR_INVALID, "%d segments in all: fewer than 2^31 expected (split the queries)" % total)
+        splits = splits.to(torch.int32)
+        rec = torch.empty((total, 8), dtype=torch.float32, device=dev)        # drt_isect: p, prim, q, code
+        if total:
+            _check(_lib.drt_renderer_intersect_triangles(self._h, scene._h, packed.data_ptr(), splits.data_ptr(), rec.data_ptr(), total, None, n,
+                                                         stream))
+        words = rec.view(torch.int32)
+        return CutList(splits, rec[:, 0:3], rec[:, 4:7], words[:, 3], words[:, 7])
+
+    def intersectTriangles(self, scene, tris):
+        """Where each query triangle cuts the mesh (drt_renderer_intersect_triangles): one oriented segment per pair (query, mesh
+        triangle) that cut each other.  tris: vertices [N, 3, 3] float32, or a packed [N, 12] (drt_tri); a mesh is a batch of queries,
+        and its records are the curve along which it cuts the scene's surface, in pieces.  CutList(splits [N + 1] int32, p [M, 3],
+        q [M, 3] float32, prim [M], code [M] int32): query i's segments p -> q at [splits[i], splits[i + 1]), in ascending mesh
+        triangle prim, running along cross(query normal, triangle normal).  Each endpoint is one of the pair's four edge cut points,
+        never interpolated along the line: code = cp + 16 * cq, where an endpoint's code is the mesh triangle's edge 0..2 or 4 + the
+        query's edge it lies on, and an endpoint on an edge that two triangles share is the same bits from both.  Touching counts, and
+        a zero-length segment is listed.  Coplanar pairs and zero-area triangles on either side give nothing -- stricter than
+        overlapTriangles -- and so does a query with a NaN or an infinity.  Not chained into curves; alpha cut-outs are ignored.  A
+        count with capacity 0, a cumulative sum on the device, and a fill; the total is read back between them to size the result:
+        that read is this call's one synchronisation with the device.  Device tensors in, device tensors out (enqueued on the
+        current torch stream); numpy in, numpy out."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        packed, from_numpy = _tri_batch(torch, dev, tris)
+        res = self._cuts(scene, packed)
+        if from_numpy:
+            return CutList(*(x.cpu().numpy().copy() for x in res))
+        return res
+
+    def selfIntersectionSegments(self, scene, positions=None):
+        """The segments along which the scene's mesh cuts itself: SelfCuts(pairs int32 [P, 2], p [P, 3], q [P, 3] float32, code
+        int32 [P]).  pairs[k] = (i, j), i < j, triangle indices in tree order, sorted by (i, j); p[k] -> q[k] is the segment of query
+        i against mesh triangle j, as intersectTriangles gives it (code's low digit is an edge of j, or 4 + an edge of i).  The
+        queries and positions= are selfIntersections': the scene's own triangles, and its filter is applied: j <= i is dropped, and
+        so is every pair in which any vertex of one triangle is bit-equal to a vertex of the other.  A pair that only touches in a
+        common plane is in selfIntersections but not here: coplanar pairs and zero-area triangles give no segment.  positions as a
+        device tensor: device tensors come back; else numpy arrays."""
+        import torch                             # (only here: importing the package does not import torch)
+        verts, as_tensor = self._own_triangles(torch, scene, positions)
+        n, dev = verts.shape[0], verts.device
+        found = self.intersectTriangles(scene, verts)
         counts = (found.splits[1:] - found.splits[:-1]).to(torch.int64)
         i = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=dev), counts)
         j = found.prim.to(torch.int64)
-        later = j > i
-        i, j = i[later], j[later]
-        bits = verts.contiguous().view(torch.int32)
-        shared = (bits[i][:, :, None, :] == bits[j][:, None, :, :]).all(dim=-1).any(dim=2).any(dim=1)
-        pairs = torch.stack([i[~shared], j[~shared]], dim=1).to(torch.int32)
-        return pairs if as_tensor else pairs.cpu().numpy()
+        keep = j > i
+        keep[keep.clone()] = ~self._share_a_vertex(torch, verts, i[keep], j[keep])
+        res = SelfCuts(torch.stack([i[keep], j[keep]], dim=1).to(torch.int32), found.p[keep], found.q[keep], found.code[keep])
+        return res if as_tensor else SelfCuts(*(x.cpu().numpy().copy() for x in res))
 
     def _sections(self, scene, planes):
         """SectionList of device tensors for packed device planes [N, 4]: a count with capacity 0, a cumulative sum on the device, a

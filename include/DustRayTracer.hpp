@@ -360,6 +360,15 @@ public:
                        uint32_t *counts, uint32_t n, int32_t mode, void *stream = nullptr) {
         drt::check(drt_renderer_plane_sections(handle, scene.handle, planes, offsets, out, out_capacity, counts, n, mode, stream));
     }
+    // new: where each query triangle cuts the mesh, a drt_tri {v[3][3]} (drt_renderer_intersect_triangles): one drt_isect {p[3], prim,
+    // q[3], code} per cutting pair in ascending triangle index, p -> q along cross(query normal, triangle normal), each endpoint one of
+    // the pair's four edge cut points; code = cp + 16 * cq, an endpoint's code the scene triangle's edge 0..2 or 4 + the query's edge;
+    // the miss record is zeros with prim = -1.  Coplanar pairs and zero-area triangles give nothing.  Segments, counts and the null rules
+    // are PlaneSections' in mode DRT_SECTION_LIST; there is no mode.  Device arrays, tris and out 16-byte aligned, enqueued on `stream`.
+    void IntersectTriangles(const Scene &scene, const drt_tri *tris, const uint32_t *offsets, drt_isect *out, uint32_t out_capacity,
+                            uint32_t *counts, uint32_t n, void *stream = nullptr) {
+        drt::check(drt_renderer_intersect_triangles(handle, scene.handle, tris, offsets, out, out_capacity, counts, n, stream));
+    }
     // new: the records of PlaneSections chained into contours by the mesh's edge adjacency, integers only (drt_renderer_chain_sections):
     // plane i owns segs and slots [splits[i], splits[i + 1]); slots[pos] = {seg, first, length, flags} in canonical order -- a path from
     // its record without a predecessor, a cycle from its smallest record, chains by their first record, miss records last; flags bit 0 =

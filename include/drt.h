@@ -31,7 +31,8 @@ extern "C" {
  * (drt_renderer_nearest), the crossing-count entry points (drt_renderer_crossings / _inside / _signed_distance), the hit-list entry
  * point (drt_renderer_list_hits), the sphere-cast entry point (drt_renderer_sphere_cast), the nearest-list entry point
  * (drt_renderer_nearest_list), the box-overlap entry point (drt_renderer_overlap_boxes), the triangle-overlap entry point
- * (drt_renderer_overlap_triangles) and the plane-section entry point (drt_renderer_plane_sections) are additions to it */
+ * (drt_renderer_overlap_triangles), the plane-section entry point (drt_renderer_plane_sections) and the intersection-segment entry
+ * point (drt_renderer_intersect_triangles) are additions to it */
 #define DRT_ABI_VERSION 2
 
 typedef enum {
@@ -683,6 +684,70 @@ int           drt_renderer_boundary_loops(drt_renderer *r, const drt_scene *scen
 int           drt_renderer_shell_terms(drt_renderer *r, const drt_scene *scene, double *terms, void *hip_stream);
 int           drt_renderer_edge_adjacency(drt_renderer *r, const drt_scene *scene, int32_t *adj, void *hip_stream);
 int           drt_renderer_topology_steps(const drt_renderer *r, uint32_t *out);
+
+/* ---- triangle intersection segments (new; where a query mesh cuts the scene -- one oriented segment per cutting pair) ----
+ * One query = a drt_tri with vertices q0, q1, q2, as for drt_renderer_overlap_triangles.  A mesh is a batch of queries, and the
+ * records of a batch are the curve along which that mesh cuts the scene's surface, in pieces: one segment per pair (query, scene
+ * triangle) that cut each other.
+ * Stored scene triangle (v0, e1, e2), with world vertices w0 = v0, w1 = v0 + e1, w2 = v0 + e2.
+ * All arithmetic is fp32 with one rounding per operation, in the order written.  dot, cross and min3 / max3 are as the box-overlap
+ * block defines them.  Alpha cut-outs are ignored (a geometric query).
+ * Validity, bounds, cull and traversal are drt_renderer_overlap_triangles', word for word: a query is valid iff all nine coordinates
+ * satisfy fabsf(x) <= FLT_MAX, and an invalid query pushes nothing and lists nothing; qmin[j] = min3(q0[j], q1[j], q2[j]),
+ * qmax[j] = max3(q0[j], q1[j], q2[j]), exact; a box (bmin, bmax) passes iff, on all three axes, qmin[j] <= bmax[j] &&
+ * bmin[j] <= qmax[j], closed comparisons; the root is tested against the scene's root box; an interior node pushes each child that
+ * passes, child 2 first; a leaf's triangles are tested in order.  The known remark applies: v0 + e1 can round one ulp outside a node
+ * box built from the real v1, and a triangle whose leaf the cull rejects gives no record.
+ * Signed values.  The scene triangle against the query's plane: a1 = q1 - q0, a2 = q2 - q0, nq = cross(a1, a2); p_k = w_k - q0,
+ * s_k = dot(nq, p_k) for k = 0, 1, 2; vertex k is above iff s_k >= 0, otherwise below; all three in one class: no record.  The query
+ * against the scene triangle's plane: nt = cross(e1, e2); r_k = q_k - v0, u_k = dot(nt, r_k); above iff u_k >= 0; all three in one
+ * class: no record.  p_k and r_k are taken from the world vertex itself, not built as p_0 + e1: the s of a vertex that two scene
+ * triangles share depends on that vertex and the query alone.
+ * A coplanar pair, and a zero-area triangle on either side, are therefore all above and give no record: this is stricter than
+ * drt_renderer_overlap_triangles' predicate, which lists coplanar pairs that touch and is conservative for zero-area triangles.
+ * Line direction: D = cross(nq, nt).  Axis choice: j = 0; if (fabsf(D[1]) > fabsf(D[0])) j = 1; if (fabsf(D[2]) > fabsf(D[j])) j = 2.
+ * If !(fabsf(D[j]) > 0): no record.
+ * Cut points use drt_renderer_plane_sections' cut(a, b): lo is the below vertex of the two and hi the above one,
+ * t = s_lo / (s_lo - s_hi), and the point is lo + (hi - lo) * t per component, on the world vertices.  For the scene triangle, with
+ * apex k (the vertex alone in its class): T1 = cut(k, k+1) lies on edge k and T2 = cut(k, k+2) lies on edge (k+2) % 3, indices mod 3;
+ * edge e runs from vertex e to vertex (e+1) % 3, as drt_scene_edge_adjacency has it.  For the query Q1 and Q2 are built the same
+ * way from q_k and u_k.
+ * Intervals on axis j: (tl, th) = (T1, T2) if T1[j] <= T2[j], else (T2, T1); (ql, qh) likewise from Q1, Q2.
+ * lo = ql if ql[j] > tl[j] else tl; hi = qh if qh[j] < th[j] else th: on a tie the scene's point is kept.  A record exists iff
+ * lo[j] <= hi[j]: touching counts, and a zero-length segment is listed; a NaN fails, and the pair is not listed.
+ * Orientation: if D[j] > 0 then p = lo and q = hi, otherwise p = hi and q = lo.  So the segment runs along cross(nq, nt).
+ * Record: a drt_isect, 32 bytes, 16-byte aligned: p[3], prim, q[3], code.  prim is the scene triangle.  code = cp + 16 * cq, where
+ * an endpoint's code is the scene triangle's edge (0..2) for a point of T, or 4 + the query's edge for a point of Q.  The miss record
+ * is all zeros with prim = -1.
+ * Endpoints are never interpolated along the line: each one is one of the four cut points, so an endpoint on a shared edge is the
+ * same bits from both neighbours wherever their stored vertices agree.
+ * List: ascending triangle index, at most one record per pair.  Segments, capacities, the miss fill, counts[i] as the total, the NULL
+ * rules and the two-pass recipe are drt_renderer_plane_sections' in mode LIST, with tris for planes; there is no mode argument:
+ * offsets holds n + 1 uint32 values; query i owns out[offsets[i] .. offsets[i+1]); cap_i = offsets[i+1] > offsets[i] ?
+ * offsets[i+1] - offsets[i] : 0, then clamped so that offsets[i] + cap_i <= out_capacity; the call writes out[offsets[i] + j] for
+ * j < cap_i and nothing else in out; the first cap_i records of the list are stored and the rest of the cap_i slots hold the miss
+ * record; counts[i] is the total, stored or not; out is NULL iff out_capacity == 0: a pure count; counts may be NULL; both NULL is
+ * DRT_ERR_INVALID; a count with capacity 0, an exclusive scan of the counts into offsets, a fill.  As there, the call returns
+ * DRT_ERR_UNSUPPORTED for a tree whose leaves, child 1 first, do not hold ascending triangle ranges: the list is appended to and
+ * never inserted into.  The checks, the error codes, the stream ordering, the refitted device copy, the 64-level bound and the
+ * untouched framebuffer, accumulation, sample count, counters, kernel info and kernel span are drt_renderer_plane_sections' too.
+ * What the rule is.  In real arithmetic, for non-coplanar triangles of non-zero area, a record exists iff the two closed triangles
+ * meet.  In fp32 the set of pairs with a record can differ from drt_renderer_overlap_triangles' list only for pairs within rounding
+ * of touching.
+ * Scale.  D is a fourth power of coordinate differences.  Scaling a mesh and its queries by a power of two changes no record (p and q
+ * scaled, prim and code the same) for 2^-24 to 2^32, measured in steps of 2^2 on the mesh and the triangle queries the working-range
+ * block below was measured on (drt_renderer_overlap_triangles there: 2^-30 to 2^30; only comparisons leave that test, while here s and
+ * u, third powers, are divided); beyond, s, u or D overflow or lose bits as subnormals and records vanish or move
+ * (tests/test_intersect_ref.py asserts the figure).
+ * What this is not: the segments are not chained into curves -- the records of a query are separate segments in triangle order, and
+ * joining them across queries and triangles is the caller's; no clipped polygons and no boolean; coplanar overlaps give nothing; there
+ * is no pair exclusion at this level -- for a query taken from the scene itself the s of a shared vertex is a rounding error of
+ * either sign, so a neighbour can give a record along the shared edge, and a caller filters such pairs; and it is not built for queries that cut tens of thousands of triangles each -- it
+ * works there, one lane per query.
+ * tris and out are 16-byte aligned; offsets and counts 4-byte aligned. */
+typedef struct drt_isect { float p[3]; int32_t prim; float q[3]; int32_t code; } drt_isect;             /* 32 B */
+int           drt_renderer_intersect_triangles(drt_renderer *r, const drt_scene *scene, const drt_tri *tris, const uint32_t *offsets,
+                                               drt_isect *out, uint32_t out_capacity, uint32_t *counts, uint32_t n, void *hip_stream);
 
 /* ---- sphere casts (new; the first contact of a moving sphere with the mesh) ----
  * One cast = a drt_ray (org o, tmin, dir d, tmax, read as drt_renderer_trace_rays reads it: dir as given, t in units of |d|,
