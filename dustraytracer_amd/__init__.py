@@ -336,6 +336,8 @@ _sig("drt_renderer_plane_sections", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P,
 _sig("drt_renderer_intersect_triangles", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P)
 _sig("drt_scene_edge_adjacency", C.c_int, _P, _P, C.c_uint32)
 _sig("drt_renderer_chain_sections", C.c_int, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _P)
+_sig("drt_tri_edge_adjacency", C.c_int, _P, C.c_uint32, _P, C.c_uint32)
+_sig("drt_renderer_chain_intersections", C.c_int, _P, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _P)
 _sig("drt_renderer_shell_labels", C.c_int, _P, _P, _P, _P, _P)
 _sig("drt_renderer_boundary_loops", C.c_int, _P, _P, _P, C.c_uint32, _P, _P)
 _sig("drt_renderer_shell_terms", C.c_int, _P, _P, _P, _P)
@@ -696,6 +698,56 @@ class ContourList(collections.namedtuple("ContourList", "splits chain_splits clo
         areas = 0.5 * _segment_sums(torch, term, chain_splits)
         areas = torch.where(dev_of(self.closed).to(torch.bool), areas, torch.full((n_chains,), float("nan"), dtype=torch.float64, device=dev))
         return areas.cpu().numpy() if as_numpy else areas
+
+
+class CurveList(collections.namedtuple("CurveList", "chain_splits closed p q query prim code end")):
+    """The curves along which a query mesh cuts the scene (Renderer.chainIntersections / intersectionCurves): chain c is the records
+    chain_splits[c]:chain_splits[c + 1] of p, q, query, prim, code and end, in chained order over the whole batch -- a curve crosses
+    queries: its vertices are the p of its records, plus the last q when it is open.  closed [C] bool; query [M] is the query
+    triangle a record belongs to, prim its scene triangle; end [M] is each record's exit status (CHAIN_*; 0 = linked to the next
+    record of its chain, or, for the last record of a closed chain, to the first)."""
+
+    def lengths(self):
+        """float64 [C]: the sum of |q - p| over each chain, in float64.  Device tensors in the list: a device tensor comes back
+        (summed as Renderer.sectionAreas sums); else a numpy array."""
+        if isinstance(self.p, np.ndarray):
+            d = self.q.astype(np.float64) - self.p.astype(np.float64)
+            at = self.chain_splits.astype(np.int64)[:-1]                     # (no chain is empty)
+            return np.add.reduceat(np.sqrt((d * d).sum(axis=1)), at) if len(at) else np.zeros(0, np.float64)
+        import torch
+        d = self.q.to(torch.float64) - self.p.to(torch.float64)
+        return _segment_sums(torch, torch.sqrt((d * d).sum(dim=1)), self.chain_splits.to(torch.int64))
+
+
+def triEdgeAdjacency(tris):
+    """int32 [N, 3]: the edge adjacency of a query mesh (drt_tri_edge_adjacency), Scene.edgeAdjacency's rule on the vertices of
+    tris -- [N, 3, 3] float32 or a packed [N, 12] (drt_tri) -- in the caller's order: the twin half-edge 3 * i' + e' of edge e (vertex e
+    to vertex (e + 1) % 3) of triangle i by bit-equal positions, -1 on a boundary edge, -2 where the edge is non-manifold, flipped or
+    of zero length.  What Renderer.chainIntersections takes as query_adj.  The table is made on the host: numpy in, numpy out; a
+    device tensor is copied to the host for it, and a device tensor comes back."""
+    as_numpy = isinstance(tris, np.ndarray)
+    if as_numpy:
+        host = tris
+    else:
+        import torch                             # (only here: importing the package does not import torch)
+        if not torch.is_tensor(tris):
+            raise DrtError(ERR_INVALID, "tris: a numpy array or a torch tensor expected")
+        host = tris.detach().cpu().numpy()
+    if host.dtype != np.float32:
+        raise DrtError(ERR_INVALID, "tris: dtype %s, float32 expected" % host.dtype)
+    if host.ndim == 3 and host.shape[1:] == (3, 3):
+        packed = np.zeros((host.shape[0], 12), np.float32)
+        packed[:, 0:9] = host.reshape(-1, 9)
+    elif host.ndim == 2 and host.shape[1] == 12:
+        packed = np.ascontiguousarray(host)
+    else:
+        raise DrtError(ERR_INVALID, "tris: shape %s, [N, 3, 3] or a packed [N, 12] expected" % (tuple(host.shape),))
+    n = packed.shape[0]
+    if n >= 2 ** 31:
+        raise DrtError(ERR_INVALID, "%d triangles: fewer than 2^31 expected" % n)
+    out = np.zeros((n, 3), np.int32)
+    _check(_lib.drt_tri_edge_adjacency(packed.ctypes.data if n else None, n, out.ctypes.data if n else None, 3 * n))
+    return out if as_numpy else torch.from_numpy(out).to(tris.device)
 # Mesh topology (drt.h "mesh topology"), everything in tree order (Scene.triangleOrder() maps it to load order)
 Shells = collections.namedtuple("Shells", "label index count triangles open_edges bad_edges watertight")   # Renderer.shells
 LoopList = collections.namedtuple("LoopList", "splits closed half_edge prim edge shell end")              # Renderer.boundaryLoops
@@ -1621,6 +1673,113 @@ class Renderer:
         if from_numpy:
             res = ContourList(*(x.cpu().numpy().copy() for x in res))
         res.normals = planes[:, 0:3].cpu().numpy().copy() if from_numpy else planes[:, 0:3].clone()
+        return res
+
+    def _query_adjacency(self, torch, dev, n, tris, query_adj):
+        """int32 [n, 3] on `dev`: query_adj as given (numpy or a tensor on `dev`), or the table of tris (triEdgeAdjacency)."""
+        if query_adj is None:
+            if tris is None:
+                raise DrtError(ERR_INVALID, "one of tris and query_adj expected: the curve crosses queries through the query mesh's edge adjacency")
+            query_adj = triEdgeAdjacency(tris)
+        if isinstance(query_adj, np.ndarray):
+            if query_adj.dtype != np.int32:
+                raise DrtError(ERR_INVALID, "query_adj: dtype %s, int32 expected" % query_adj.dtype)
+            query_adj = torch.from_numpy(np.ascontiguousarray(query_adj)).to(dev)
+        elif not torch.is_tensor(query_adj) or query_adj.dtype != torch.int32 or query_adj.device != dev:
+            raise DrtError(ERR_INVALID, "query_adj: a numpy array or a tensor on %s, int32, expected" % (dev,))
+        if query_adj.numel() != 3 * n:
+            raise DrtError(ERR_INVALID, "query_adj: %d values for %d queries, 3 per query expected" % (query_adj.numel(), n))
+        return query_adj.contiguous()
+
+    def _chain_cuts(self, cuts, scene, query_adj):
+        """(CurveList of device tensors, slots [M, 4] int32, counts [3] int32) for a CutList of device tensors and the query mesh's
+        table on the device: the records packed again as drt_isect, drt_renderer_chain_intersections, and the lists read off the
+        slots."""
+        import torch
+        dev = torch.device("cuda", self._device)
+        splits = cuts.splits.to(torch.int32).contiguous()
+        n, total = splits.shape[0] - 1, cuts.prim.shape[0]
+        if n < 0 or cuts.p.shape != (total, 3) or cuts.q.shape != (total, 3) or cuts.code.shape != (total,):
+            raise DrtError(ERR_INVALID, "a CutList expected: splits [N + 1], p and q [M, 3], prim and code [M]")
+        if total >= 2 ** 31:
+            raise DrtError(ERR_INVALID, "%d segments in all: fewer than 2^31 expected (split the queries)" % total)
+        rec = torch.empty((total, 8), dtype=torch.float32, device=dev)         # drt_isect: p, prim, q, code
+        words = rec.view(torch.int32)
+        rec[:, 0:3], rec[:, 4:7] = cuts.p, cuts.q
+        words[:, 3], words[:, 7] = cuts.prim, cuts.code
+        slots = torch.empty((total, 4), dtype=torch.int32, device=dev)
+        counts = torch.zeros(3, dtype=torch.int32, device=dev)
+        if n > 0 and total:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(_lib.drt_renderer_chain_intersections(self._h, scene._h, rec.data_ptr(), splits.data_ptr(), query_adj.data_ptr(), slots.data_ptr(),
+                                                         counts.data_ptr(), n, total, stream))
+        else:
+            slots[:, 0] = slots[:, 1] = torch.arange(total, dtype=torch.int32, device=dev)      # (no query: nothing is live)
+            slots[:, 2], slots[:, 3] = 1, CHAIN_MISS << 1
+        # what the slots say: a chain starts where first == position; records that are not live are dropped
+        status = slots[:, 3] >> 1
+        kept = status != CHAIN_MISS
+        starts = (slots[:, 1] == torch.arange(total, dtype=torch.int32, device=dev)) & kept
+        seg = slots[:, 0][kept].to(torch.int64)
+        kept_before = torch.cumsum(kept.to(torch.int64), dim=0) - kept.to(torch.int64)
+        chain_splits = torch.cat([kept_before[starts], torch.full((1,), seg.shape[0], dtype=torch.int64, device=dev)]).to(torch.int32)
+        # the owning query: a CutList's ranges ascend and tile the list, so it is the number of range ends at or before the record
+        query = torch.searchsorted(splits[1:].to(torch.int64).contiguous(), torch.arange(total, dtype=torch.int64, device=dev), right=True).to(torch.int32)
+        chained = rec[seg]                                                     # the records in chained order
+        chained_words = chained.view(torch.int32)
+        out = CurveList(chain_splits, (slots[:, 3][starts] & 1).to(torch.bool), chained[:, 0:3], chained[:, 4:7], query[seg],
+                        chained_words[:, 3], chained_words[:, 7], status[kept])
+        return out, slots, counts
+
+    def chainIntersections(self, scene, cuts, tris=None, query_adj=None):
+        """The segments of a CutList (intersectTriangles) chained into curves: closed loops and open polylines over the whole batch
+        (drt_renderer_chain_intersections).  A segment that leaves through an edge of the scene triangle continues in the triangle
+        across that edge (Scene.edgeAdjacency) with the same query; one that leaves through an edge of the query continues in the
+        same scene triangle with the query across that edge, looked up in the query mesh's own table: give the mesh the list was
+        made with as tris, or its triEdgeAdjacency(tris) as query_adj (a table stays valid while the mesh moves rigidly or
+        deforms without tearing).  Integers only, no welding, no tolerance, the same bytes on every run.  A path starts at its
+        record without a predecessor, a cycle at its record of smallest index; the chains are ordered by their first record.
+        CurveList(chain_splits [C + 1], closed [C], p [M, 3], q [M, 3], query [M], prim [M], code [M], end [M]) in chained order; end
+        is each record's exit status as chainSections has it, here for either mesh (1 = a boundary edge, 2 = a non-manifold or
+        flipped edge, 3 = the neighbour is not in the list, 4 = the neighbour is cut through other edges).  A curve is closed
+        exactly where neighbouring triangles agree; one that runs through vertices or along edges falls into open chains.
+        Self-intersection curves are not chained.  Device tensors in, device tensors out (enqueued on the current torch stream);
+        numpy in, numpy out."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        if not isinstance(cuts, tuple) or len(cuts) != 5:
+            raise DrtError(ERR_INVALID, "a CutList expected")
+        from_numpy = isinstance(cuts[0], np.ndarray)
+        want = (("splits", np.int32, torch.int32), ("p", np.float32, torch.float32), ("q", np.float32, torch.float32),
+                ("prim", np.int32, torch.int32), ("code", np.int32, torch.int32))
+        parts = []
+        for a, (what, np_type, torch_type) in zip(cuts, want):
+            if isinstance(a, np.ndarray) != from_numpy or not (from_numpy or torch.is_tensor(a)):
+                raise DrtError(ERR_INVALID, "%s: numpy arrays or device tensors expected, not a mix" % what)
+            if from_numpy:
+                if a.dtype != np_type:
+                    raise DrtError(ERR_INVALID, "%s: dtype %s, %s expected" % (what, a.dtype, np.dtype(np_type)))
+                a = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+            elif a.dtype != torch_type or a.device != dev:
+                raise DrtError(ERR_INVALID, "%s: %s on %s, %s on %s expected" % (what, a.dtype, a.device, torch_type, dev))
+            parts.append(a)
+        table = self._query_adjacency(torch, dev, parts[0].shape[0] - 1, tris, query_adj)
+        res = self._chain_cuts(CutList(*parts), scene, table)[0]
+        if from_numpy:
+            return CurveList(*(x.cpu().numpy().copy() for x in res))
+        return res
+
+    def intersectionCurves(self, scene, tris, query_adj=None):
+        """intersectTriangles followed by chainIntersections: the CurveList along which the mesh tris ([N, 3, 3] float32 or a packed
+        [N, 12]) cuts the scene.  query_adj: the mesh's triEdgeAdjacency, to reuse the table for a moving tool; made from tris when
+        not given.  The one synchronisation with the device is intersectTriangles' read of the total."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        packed, from_numpy = _tri_batch(torch, dev, tris)
+        table = self._query_adjacency(torch, dev, packed.shape[0], tris, query_adj)
+        res = self._chain_cuts(self._cuts(scene, packed), scene, table)[0]
+        if from_numpy:
+            return CurveList(*(x.cpu().numpy().copy() for x in res))
         return res
 
     def _shells(self, scene):

@@ -27,6 +27,9 @@
 //             difference to chains[] (two integer atomics per word: the order does not matter).
 //   scatter   slots[position of the first record + rank] = {record, first, length, flags}
 //
+// Everything behind the link is also what the intersection curves run (kernel_curve.hip, through contour.hpp launch_chain_phases), over
+// one range [0, total) instead of a range per plane: the three kernels that look at ranges are templates on that, kWhole.
+//
 // Bounds on any input: a record's prim and code are checked before they index the adjacency; pred, succ and the states hold record
 // indices below total; a position is written only inside its plane's range (else the record is written as a chain of one at its own
 // index), which input with overlapping ranges needs.
@@ -40,20 +43,18 @@ namespace {
 
 #define CT_DEV static __device__ __forceinline__
 
-struct Range { uint32_t lo, hi; };
+using Range = ContourRange;
 
-// drt.h "inputs": cap_i as drt_renderer_plane_sections clamps it -- a decreasing pair is empty, nothing beyond total
-CT_DEV Range plane_range(const uint32_t *splits, uint32_t i, uint32_t total) {
-    const uint32_t lo = splits[i], end = splits[i + 1];
-    uint32_t cap = end > lo ? end - lo : 0u;
-    if (lo >= total) cap = 0u;
-    else cap = min(cap, total - lo);
-    Range r;
-    r.lo = lo; r.hi = lo + cap;
-    return r;
+// (contour.hpp: kernel_curve.hip reads ranges and records the same way)
+CT_DEV Range plane_range(const uint32_t *splits, uint32_t i, uint32_t total) { return contour_range(splits, i, total); }
+CT_DEV uint32_t seg_word(const void *segs, uint32_t j, int word) { return contour_seg_word(segs, j, word); }
+
+// The range a record's position must lie in: its plane's, or in a kWhole launch (contour.hpp launch_chain_phases) the whole list
+template <bool kWhole>
+CT_DEV Range record_range(const ContourArgs &a, uint32_t owner) {
+    if (kWhole) { Range r; r.lo = 0u; r.hi = a.total; return r; }
+    return plane_range(a.splits, owner, a.total);
 }
-
-CT_DEV uint32_t seg_word(const void *segs, uint32_t j, int word) { return reinterpret_cast<const uint32_t *>(segs)[(size_t)j * 8 + word]; }
 
 // the edges a record is entered and left through: valid iff code < 8 and its apex < 3
 CT_DEV bool code_edges(uint32_t code, uint32_t &in, uint32_t &out) {
@@ -68,19 +69,7 @@ CT_DEV bool code_edges(uint32_t code, uint32_t &in, uint32_t &out) {
 __global__ __launch_bounds__(kContourThreads) void contour_keys_kernel(const ContourArgs a) {
     const uint32_t j = blockIdx.x * kContourThreads + threadIdx.x;
     if (j >= a.total) return;
-    // the last plane whose range starts at or before j
-    uint32_t lo = 0, hi = a.n;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (a.splits[mid] <= j) lo = mid + 1;
-        else hi = mid;
-    }
-    uint32_t owner = kContourNone;
-    if (lo > 0) {
-        const Range r = plane_range(a.splits, lo - 1, a.total);
-        if (j >= r.lo && j < r.hi) owner = lo - 1;
-    }
-    a.owner[j] = owner;
+    a.owner[j] = contour_owner(a.splits, a.n, a.total, j);      // the last plane whose range starts at or before j
     a.key[j] = seg_word(a.segs, j, 3);
     a.pred[j] = kContourNone;
 }
@@ -179,10 +168,11 @@ __global__ __launch_bounds__(kContourThreads) void contour_tail_kernel(const Con
 struct Sums { uint32_t length, chains, closed; };
 
 // what record j adds to the scans
+template <bool kWhole>
 CT_DEV Sums scan_term(const ContourArgs &a, const uint4 *state, uint32_t j) {
     Sums t = { 0u, 0u, 0u };
     if (j >= a.total) return t;
-    if (a.owner[j] == kContourNone) { t.length = 1u; return t; }
+    if (!kWhole && a.owner[j] == kContourNone) { t.length = 1u; return t; }
     const Ranked r = ranked(state[j]);
     if (r.start != j) return t;
     t.length = a.key[j];
@@ -220,13 +210,14 @@ CT_DEV Sums block_exclusive(Sums mine, Sums *s_wave, Sums *total) {
     return r;
 }
 
+template <bool kWhole>
 __global__ __launch_bounds__(kContourThreads) void contour_block_sums_kernel(const ContourArgs a, const uint4 *state) {
     __shared__ Sums s_wave[kContourThreads / 64];
     const uint32_t first = blockIdx.x * kContourScanBlock + threadIdx.x * kContourScanItems;
     Sums mine = { 0u, 0u, 0u };
 #pragma unroll
     for (int k = 0; k < kContourScanItems; k++) {
-        const Sums t = scan_term(a, state, first + k);
+        const Sums t = scan_term<kWhole>(a, state, first + k);
         mine.length += t.length; mine.chains += t.chains; mine.closed += t.closed;
     }
     Sums total;
@@ -257,13 +248,14 @@ __global__ __launch_bounds__(kContourThreads) void contour_scan_sums_kernel(cons
     }
 }
 
+template <bool kWhole>
 __global__ __launch_bounds__(kContourThreads) void contour_offsets_kernel(const ContourArgs a, const uint4 *state) {
     __shared__ Sums s_wave[kContourThreads / 64];
     const uint32_t first = blockIdx.x * kContourScanBlock + threadIdx.x * kContourScanItems;
     Sums v[kContourScanItems], mine = { 0u, 0u, 0u };
 #pragma unroll
     for (int k = 0; k < kContourScanItems; k++) {
-        v[k] = scan_term(a, state, first + k);
+        v[k] = scan_term<kWhole>(a, state, first + k);
         mine.length += v[k].length; mine.chains += v[k].chains; mine.closed += v[k].closed;
     }
     Sums total;
@@ -276,9 +268,9 @@ __global__ __launch_bounds__(kContourThreads) void contour_offsets_kernel(const 
         const uint32_t j = first + k;
         if (j < a.total) {
             a.pred[j] = run.length;                      // (the predecessors are spent: the positions)
-            const uint32_t owner = a.owner[j];
+            const uint32_t owner = kWhole ? 0u : a.owner[j];
             if (a.chains && owner != kContourNone) {
-                const Range r = plane_range(a.splits, owner, a.total);
+                const Range r = record_range<kWhole>(a, owner);
                 if (j == r.lo) {
                     atomicSub(&a.chains[2u * owner], run.chains);
                     atomicSub(&a.chains[2u * owner + 1], run.closed);
@@ -293,17 +285,18 @@ __global__ __launch_bounds__(kContourThreads) void contour_offsets_kernel(const 
     }
 }
 
+template <bool kWhole>
 __global__ __launch_bounds__(kContourThreads) void contour_scatter_kernel(const ContourArgs a, const uint4 *state) {
     const uint32_t j = blockIdx.x * kContourThreads + threadIdx.x;
     if (j >= a.total) return;
-    const uint32_t owner = a.owner[j];
+    const uint32_t owner = kWhole ? 0u : a.owner[j];
     if (owner == kContourNone) return;
     const Ranked r = ranked(state[j]);
     const uint32_t link = a.succ[j];
     const uint32_t status = (link & kContourFlag) ? (link & 7u) : 0u;
     const uint32_t first = a.pred[r.start], length = a.key[r.start];
     const uint32_t pos = first + r.rank;
-    const Range range = plane_range(a.splits, owner, a.total);
+    const Range range = record_range<kWhole>(a, owner);
     uint4 *slots = reinterpret_cast<uint4 *>(a.slots);
     if (first >= range.lo && pos >= first && pos < range.hi) slots[pos] = make_uint4(j, first, length, (r.closed ? 1u : 0u) | (status << 1));
     else slots[j] = make_uint4(j, j, 1u, status << 1);
@@ -311,11 +304,31 @@ __global__ __launch_bounds__(kContourThreads) void contour_scatter_kernel(const 
 
 }  // namespace
 
-hipError_t launch_contour(const ContourArgs &a, hipStream_t stream) {
+template <bool kWhole>
+static void launch_phases(const ContourArgs &a, hipStream_t stream) {
     const int rounds = contour_rounds(a.total);
     const dim3 block(kContourThreads);
     const dim3 lanes((a.total + kContourThreads - 1) / kContourThreads);
     const uint32_t n_blocks = contour_scan_blocks(a.total);
+    hipLaunchKernelGGL(contour_init_kernel, lanes, block, 0, stream, a);
+    for (int k = 0; k < rounds; k++) hipLaunchKernelGGL(contour_jump_kernel, lanes, block, 0, stream, a, k);
+    const uint4 *state = a.state[rounds & 1];
+    hipLaunchKernelGGL(contour_tail_kernel, lanes, block, 0, stream, a, state);
+    hipLaunchKernelGGL(contour_block_sums_kernel<kWhole>, dim3(n_blocks), block, 0, stream, a, state);
+    hipLaunchKernelGGL(contour_scan_sums_kernel, dim3(1), block, 0, stream, a, n_blocks);
+    hipLaunchKernelGGL(contour_offsets_kernel<kWhole>, dim3(n_blocks), block, 0, stream, a, state);
+    hipLaunchKernelGGL(contour_scatter_kernel<kWhole>, lanes, block, 0, stream, a, state);
+}
+
+hipError_t launch_chain_phases(const ContourArgs &a, bool whole, hipStream_t stream) {
+    if (whole) launch_phases<true>(a, stream);
+    else launch_phases<false>(a, stream);
+    return hipGetLastError();
+}
+
+hipError_t launch_contour(const ContourArgs &a, hipStream_t stream) {
+    const dim3 block(kContourThreads);
+    const dim3 lanes((a.total + kContourThreads - 1) / kContourThreads);
     hipError_t e = hipMemsetAsync(a.moved, 0, (kContourMaxRounds + 1) * sizeof(uint32_t), stream);
     if (e != hipSuccess) return e;
     if (a.chains) {
@@ -324,15 +337,7 @@ hipError_t launch_contour(const ContourArgs &a, hipStream_t stream) {
     }
     hipLaunchKernelGGL(contour_keys_kernel, lanes, block, 0, stream, a);
     hipLaunchKernelGGL(contour_link_kernel, lanes, block, 0, stream, a);
-    hipLaunchKernelGGL(contour_init_kernel, lanes, block, 0, stream, a);
-    for (int k = 0; k < rounds; k++) hipLaunchKernelGGL(contour_jump_kernel, lanes, block, 0, stream, a, k);
-    const uint4 *state = a.state[rounds & 1];
-    hipLaunchKernelGGL(contour_tail_kernel, lanes, block, 0, stream, a, state);
-    hipLaunchKernelGGL(contour_block_sums_kernel, dim3(n_blocks), block, 0, stream, a, state);
-    hipLaunchKernelGGL(contour_scan_sums_kernel, dim3(1), block, 0, stream, a, n_blocks);
-    hipLaunchKernelGGL(contour_offsets_kernel, dim3(n_blocks), block, 0, stream, a, state);
-    hipLaunchKernelGGL(contour_scatter_kernel, lanes, block, 0, stream, a, state);
-    return hipGetLastError();
+    return launch_chain_phases(a, false, stream);
 }
 
 }  // namespace drt

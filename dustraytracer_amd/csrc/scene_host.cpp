@@ -8,6 +8,7 @@
 // host code built without FMA.
 #include "scene_host.hpp"
 #include "bvh_build_device.hpp"
+#include "edge_adjacency.hpp"
 
 #include <algorithm>
 #include <atomic>
@@ -726,49 +727,11 @@ int32_t HostScene::bvh_depth() const {
 // ---------------------------------------------------------------------------------------------
 // Edge adjacency (drt_scene_edge_adjacency): the twin of every half-edge, by bit-equal positions
 // ---------------------------------------------------------------------------------------------
-// Half-edge h = 3 t + e runs from vertex e to vertex (e + 1) % 3 of triangle t.  The half-edges are sorted by their unordered pair
-// of endpoint positions (the three words of each, compared as integers); a group of two that run in opposite directions is a pair
-// of twins, a group of one a boundary edge (-1), everything else -2 -- three or more, two the same way, both ends the same position.
+// The rule and the routine are edge_adjacency.hpp's (drt_tri_edge_adjacency runs the same one over a query mesh): here it reads the
+// positions of the triangles in tree order.
 std::vector<int32_t> HostScene::edge_adjacency() const {
     if (nodes.empty()) throw std::invalid_argument("scene has no BVH: the adjacency is in tree order, build one first");
-    struct HalfEdge { uint32_t lo[3], hi[3]; int32_t h; bool forward; };      // forward: it runs from lo to hi
-    const size_t n = triangles.size();
-    std::vector<int32_t> adj(3 * n, -2);
-    std::vector<HalfEdge> edges;
-    edges.reserve(3 * n);
-    for (size_t t = 0; t < n; t++)
-        for (int e = 0; e < 3; e++) {
-            uint32_t a[3], b[3];
-            std::memcpy(a, triangles[t].vertex[e].position, 12);
-            std::memcpy(b, triangles[t].vertex[(e + 1) % 3].position, 12);
-            const int c = std::memcmp(a, b, 12) == 0 ? 0 : (std::lexicographical_compare(a, a + 3, b, b + 3) ? -1 : 1);
-            if (c == 0) continue;                                          // both ends the same position: -2
-            HalfEdge he;
-            std::memcpy(he.lo, c < 0 ? a : b, 12);
-            std::memcpy(he.hi, c < 0 ? b : a, 12);
-            he.h = (int32_t)(3 * t + e);
-            he.forward = c < 0;
-            edges.push_back(he);
-        }
-    auto key_less = [](const HalfEdge &x, const HalfEdge &y) {
-        for (int k = 0; k < 3; k++)
-            if (x.lo[k] != y.lo[k]) return x.lo[k] < y.lo[k];
-        for (int k = 0; k < 3; k++)
-            if (x.hi[k] != y.hi[k]) return x.hi[k] < y.hi[k];
-        return false;
-    };
-    std::sort(edges.begin(), edges.end(), key_less);
-    for (size_t i = 0; i < edges.size();) {
-        size_t j = i + 1;
-        while (j < edges.size() && !key_less(edges[i], edges[j])) j++;
-        if (j - i == 1) adj[(size_t)edges[i].h] = -1;
-        else if (j - i == 2 && edges[i].forward != edges[i + 1].forward) {
-            adj[(size_t)edges[i].h] = edges[i + 1].h;
-            adj[(size_t)edges[i + 1].h] = edges[i].h;
-        }
-        i = j;
-    }
-    return adj;
+    return edge_adjacency_of(triangles.empty() ? nullptr : triangles[0].vertex[0].position, sizeof(drt_triangle), sizeof(drt_vertex), triangles.size());
 }
 
 // ---------------------------------------------------------------------------------------------

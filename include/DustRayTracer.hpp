@@ -175,6 +175,14 @@ struct Scene {
     drt_scene *handle;
 };
 
+// new: the edge adjacency of a query mesh, Scene::EdgeAdjacency's rule on the nine coordinates of each drt_tri in the caller's order
+// (drt_tri_edge_adjacency): 3 values per triangle, host memory; what Renderer::ChainIntersections takes as query_adj
+inline std::vector<int32_t> TriEdgeAdjacency(const drt_tri *tris, uint32_t n) {
+    std::vector<int32_t> v(3 * (size_t)n);
+    drt::check(drt_tri_edge_adjacency(tris, n, v.data(), (uint32_t)v.size()));
+    return v;
+}
+
 // Core/BVH/BVHBuilder.cuh:12-23
 class BVHBuilder {
 public:
@@ -377,6 +385,16 @@ public:
     void ChainSections(const Scene &scene, const drt_section *segs, const uint32_t *splits, drt_chain_slot *slots, uint32_t *chains, uint32_t n,
                        uint32_t total, void *stream = nullptr) {
         drt::check(drt_renderer_chain_sections(handle, scene.handle, segs, splits, slots, chains, n, total, stream));
+    }
+    // new: the records of IntersectTriangles chained into curves across scene triangles and across queries, integers only
+    // (drt_renderer_chain_intersections): query i owns segs [splits[i], splits[i + 1]); query_adj = TriEdgeAdjacency of the query mesh,
+    // copied to the device (3 n values).  A record that leaves through a scene edge continues in the twin triangle with the same query,
+    // one that leaves through a query edge in the same triangle with the twin query.  slots[pos] = {seg, first, length, flags} in one
+    // canonical order over the whole list, as ChainSections; counts (may be null) = {chains, closed ones, records that are not live}.
+    // Device arrays, segs and slots 16-byte aligned, enqueued on `stream`.
+    void ChainIntersections(const Scene &scene, const drt_isect *segs, const uint32_t *splits, const int32_t *query_adj, drt_chain_slot *slots,
+                            uint32_t *counts, uint32_t n, uint32_t total, void *stream = nullptr) {
+        drt::check(drt_renderer_chain_intersections(handle, scene.handle, segs, splits, query_adj, slots, counts, n, total, stream));
     }
     // new: mesh topology (drt.h "mesh topology"), all in tree order and on device arrays, enqueued on `stream`.  ShellLabels: labels[t] =
     // the smallest triangle index of t's shell (triangles joined by twin half-edges), counts (may be null) = {shells, open half-edges,

@@ -31,8 +31,9 @@ extern "C" {
  * (drt_renderer_nearest), the crossing-count entry points (drt_renderer_crossings / _inside / _signed_distance), the hit-list entry
  * point (drt_renderer_list_hits), the sphere-cast entry point (drt_renderer_sphere_cast), the nearest-list entry point
  * (drt_renderer_nearest_list), the box-overlap entry point (drt_renderer_overlap_boxes), the triangle-overlap entry point
- * (drt_renderer_overlap_triangles), the plane-section entry point (drt_renderer_plane_sections) and the intersection-segment entry
- * point (drt_renderer_intersect_triangles) are additions to it */
+ * (drt_renderer_overlap_triangles), the plane-section entry point (drt_renderer_plane_sections), the intersection-segment entry
+ * point (drt_renderer_intersect_triangles) and the intersection-curve entry points (drt_tri_edge_adjacency,
+ * drt_renderer_chain_intersections) are additions to it */
 #define DRT_ABI_VERSION 2
 
 typedef enum {
@@ -856,6 +857,67 @@ int           drt_renderer_sphere_cast(drt_renderer *r, const drt_scene *scene, 
  * (drt_renderer_overlap_triangles' predicate is conservative for zero-area triangles in a stronger sense than "a near miss in the
  * triangle's own plane": a segment or point query passes all seventeen axes against a POINT of the scene wherever it is, and only the
  * node cull keeps such a pair out of the list.) */
+
+/* ---- intersection curves (new; the records of drt_renderer_intersect_triangles chained into closed loops and open polylines) ----
+ * The records of a batch of queries are the curve along which a query mesh cuts the scene, in pieces.  code = cp + 16 * cq names
+ * the edge each endpoint lies on -- edges 0..2 of the scene triangle, 4..6 of the query -- endpoints are cut points, never
+ * interpolated, and the segment runs from p to q along cross(nq, nt), which flows one way along the curve on consistently oriented
+ * meshes.  So the successor of a segment is an integer question to two edge adjacency tables: leaving through a scene edge, the
+ * curve continues in the twin scene triangle with the same query; leaving through a query edge, it continues in the same scene
+ * triangle with the twin query.  No coordinate is compared, no tolerance is chosen, nothing is welded, and the result is the same
+ * bytes on every run.
+ * Edge adjacency of a query mesh, drt_tri_edge_adjacency: tris and out are HOST pointers; out receives 3 * n values and capacity
+ * is the room in values.  The rule is drt_scene_edge_adjacency's, word for word, on the nine coordinates of each drt_tri (the pad
+ * is not read): half-edge 3 * i + e runs from vertex e to vertex (e + 1) % 3 of query i; two positions are the same iff their
+ * three words are bit-equal; twins, -1 and -2 as there.  There is no BVH and no order other than the caller's.  DRT_ERR_INVALID:
+ * capacity below 3 * n, or a NULL pointer with n > 0.
+ * drt_renderer_chain_intersections: segs, splits (n + 1 values), query_adj (3 * n values), slots (total entries) and counts (3
+ * words, may be NULL) are device pointers on the renderer's device; the call is enqueued on hip_stream (NULL = the renderer's)
+ * and orders with the other queries as they do.  The scene's table is the renderer's device copy of drt_scene_edge_adjacency, the
+ * one drt_renderer_chain_sections makes and drops; after a device-only drt_renderer_refit it is still the host scene's.
+ * Ranges: query i's range is segs[splits[i] .. splits[i+1]), clamped exactly as drt_renderer_chain_sections clamps it: a
+ * decreasing pair is an empty range, and nothing beyond total is read or written.  A range is what a fill wrote: records in
+ * ascending prim, followed by any miss records.  The owner of record j is found by binary search as if splits ascended: lo = 0,
+ * hi = n; while lo < hi: mid = lo + (hi - lo) / 2, and lo = mid + 1 if splits[mid] <= j, else hi = mid; j is owned by query
+ * lo - 1 iff lo > 0 and j lies in that query's range, and by no query otherwise.  On ascending splits that is the one range that
+ * holds j.
+ * Live records: a record is live iff it has an owner, 0 <= prim < n_triangles (a miss record has prim -1), and both cp = code & 15
+ * and cq = code >> 4 are in {0, 1, 2, 4, 5, 6}.  A record that is not live has no successor, takes no predecessor, and gets exit
+ * status 5.
+ * Link: for a live record j of query i, let T = prim_j.  If cq < 4: a = adj[3 * T + cq], the target range is query i's, the
+ * target prim is a / 3 and the required entry code is a % 3.  If cq >= 4: a = query_adj[3 * i + cq - 4], the target range is
+ * query a / 3, the target prim is T and the required entry code is 4 + a % 3; a value with a / 3 >= n is treated as -2, and so
+ * is every negative value but -1.  a == -1: exit status 1 (a boundary edge).  a == -2: exit status 2 (non-manifold or flipped).
+ * Otherwise m is the first record of the target range whose prim, read as unsigned, is not below the target prim, found by binary
+ * search over the range (lo, hi = its ends; while lo < hi: mid = lo + (hi - lo) / 2, and lo = mid + 1 if prim_mid < target, else
+ * hi = mid; m = lo).  If there is no such m, or prim_m is not the target prim, or m is not live, or m's owner is not the target
+ * query: exit status 3 (the neighbour is not in the list).  Else if (code_m & 15) is not the required entry code: exit status 4
+ * (the neighbour is cut through other edges).  Else succ(j) = m, exit status 0.  Both tables pair half-edges one to one, so m's
+ * range, prim and entry code name j uniquely: succ is injective, and the components are simple paths and simple cycles.  On input
+ * that breaks this (a query_adj that is no involution, a prim twice in a range), of the records that claim the same successor the
+ * one of smallest index keeps it and the others get exit status 3: the components are simple paths and simple cycles on any
+ * input, and every index written is below total.
+ * Canonical order: one order over the whole list, because a curve crosses queries.  A path starts at its record without a
+ * predecessor; a cycle starts at its record of smallest index, and is closed.  A record that is not live is a chain of one.  The
+ * chains are ordered by the ascending index of their first record, and position pos runs over [0, total) in that order.
+ * slots[pos] = {seg, first, length, flags} as drt_renderer_chain_sections has them: seg = the index into segs of the record that
+ * stands there; first = the position of its chain's first record; length = its chain's length; flags: bit 0 = the chain is
+ * closed, bits 1..3 = that record's exit status.  Every slot below total is written.  counts = {chains of live records, closed
+ * ones among them, records that are not live}.  The result depends on segs, splits and the two tables only.
+ * What this is not: no welding and no new points -- a curve's vertices are the p of its records, plus the last q of an open
+ * chain; a curve is closed exactly where neighbouring triangles of either mesh agree on the side of their shared vertices, and
+ * statuses 3 and 4 mark the places where they do not (a curve that runs through vertices or along edges falls into open chains);
+ * self-intersection curves are not chained -- a mesh against itself lists each pair from both sides with different roles and
+ * orientation; no clipped polygons and no boolean; no RendererGroup; nothing on the command line.
+ * Checks, drt_renderer_chain_sections' in its order, with query_adj checked where splits is: NULL r or scene; n == 0 or
+ * total == 0 is DRT_OK with no launch; NULL segs, splits, query_adj or slots; segs and slots 16-byte aligned, splits, query_adj
+ * and counts 4-byte aligned; n < 2^31 and total < 2^31; no pending asynchronous batch; device memory on the renderer's device;
+ * the scene's upload (DRT_ERR_UNSUPPORTED beyond 64 levels); no BVH as drt_scene_edge_adjacency.  All DRT_ERR_INVALID but the
+ * upload's.  The framebuffer, accumulation, sample count, counters, kernel info and kernel span are not touched. */
+int           drt_tri_edge_adjacency(const drt_tri *tris, uint32_t n, int32_t *out, uint32_t capacity);
+int           drt_renderer_chain_intersections(drt_renderer *r, const drt_scene *scene, const drt_isect *segs, const uint32_t *splits,
+                                               const int32_t *query_adj, drt_chain_slot *slots, uint32_t *counts, uint32_t n,
+                                               uint32_t total, void *hip_stream);
 
 /* ---- first-hit guide buffers and the a-trous denoiser (new; the reference's TODO list, RayGen.cuh:13-21, starts with "DLSS 3.5
  * like features") ----
