@@ -636,8 +636,8 @@ struct Builder {
 
 void HostScene::build_bvh(int32_t target_leaf_prims, int32_t bin_count) {
     if (bin_count < 2) throw std::invalid_argument("bin_count must be >= 2");
-    nodes.clear();
-    revision = next_revision();
+    // Nothing of the scene changes before the build has succeeded: a refused build (BvhError) leaves the tree, the triangle
+    // order and the revision as they were, as build_bvh_on_device does.
     const int32_t n = (int32_t)triangles.size();
     drt_bvh_node root = fresh_node();
     set_bounds(root, absolute_extent<int32_t>(triangles, 0, n, nullptr));
@@ -645,7 +645,8 @@ void HostScene::build_bvh(int32_t target_leaf_prims, int32_t bin_count) {
     root.prim_count = n;
     if (n <= target_leaf_prims) {                        // BVHBuilder.cu:34-43
         root.is_leaf = 1;
-        nodes.push_back(root);
+        nodes.assign(1, root);
+        revision = next_revision();
         return;
     }
     std::vector<drt_triangle> work = triangles;          // reordered copy, committed on success
@@ -688,6 +689,7 @@ void HostScene::build_bvh(int32_t target_leaf_prims, int32_t bin_count) {
     }
     triangles.swap(work);
     nodes.swap(out);
+    revision = next_revision();
 }
 
 float HostScene::build_bvh_on_device(int32_t target_leaf_prims, int32_t bin_count, int device) {

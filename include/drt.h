@@ -175,7 +175,9 @@ int        drt_scene_add_material_ex(drt_scene *s, const drt_material *m);   /* 
 uint32_t   drt_pcg_hash(uint32_t input);
 float      drt_random_float(uint32_t *seed);
 int        drt_scene_add_texture(drt_scene *s, const uint8_t *texels, int32_t width, int32_t height, int32_t components);
-int        drt_scene_build_bvh(drt_scene *s, int32_t target_leaf_prims, int32_t bin_count);  /* BVHBuilder::buildIterative */
+/* BVHBuilder::buildIterative.  A build that fails (DRT_ERR_BVH, from any of the three builders below) changes nothing: the scene
+ * keeps the nodes and the triangle order it had. */
+int        drt_scene_build_bvh(drt_scene *s, int32_t target_leaf_prims, int32_t bin_count);
 /* The same build run on GPU `device`: identical nodes, node order and triangle order -- a bound that
  * is a zero may carry the other sign.  build_ms (may be NULL) receives the device time.  DRT_ERR_DEVICE without a GPU. */
 /* BVHBuilder::build (BVH/BVHBuilder.cu:100-173): the same tree and triangle order as drt_scene_build_bvh, with the node array in
