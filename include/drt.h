@@ -911,6 +911,22 @@ int           drt_renderer_sphere_cast(drt_renderer *r, const drt_scene *scene, 
  * statuses 3 and 4 mark the places where they do not (a curve that runs through vertices or along edges falls into open chains);
  * self-intersection curves are not chained -- a mesh against itself lists each pair from both sides with different roles and
  * orientation; no clipped polygons and no boolean; no RendererGroup; nothing on the command line.
+ * Working range and hostile surfaces (measured on the restatements, tests/test_hostile_surfaces_ref.py asserts the figures, and
+ * compared with the kernels bit for bit in tests/test_gpu_hostile_surfaces.py; no rule is changed here).  Far from the origin: two
+ * UV spheres of 1520 and 960 triangles of radius about 1 cut in one closed loop of 186 records; moved to (4096, -8192, 16384) and
+ * rounded to fp32 the same pair gives three open chains of 58, 123 and 8 records that all end with status 4 -- a coordinate of 16384
+ * leaves 2^-9 of resolution, and neighbours no longer agree on the side of a shared vertex.  Translate such a pair to its own
+ * origin first.  Zero-area triangles inside a connected mesh (the cap (a, b, m) that closes an edge a b split on one side only, m
+ * its midpoint): drt_renderer_chain_sections runs THROUGH an exactly flat cap -- the cap is cut like any triangle, its record has
+ * zero length, and the contour stays closed (a band of 1040 triangles with 120 such caps: one closed chain at every level).
+ * drt_renderer_intersect_triangles gives an exactly flat triangle no record at all (nt = 0, so u0 = u1 = u2 = 0 are one class), and
+ * a curve that reaches one ends there with status 3; a cap whose midpoint was rounded is a sliver, has records, and links or ends
+ * with 3 or 4 as its rounded normal decides.  A cap on each side of one edge makes the edges a m and m b non-manifold (-2).
+ * Scale: the records are unchanged for 2^-24 to 2^32 (nq, nt are second powers of the lengths, D = cross(nq, nt) a fourth).  Beyond,
+ * they are lost one by one, not all at once: of 229 records of the degenerate test mesh 213 are left at 2^-32, 68 at 2^-36 and none
+ * at 2^-40 (D passes through the subnormals to 0 and fabsf(D[j]) > 0 fails); 161 at 2^36, 125 at 2^42 and 4 at 2^50 (infinities
+ * compare like large numbers until inf - inf gives a NaN, which fails every comparison).  The chains of what is left follow the
+ * rules as written.
  * Checks, drt_renderer_chain_sections' in its order, with query_adj checked where splits is: NULL r or scene; n == 0 or
  * total == 0 is DRT_OK with no launch; NULL segs, splits, query_adj or slots; segs and slots 16-byte aligned, splits, query_adj
  * and counts 4-byte aligned; n < 2^31 and total < 2^31; no pending asynchronous batch; device memory on the renderer's device;
