@@ -334,6 +334,7 @@ _sig("drt_renderer_overlap_boxes", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P, 
 _sig("drt_renderer_overlap_triangles", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_renderer_plane_sections", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_renderer_intersect_triangles", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P)
+_sig("drt_renderer_triangle_distance", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_scene_edge_adjacency", C.c_int, _P, _P, C.c_uint32)
 _sig("drt_renderer_chain_sections", C.c_int, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _P)
 _sig("drt_tri_edge_adjacency", C.c_int, _P, C.c_uint32, _P, C.c_uint32)
@@ -642,6 +643,9 @@ BoxTable = collections.namedtuple("BoxTable", "prim count")             # the fi
 TriList = collections.namedtuple("TriList", "splits prim")               # every triangle that query triangles touch, CSR (Renderer.overlapTriangles)
 TriTable = collections.namedtuple("TriTable", "prim count")             # the first k triangles that query triangles touch (Renderer.overlapTriangles, k=)
 OVERLAP_LIST, OVERLAP_ANY = 0, 1                                        # drt.h DRT_OVERLAP_*
+TRIDIST_NEAREST, TRIDIST_ANY = 0, 1                                      # drt.h DRT_TRIDIST_*
+TriNearest = collections.namedtuple("TriNearest", "d2 prim point_q point_t u v feature")   # the mesh triangle nearest query triangles (Renderer.triangleDistance)
+MeshDistance = collections.namedtuple("MeshDistance", "d2 query prim point_q point_t feature")   # the nearest pair of a batch (Renderer.meshDistance)
 SectionList = collections.namedtuple("SectionList", "splits p q prim code")   # every segment where planes cut the mesh, CSR (Renderer.planeSections)
 SECTION_LIST, SECTION_ANY = 0, 1                                        # drt.h DRT_SECTION_*
 CutList = collections.namedtuple("CutList", "splits p q prim code")     # every segment where query triangles cut the mesh, CSR (Renderer.intersectTriangles)
@@ -1372,6 +1376,94 @@ class Renderer:
             _check(_lib.drt_renderer_overlap_triangles(self._h, scene._h, packed.data_ptr(), None, None, 0, counts.data_ptr(), n, OVERLAP_ANY, stream))
         res = counts > 0
         return res.cpu().numpy() if from_numpy else res
+
+    def _tri_distance(self, scene, tris, max_dist, mode):
+        """(records [N, 12] float32 on the device (drt_tri_near), came_from_numpy) of drt_renderer_triangle_distance.  max_dist: a
+        scalar (inf: the entry point's NULL) or [N] float32 of the triangles' kind."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        packed, from_numpy = _tri_batch(torch, dev, tris)
+        n = packed.shape[0]
+        md = None
+        if isinstance(max_dist, (int, float, np.floating, np.integer)) and not isinstance(max_dist, bool):
+            if float(max_dist) != float("inf"):
+                md = torch.full((n,), float(max_dist), dtype=torch.float32, device=dev)
+        elif isinstance(max_dist, np.ndarray) or torch.is_tensor(max_dist):
+            if isinstance(max_dist, np.ndarray) != from_numpy:
+                raise DrtError(ERR_INVALID, "mix of numpy arrays and device tensors")
+            if max_dist.dtype != (np.float32 if from_numpy else torch.float32):
+                raise DrtError(ERR_INVALID, "max_dist: dtype %s, float32 expected" % max_dist.dtype)
+            if not from_numpy and max_dist.device != dev:
+                raise DrtError(ERR_INVALID, "max_dist: on %s, the renderer is on %s" % (max_dist.device, dev))
+            if tuple(max_dist.shape) != (n,):
+                raise DrtError(ERR_INVALID, "max_dist: shape %s for %d triangles" % (tuple(max_dist.shape), n))
+            md = torch.from_numpy(np.ascontiguousarray(max_dist)).to(dev) if from_numpy else max_dist.contiguous()
+        else:
+            raise DrtError(ERR_INVALID, "max_dist: a number, a numpy array or a torch tensor expected")
+        out = torch.empty((n, 12), dtype=torch.float32, device=dev)
+        if n:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(_lib.drt_renderer_triangle_distance(self._h, scene._h, packed.data_ptr(), None if md is None else md.data_ptr(),
+                                                       out.data_ptr(), n, mode, stream))
+        return out, from_numpy
+
+    def triangleDistance(self, scene, tris, max_dist=float("inf")):
+        """The mesh triangle nearest each query triangle (drt_renderer_triangle_distance in mode DRT_TRIDIST_NEAREST): TriNearest(d2 [N],
+        prim [N] int32, point_q [N, 3], point_t [N, 3], u, v, feature [N] int32).  point_q lies on the query triangle, point_t on
+        triangle prim at barycentrics (u, v), and d2 is their squared distance; feature & 15 names the deciding candidate (0..2 a
+        query vertex, 3..5 a vertex of the scene triangle, 6 + 3 i + j an edge pair).  Where the pair touches -- the overlap predicate
+        of overlapTriangles does not separate it -- d2 = 0, feature has bit 16 set and the points are not a contact point.  prim -1 =
+        nothing within max_dist, a query with a NaN or an infinity, or an empty scene (then d2 = max_dist^2 and the rest is 0).
+        tris: vertices [N, 3, 3] float32, or a packed [N, 12] (drt_tri); max_dist: a scalar or [N].  No penetration depth, no
+        self-clearance (a triangle of the scene touches itself), alpha cut-outs are ignored.  Device tensors in, device tensors out
+        (enqueued on the current torch stream); numpy in, numpy out.  After refit(scene, positions) the moved geometry is queried."""
+        import torch
+        out, from_numpy = self._tri_distance(scene, tris, max_dist, TRIDIST_NEAREST)
+        if from_numpy:
+            h = out.cpu().numpy()
+            i = h.view(np.int32)
+            return TriNearest(h[:, 3].copy(), i[:, 7].copy(), h[:, 0:3].copy(), h[:, 4:7].copy(), h[:, 8].copy(), h[:, 9].copy(), i[:, 10].copy())
+        i = out.view(torch.int32)
+        return TriNearest(out[:, 3], i[:, 7], out[:, 0:3], out[:, 4:7], out[:, 8], out[:, 9], i[:, 10])
+
+    def withinDistance(self, scene, tris, dist):
+        """Whether any triangle of the mesh lies within `dist` (a scalar or [N]) of each query triangle, strictly: bool [N]
+        (drt_renderer_triangle_distance in mode DRT_TRIDIST_ANY, whose search ends at the first pair found).  dist = 0 finds nothing:
+        touching is intersectsAny.  Triangles and conventions as triangleDistance."""
+        import torch
+        out, from_numpy = self._tri_distance(scene, tris, dist, TRIDIST_ANY)
+        res = out.view(torch.int32)[:, 7] >= 0
+        return res.cpu().numpy() if from_numpy else res
+
+    def meshDistance(self, scene, tris, max_dist=float("inf")):
+        """The clearance between a query mesh and the scene: the smallest d2 of triangleDistance over the batch, reduced on the device:
+        MeshDistance(d2, query, prim, point_q [3], point_t [3], feature) -- query is the index of the query triangle, and of equal d2
+        the smallest index wins.  An empty batch or no pair within max_dist: query = prim = -1, d2 = inf, the rest 0.  d2 = 0 means
+        that the meshes touch by the overlap predicate; there is no penetration depth.  Device tensors in, 0-dimensional device
+        tensors out (nothing is read back); numpy in, numpy scalars out."""
+        import torch
+        out, from_numpy = self._tri_distance(scene, tris, max_dist, TRIDIST_NEAREST)
+        n = out.shape[0]
+        dev = out.device
+        miss = torch.zeros(12, dtype=torch.float32, device=dev)
+        miss[3] = float("inf")
+        miss.view(torch.int32)[7] = -1
+        query = torch.full((), -1, dtype=torch.int64, device=dev)
+        row = miss
+        if n:
+            hit = out.view(torch.int32)[:, 7] >= 0
+            key = torch.where(hit, out[:, 3], torch.full_like(out[:, 3], float("inf")))
+            least = hit & (key == key.min())                                       # (a hit's d2 is finite: below max_dist^2)
+            index = torch.arange(n, dtype=torch.int64, device=dev)
+            first = torch.where(least, index, torch.full_like(index, n)).min()     # the smallest query index of equal minima
+            found = first < n
+            row = torch.where(found, out.index_select(0, first.clamp(max=n - 1).reshape(1))[0], miss)
+            query = torch.where(found, first, query)
+        i = row.view(torch.int32)
+        res = MeshDistance(row[3], query.to(torch.int32), i[7], row[0:3], row[4:7], i[10])
+        if from_numpy:
+            return MeshDistance(*(x.cpu().numpy().copy() if x.dim() else x.cpu().numpy()[()] for x in res))
+        return res
 
     def selfIntersections(self, scene, positions=None):
         """Where the scene's mesh cuts itself: int32 [P, 2], the pairs i < j of triangle indices (tree order, as every query reports

@@ -359,6 +359,14 @@ public:
                           uint32_t *counts, uint32_t n, int32_t mode, void *stream = nullptr) {
         drt::check(drt_renderer_overlap_triangles(handle, scene.handle, tris, offsets, prims, prims_capacity, counts, n, mode, stream));
     }
+    // new: the mesh triangle nearest each query triangle within max_dist[i] (null: infinite), a drt_tri_near {point_q[3], d2,
+    // point_t[3], prim, u, v, feature} per query (drt_renderer_triangle_distance); d2 = 0 with feature | 16 where the overlap predicate
+    // does not separate the pair; the miss record is zeros with d2 = max_dist^2 and prim = -1.  Mode DRT_TRIDIST_ANY ends a query at
+    // the first pair within the distance.  Device arrays, tris and out 16-byte aligned, enqueued on `stream`.
+    void TriangleDistance(const Scene &scene, const drt_tri *tris, const float *max_dist, drt_tri_near *out, uint32_t n,
+                          int32_t mode = DRT_TRIDIST_NEAREST, void *stream = nullptr) {
+        drt::check(drt_renderer_triangle_distance(handle, scene.handle, tris, max_dist, out, n, mode, stream));
+    }
     // new: the segments where each query plane dot(n, x) = d cuts the mesh, a drt_plane {n[3], d} (drt_renderer_plane_sections): one
     // drt_section {p[3], prim, q[3], code} per cut triangle in ascending triangle index, p -> q counter-clockwise about n on a closed
     // mesh with outward faces; the miss record is zeros with prim = -1.  Modes (DRT_SECTION_LIST / DRT_SECTION_ANY), segments, counts

@@ -32,8 +32,8 @@ extern "C" {
  * point (drt_renderer_list_hits), the sphere-cast entry point (drt_renderer_sphere_cast), the nearest-list entry point
  * (drt_renderer_nearest_list), the box-overlap entry point (drt_renderer_overlap_boxes), the triangle-overlap entry point
  * (drt_renderer_overlap_triangles), the plane-section entry point (drt_renderer_plane_sections), the intersection-segment entry
- * point (drt_renderer_intersect_triangles) and the intersection-curve entry points (drt_tri_edge_adjacency,
- * drt_renderer_chain_intersections) are additions to it */
+ * point (drt_renderer_intersect_triangles), the intersection-curve entry points (drt_tri_edge_adjacency,
+ * drt_renderer_chain_intersections) and the triangle-distance entry point (drt_renderer_triangle_distance) are additions to it */
 #define DRT_ABI_VERSION 2
 
 typedef enum {
@@ -847,6 +847,10 @@ int           drt_renderer_sphere_cast(drt_renderer *r, const drt_scene *scene, 
  * vanish).
  * drt_renderer_overlap_boxes: the cross axes are third powers and only comparisons leave the test: unchanged for 2^-32 to 2^42.
  * drt_renderer_overlap_triangles: fourth powers: unchanged for 2^-30 to 2^30; beyond, pairs are no longer listed.
+ * drt_renderer_triangle_distance: the point-triangle candidates are drt_renderer_nearest's fourth powers, den = a e - b b of an edge
+ * pair is one too, and the predicate is drt_renderer_overlap_triangles': unchanged for 2^-30 to 2^26 on a mesh of the same kind with
+ * query triangles of the same sizes (tests/test_tri_distance_ref.py asserts the figure); beyond, candidates become NaNs, which never
+ * win, and pairs that touch are no longer seen to.
  * drt_renderer_sphere_cast: disc = ee (A r2 - det det) with A = |cross(d, e)|^2 is an EIGHTH power of the lengths when the direction is
  * scaled with the mesh (t stays), a sixth with a direction of fixed length: unchanged for 2^-4 to 2^10 only.  Give a large or a tiny mesh
  * directions of about unit length, or rescale it.  Apart from scale, a sliver (three vertices collinear to the last bit) has a face test
@@ -936,6 +940,71 @@ int           drt_tri_edge_adjacency(const drt_tri *tris, uint32_t n, int32_t *o
 int           drt_renderer_chain_intersections(drt_renderer *r, const drt_scene *scene, const drt_isect *segs, const uint32_t *splits,
                                                const int32_t *query_adj, drt_chain_slot *slots, uint32_t *counts, uint32_t n,
                                                uint32_t total, void *hip_stream);
+
+/* ---- triangle distance queries (new; the mesh triangle nearest each query triangle -- how far apart two meshes are) ----
+ * One query = a drt_tri (48 bytes, 16-byte aligned, the three pad words are ignored) and a search distance: max_dist[i], or infinite
+ * when max_dist is NULL.  The answer is the triangle of the mesh nearest the query triangle within that distance, the squared
+ * distance and a witness pair of points.  A mesh is a batch of queries; the clearance of two meshes is the smallest d2 of the batch.
+ * All arithmetic is fp32 with one rounding per operation, in the order written; dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z, / is the
+ * correctly rounded division; there is no tolerance anywhere.
+ * Validity and bounds are drt_renderer_overlap_triangles', unchanged: a query is valid iff all nine coordinates satisfy
+ * fabsf(x) <= FLT_MAX, and qmin[j] = min3(q0[j], q1[j], q2[j]), qmax[j] = max3(q0[j], q1[j], q2[j]).  An invalid query pushes nothing
+ * and gets the miss record.
+ * Pair distance, on the query (q0, q1, q2) and the stored (v0, e1, e2), relative to q0 as the overlap test is, so that the magnitudes
+ * are those of the pair and not of its distance from the origin:
+ *   a1 = q1 - q0, a2 = q2 - q0, g = a2 - a1; p0 = v0 - q0, p1 = p0 + e1, p2 = p0 + e2, h = e2 - e1.
+ * Fifteen candidates, in this order:
+ *   0..2   the query's vertices 0, a1, a2 against the scene triangle (p0, e1, e2), by the seven cases of drt_renderer_nearest:
+ *          c_query = the vertex, c_scene = (p0 + e1 u) + e2 v, dist2 as there
+ *   3..5   the scene triangle's vertices p0, p1, p2 against the query triangle (0, a1, a2), by the same routine with v0 = 0:
+ *          c_scene = the vertex, c_query = (0 + a1 u) + a2 v
+ *   6..14  the nine edge pairs: query edge i of ((0, a1), (a1, g), (a2, -a2)) against scene edge j of ((p0, e1), (p1, h), (p2, -e2)),
+ *          candidate 6 + 3 i + j
+ * An edge pair (P1, d1), (P2, d2) is the clamped segment-segment closest points of Ericson, Real-Time Collision Detection 5.1.9, with
+ * exact-zero degenerate cases and no epsilon:
+ *   r = P1 - P2, a = dot(d1, d1), e = dot(d2, d2), f = dot(d2, r), c = dot(d1, r), b = dot(d1, d2), den = a e - b b;
+ *   clamp(x) = fminf(fmaxf(x, 0), 1) + 0 (a NaN x gives 0; the sum makes a zero result +0 whichever zero fmaxf(-0, 0) returns);
+ *   a <= 0 && e <= 0: s = t = 0;  else a <= 0: s = 0, t = clamp(f / e);  else e <= 0: t = 0, s = clamp(-c / a);
+ *   otherwise s = den > 0 ? clamp((b f - c e) / den) : 0 and t = (b s + f) / e; if t < 0 then t = 0 and s = clamp(-c / a); else if
+ *   t > 1 then t = 1 and s = clamp((b - c) / a);
+ *   c_query = c1 = P1 + d1 s, c_scene = c2 = P2 + d2 t, diff = c1 - c2, dist2 = dot(diff, diff).
+ * The pair's d2 and its candidate: d2 = +infinity, candidate = 0, and candidate k, in order, replaces them iff its dist2 < d2 -- strict,
+ * so the first wins a tie and a NaN never wins.  Every candidate is the squared distance of two points that lie on the two triangles,
+ * so d2 never understates the true distance by more than rounding.  Then, if the seventeen axes of drt_renderer_overlap_triangles'
+ * triangle test (unchanged) do not separate the pair: d2 = 0 and feature = candidate | 16; the witness points stay those of the best
+ * candidate and are then NOT a contact point.  Otherwise feature = candidate.  The predicate is part of the rule because the fifteen
+ * candidates alone cannot see an edge that pierces the interior of a large triangle: there all fifteen are positive.  Its conservatism
+ * on zero-area triangles is inherited: a segment or a point may get d2 = 0 for a near miss in the triangle's own plane.
+ * Node bound: per axis d = fmaxf(fmaxf(bmin - qmax, 0), qmin - bmax) (a NaN operand is dropped), box2 = (dx dx + dy dy) + dz dz:
+ * drt_renderer_nearest's box distance with the point replaced by the query's interval.
+ * Traversal: drt_renderer_nearest's, word for word.  best = max_dist * max_dist, prim = -1.  The root is pushed with its box2.  A
+ * popped entry is dropped unless box2 < best.  A leaf tests its triangles in order; a pair replaces the result iff d2 < best.  An
+ * interior node computes box2 of both children and pushes a child iff its box2 < best, the farther one first (b1 > b2 -> child 1).
+ * Once a pair with d2 = 0 is found nothing passes any more, so touching meshes end early.  The node bound is taken in absolute
+ * coordinates and the pair relative to q0: for a query far from a flat wall the two can differ by an ulp, and a triangle whose node
+ * the bound rejects is not tested, whatever its pair distance would be.
+ * Modes: DRT_TRIDIST_NEAREST is the search above.  DRT_TRIDIST_ANY ends a query at the first pair with d2 < best and records that
+ * pair: the first within the distance in traversal order, not the nearest.  Its purpose is the boolean prim >= 0.
+ * Result: drt_tri_near {point_q, d2, point_t, prim, u, v, feature, pad}, 48 bytes.  point_q = q0 + c_query and point_t = q0 + c_scene
+ * of the winning candidate of the winning pair; prim = triangle index in drt_scene_get_triangles order; (u, v) are the barycentrics
+ * of point_t on the scene triangle, v0 + e1 u + e2 v: the routine's own for candidates 0..2; (0, 0), (1, 0), (0, 1) for 3, 4, 5; and
+ * from the edge parameter t for 6..14 -- (t, 0) on scene edge 0, (1 - t, t) on edge 1, (0, 1 - t) on edge 2, one subtraction.  pad = 0.
+ * The miss record (nothing within max_dist, an invalid query, a NaN max_dist, an empty scene) is all zero with d2 = max_dist * max_dist
+ * and prim = -1.  A negative max_dist searches as its absolute value does, as drt_renderer_nearest's.  A result depends on its query
+ * and the scene only.
+ * What this is not: there is no penetration depth -- d2 = 0 says that the conservative overlap predicate does not separate the pair,
+ * and nothing about how deep; no self-clearance -- a query taken from the scene itself touches itself and its neighbours; one answer
+ * per query -- no k-nearest or within-distance list of triangles; alpha cut-outs are ignored.
+ * Conventions are drt_renderer_nearest's and drt_renderer_overlap_triangles': the argument checks in that order (the handles, the mode,
+ * n == 0 is a no-op, NULL tris or out, alignment -- tris and out 16-byte, max_dist 4-byte --, n < 2^31, a pending batch, device memory
+ * on the renderer's device), hip_stream NULL = the renderer's stream, the call only enqueues, in order with the other queries (the
+ * same event), a refitted device copy is the one queried, the 64-level bound, legal on a sharded renderer, and the framebuffer,
+ * accumulation, sample count, counters, kernel info and kernel span are not touched. */
+typedef struct drt_tri_near { float point_q[3]; float d2; float point_t[3]; int32_t prim; float u, v; int32_t feature; int32_t pad; } drt_tri_near;   /* 48 B */
+#define DRT_TRIDIST_NEAREST 0
+#define DRT_TRIDIST_ANY     1
+int           drt_renderer_triangle_distance(drt_renderer *r, const drt_scene *scene, const drt_tri *tris, const float *max_dist,
+                                             drt_tri_near *out, uint32_t n, int32_t mode, void *hip_stream);
 
 /* ---- first-hit guide buffers and the a-trous denoiser (new; the reference's TODO list, RayGen.cuh:13-21, starts with "DLSS 3.5
  * like features") ----
