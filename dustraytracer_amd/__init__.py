@@ -335,6 +335,7 @@ _sig("drt_renderer_overlap_triangles", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, 
 _sig("drt_renderer_plane_sections", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_renderer_intersect_triangles", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P)
 _sig("drt_renderer_triangle_distance", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, C.c_int32, _P)
+_sig("drt_renderer_triangle_cast", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_scene_edge_adjacency", C.c_int, _P, _P, C.c_uint32)
 _sig("drt_renderer_chain_sections", C.c_int, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _P)
 _sig("drt_tri_edge_adjacency", C.c_int, _P, C.c_uint32, _P, C.c_uint32)
@@ -646,6 +647,9 @@ OVERLAP_LIST, OVERLAP_ANY = 0, 1                                        # drt.h 
 TRIDIST_NEAREST, TRIDIST_ANY = 0, 1                                      # drt.h DRT_TRIDIST_*
 TriNearest = collections.namedtuple("TriNearest", "d2 prim point_q point_t u v feature")   # the mesh triangle nearest query triangles (Renderer.triangleDistance)
 MeshDistance = collections.namedtuple("MeshDistance", "d2 query prim point_q point_t feature")   # the nearest pair of a batch (Renderer.meshDistance)
+TRICAST_FIRST, TRICAST_ANY = 0, 1                                        # drt.h DRT_TRICAST_*
+TriHits = collections.namedtuple("TriHits", "t prim point normal u v feature")   # first contacts of translating triangles (Renderer.triangleCast)
+MeshHit = collections.namedtuple("MeshHit", "t query prim point normal feature")   # the earliest contact of a batch (Renderer.meshCast)
 SectionList = collections.namedtuple("SectionList", "splits p q prim code")   # every segment where planes cut the mesh, CSR (Renderer.planeSections)
 SECTION_LIST, SECTION_ANY = 0, 1                                        # drt.h DRT_SECTION_*
 CutList = collections.namedtuple("CutList", "splits p q prim code")     # every segment where query triangles cut the mesh, CSR (Renderer.intersectTriangles)
@@ -1463,6 +1467,102 @@ class Renderer:
         res = MeshDistance(row[3], query.to(torch.int32), i[7], row[0:3], row[4:7], i[10])
         if from_numpy:
             return MeshDistance(*(x.cpu().numpy().copy() if x.dim() else x.cpu().numpy()[()] for x in res))
+        return res
+
+    def _tri_cast(self, scene, tris, dirs, tmax, mode):
+        """(records [N, 12] float32 on the device (drt_tri_hit), came_from_numpy) of drt_renderer_triangle_cast.  dirs: [3] or [N, 3]
+        float32 of the triangles' kind; tmax: a scalar or [N] float32 of the triangles' kind."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        packed, from_numpy = _tri_batch(torch, dev, tris)
+        n = packed.shape[0]
+
+        def per_cast(x, name, tail):
+            if isinstance(x, (list, tuple)):
+                x = np.asarray(x, np.float32) if from_numpy else torch.tensor(x, dtype=torch.float32, device=dev)
+            if not (isinstance(x, np.ndarray) or torch.is_tensor(x)):
+                raise DrtError(ERR_INVALID, "%s: a number, a numpy array or a torch tensor expected" % name)
+            if isinstance(x, np.ndarray) != from_numpy:
+                raise DrtError(ERR_INVALID, "mix of numpy arrays and device tensors")
+            if x.dtype != (np.float32 if from_numpy else torch.float32):
+                raise DrtError(ERR_INVALID, "%s: dtype %s, float32 expected" % (name, x.dtype))
+            if not from_numpy and x.device != dev:
+                raise DrtError(ERR_INVALID, "%s: on %s, the renderer is on %s" % (name, x.device, dev))
+            if tuple(x.shape) not in (tail, (n,) + tail):
+                raise DrtError(ERR_INVALID, "%s: shape %s for %d triangles" % (name, tuple(x.shape), n))
+            return torch.from_numpy(np.ascontiguousarray(x)).to(dev) if from_numpy else x
+
+        motions = torch.empty((n, 4), dtype=torch.float32, device=dev)             # drt_motion {d[3], tmax}
+        motions[:, 0:3] = per_cast(dirs, "dirs", (3,))
+        if isinstance(tmax, (int, float, np.floating, np.integer)) and not isinstance(tmax, bool):
+            motions[:, 3] = float(tmax)
+        else:
+            motions[:, 3] = per_cast(tmax, "tmax", ())
+        out = torch.empty((n, 12), dtype=torch.float32, device=dev)
+        if n:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(_lib.drt_renderer_triangle_cast(self._h, scene._h, packed.data_ptr(), motions.data_ptr(), out.data_ptr(), n, mode, stream))
+        return out, from_numpy
+
+    def triangleCast(self, scene, tris, dirs, tmax=1.0):
+        """The first contact of each query triangle translating along its direction with the mesh (drt_renderer_triangle_cast in mode
+        DRT_TRICAST_FIRST): TriHits(t [N], prim [N] int32, point [N, 3], normal [N, 3], u, v, feature [N] int32).  The triangle is at
+        tris + dirs * t, and t is the smallest in [0, tmax) at which it touches triangle prim, at `point` on that triangle with
+        barycentrics (u, v); normal is unnormalised and turned against the motion; feature & 15 names the deciding candidate (0..2 a
+        query vertex onto the face, 3..5 a vertex of the scene triangle onto the query's face, 6 + 3 i + j an edge pair).  Where the pair
+        already touches at the start -- the overlap predicate of overlapTriangles does not separate it -- t = 0, feature has bit 16 set
+        and point, normal, u, v are zeros.  prim -1 = nothing touched before tmax, a query with a NaN or an infinity, a NaN in dirs or
+        tmax, or an empty scene (then t = tmax, feature = -1 and the rest is 0).  tris: vertices [N, 3, 3] float32, or a packed
+        [N, 12] (drt_tri); dirs: [3] or [N, 3]; tmax: a scalar or [N].  No rotation, no thickness or tolerance, no penetration depth; a
+        coplanar pair sliding in its plane is seen only if it overlaps at the start; alpha cut-outs are ignored.  Device tensors in,
+        device tensors out (enqueued on the current torch stream); numpy in, numpy out.  After refit(scene, positions) the moved
+        geometry is queried."""
+        import torch
+        out, from_numpy = self._tri_cast(scene, tris, dirs, tmax, TRICAST_FIRST)
+        if from_numpy:
+            h = out.cpu().numpy()
+            i = h.view(np.int32)
+            return TriHits(h[:, 3].copy(), i[:, 7].copy(), h[:, 0:3].copy(), h[:, 4:7].copy(), h[:, 8].copy(), h[:, 9].copy(), i[:, 10].copy())
+        i = out.view(torch.int32)
+        return TriHits(out[:, 3], i[:, 7], out[:, 0:3], out[:, 4:7], out[:, 8], out[:, 9], i[:, 10])
+
+    def castsAny(self, scene, tris, dirs, tmax=1.0):
+        """Whether each query triangle touches the mesh anywhere along its motion in [0, tmax): bool [N] (drt_renderer_triangle_cast
+        in mode DRT_TRICAST_ANY, whose search ends at the first pair found).  Triangles and conventions as triangleCast."""
+        import torch
+        out, from_numpy = self._tri_cast(scene, tris, dirs, tmax, TRICAST_ANY)
+        res = out.view(torch.int32)[:, 7] >= 0
+        return res.cpu().numpy() if from_numpy else res
+
+    def meshCast(self, scene, tris, d, tmax=1.0):
+        """The time of impact of a query mesh translating along d with the scene: the smallest t of triangleCast over the batch, reduced
+        on the device: MeshHit(t, query, prim, point [3], normal [3], feature) -- query is the index of the query triangle, and of
+        equal t the smallest index wins.  An empty batch or no contact before tmax: query = prim = -1, t = inf, feature = -1, the rest
+        0.  t = 0 with feature bit 16 means that the meshes touch at the start by the overlap predicate; there is no penetration depth
+        and no rotation.  Device tensors in, 0-dimensional device tensors out (nothing is read back); numpy in, numpy scalars out."""
+        import torch
+        out, from_numpy = self._tri_cast(scene, tris, d, tmax, TRICAST_FIRST)
+        n = out.shape[0]
+        dev = out.device
+        miss = torch.zeros(12, dtype=torch.float32, device=dev)
+        miss[3] = float("inf")
+        miss.view(torch.int32)[7] = -1
+        miss.view(torch.int32)[10] = -1
+        query = torch.full((), -1, dtype=torch.int64, device=dev)
+        row = miss
+        if n:
+            hit = out.view(torch.int32)[:, 7] >= 0
+            key = torch.where(hit, out[:, 3], torch.full_like(out[:, 3], float("inf")))
+            least = hit & (key == key.min())                                       # (a hit's t is finite: below tmax)
+            index = torch.arange(n, dtype=torch.int64, device=dev)
+            first = torch.where(least, index, torch.full_like(index, n)).min()     # the smallest query index of equal minima
+            found = first < n
+            row = torch.where(found, out.index_select(0, first.clamp(max=n - 1).reshape(1))[0], miss)
+            query = torch.where(found, first, query)
+        i = row.view(torch.int32)
+        res = MeshHit(row[3], query.to(torch.int32), i[7], row[0:3], row[4:7], i[10])
+        if from_numpy:
+            return MeshHit(*(x.cpu().numpy().copy() if x.dim() else x.cpu().numpy()[()] for x in res))
         return res
 
     def selfIntersections(self, scene, positions=None):

@@ -367,6 +367,15 @@ public:
                           int32_t mode = DRT_TRIDIST_NEAREST, void *stream = nullptr) {
         drt::check(drt_renderer_triangle_distance(handle, scene.handle, tris, max_dist, out, n, mode, stream));
     }
+    // new: the first contact of each query triangle translating along motions[i].d with the mesh, the smallest t in [0, tmax), a
+    // drt_tri_hit {point[3], t, normal[3], prim, u, v, feature} per cast (drt_renderer_triangle_cast); t = 0 with feature | 16 where
+    // the overlap predicate does not separate the pair at the start; the miss record is zeros with t = tmax, prim = -1, feature = -1.
+    // Mode DRT_TRICAST_ANY ends a cast at the first pair found.  No rotation, no thickness, no penetration depth.  Device arrays, all
+    // three 16-byte aligned, enqueued on `stream`.
+    void TriangleCast(const Scene &scene, const drt_tri *tris, const drt_motion *motions, drt_tri_hit *out, uint32_t n,
+                      int32_t mode = DRT_TRICAST_FIRST, void *stream = nullptr) {
+        drt::check(drt_renderer_triangle_cast(handle, scene.handle, tris, motions, out, n, mode, stream));
+    }
     // new: the segments where each query plane dot(n, x) = d cuts the mesh, a drt_plane {n[3], d} (drt_renderer_plane_sections): one
     // drt_section {p[3], prim, q[3], code} per cut triangle in ascending triangle index, p -> q counter-clockwise about n on a closed
     // mesh with outward faces; the miss record is zeros with prim = -1.  Modes (DRT_SECTION_LIST / DRT_SECTION_ANY), segments, counts

@@ -33,7 +33,8 @@ extern "C" {
  * (drt_renderer_nearest_list), the box-overlap entry point (drt_renderer_overlap_boxes), the triangle-overlap entry point
  * (drt_renderer_overlap_triangles), the plane-section entry point (drt_renderer_plane_sections), the intersection-segment entry
  * point (drt_renderer_intersect_triangles), the intersection-curve entry points (drt_tri_edge_adjacency,
- * drt_renderer_chain_intersections) and the triangle-distance entry point (drt_renderer_triangle_distance) are additions to it */
+ * drt_renderer_chain_intersections), the triangle-distance entry point (drt_renderer_triangle_distance) and the triangle-cast entry
+ * point (drt_renderer_triangle_cast) are additions to it */
 #define DRT_ABI_VERSION 2
 
 typedef enum {
@@ -851,6 +852,11 @@ int           drt_renderer_sphere_cast(drt_renderer *r, const drt_scene *scene, 
  * pair is one too, and the predicate is drt_renderer_overlap_triangles': unchanged for 2^-30 to 2^26 on a mesh of the same kind with
  * query triangles of the same sizes (tests/test_tri_distance_ref.py asserts the figure); beyond, candidates become NaNs, which never
  * win, and pairs that touch are no longer seen to.
+ * drt_renderer_triangle_cast: every det and numerator is a THIRD power of the lengths when d is scaled with the mesh (t stays), and only
+ * comparisons and one quotient of two of them leave a candidate: unchanged for 2^-42 to 2^36 on a mesh of the same kind with query
+ * triangles of the same sizes and motions towards and away from it (tests/test_tri_cast_ref.py asserts the figure); beyond, the
+ * determinants pass through the subnormals to 0 (no candidate) or overflow to infinities and NaNs, which fail every test, and the
+ * predicate's fourth powers go as drt_renderer_overlap_triangles' do: contacts and start overlaps are lost.
  * drt_renderer_sphere_cast: disc = ee (A r2 - det det) with A = |cross(d, e)|^2 is an EIGHTH power of the lengths when the direction is
  * scaled with the mesh (t stays), a sixth with a direction of fixed length: unchanged for 2^-4 to 2^10 only.  Give a large or a tiny mesh
  * directions of about unit length, or rescale it.  Apart from scale, a sliver (three vertices collinear to the last bit) has a face test
@@ -1005,6 +1011,81 @@ typedef struct drt_tri_near { float point_q[3]; float d2; float point_t[3]; int3
 #define DRT_TRIDIST_ANY     1
 int           drt_renderer_triangle_distance(drt_renderer *r, const drt_scene *scene, const drt_tri *tris, const float *max_dist,
                                              drt_tri_near *out, uint32_t n, int32_t mode, void *hip_stream);
+
+/* ---- triangle casts (new; the first contact of a translating triangle with the mesh -- when a moving mesh touches) ----
+ * One cast = a drt_tri (48 bytes, 16-byte aligned, the three pad words are ignored) and a drt_motion {d[3], tmax} (16 bytes, 16-byte
+ * aligned).  The triangle is at q + d t; the answer is the smallest t in [0, tmax) at which it touches a triangle of the mesh, that
+ * triangle, the contact point on it and a contact normal.  There is no tmin: the caller passes the triangle where the motion starts, so
+ * t is a quotient and not a sum.  A moving mesh is a batch of casts; its time of impact is the smallest t of the batch.
+ * All arithmetic is fp32 with one rounding per operation, in the order written; dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z,
+ * cross(a, b) = (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x), / is the correctly rounded division; there is no tolerance
+ * and no thickness anywhere.
+ * Validity: the query is valid iff drt_renderer_overlap_triangles' validity holds (all nine coordinates satisfy fabsf(x) <= FLT_MAX)
+ * and no component of d and not tmax is a NaN.  An invalid cast pushes nothing and gets the miss record.
+ * Pair, on the query (q0, q1, q2) and the stored (v0, e1, e2), relative to q0 as the distance query is:
+ *   a1 = q1 - q0, a2 = q2 - q0, g = a2 - a1, nq = cross(a1, a2); p0 = v0 - q0, p1 = p0 + e1, p2 = p0 + e2, h = e2 - e1.
+ * How a quotient is formed, everywhere: a candidate has ONE determinant det and three numerators.  sg = det < 0 ? -1 : 1 and
+ * ad = fabsf(det); every numerator is multiplied by sg (exact); every test compares a numerator with 0 or with ad, all closed; and a
+ * parameter is fabsf(numerator) / ad, one division, formed only for a candidate that passed (so a zero is +0).  No parameter is
+ * divided before it is tested, and no reciprocal is taken.  A NaN fails every test; det = 0 has no candidate.
+ * Fifteen candidates, in this order:
+ *   0..2   the query's vertices 0, a1, a2 as rays (o, d) against the scene triangle (p0, e1, e2); 3..5 the scene triangle's vertices
+ *          p0, p1, p2 as rays (o, -d) against the query triangle (0, a1, a2).  A ray (o, d) against (w0, f1, f2) is Moller-Trumbore
+ *          without the renderer's 1e-6: pv = cross(d, f2), det = dot(f1, pv), tv = o - w0, qv = cross(tv, f1),
+ *          nu = dot(tv, pv) sg, nv = dot(d, qv) sg, ntau = dot(f2, qv) sg;
+ *          passes iff det != 0 && nu >= 0 && nv >= 0 && nu + nv <= ad && ntau >= 0; tau = fabsf(ntau) / ad.
+ *   6..14  the nine edge pairs: query edge i of ((0, a1), (a1, g), (a2, -a2)) against scene edge j of ((p0, e1), (p1, h), (p2, -e2)),
+ *          candidate 6 + 3 i + j.  An edge pair (a, ea), (b, eb) solves a + ea s + d tau = b + eb w by Cramer's rule on the columns
+ *          (ea, d, -eb): nb = -eb, c = cross(d, nb), det = dot(ea, c), r = b - a,
+ *          ns = dot(r, c) sg, ntau = dot(ea, cross(r, nb)) sg, nw = dot(ea, cross(d, r)) sg;
+ *          passes iff det != 0 && ns >= 0 && ns <= ad && nw >= 0 && nw <= ad && ntau >= 0; tau = fabsf(ntau) / ad.
+ * The pair's t and its candidate: t = +infinity, candidate = 15, and candidate k, in order, replaces them iff it passes and its
+ * tau < t -- strict, so the first wins a tie.  Touching counts: every comparison is closed.
+ * Start overlap: if the seventeen axes of drt_renderer_overlap_triangles' triangle test (unchanged) do not separate the query at
+ * t = 0 from the scene triangle, the pair's t = 0 and feature = candidate | 16 (31 if no candidate passed).  Otherwise feature =
+ * candidate.  The predicate is part of the rule because the candidates alone cannot see a pair that already interpenetrates: an edge
+ * through the interior of a large triangle moving along that triangle's plane has no candidate at all, or only positive ones.  Its
+ * conservatism on zero-area triangles is inherited.
+ * Across triangles, drt_renderer_sphere_cast's rule: best = tmax, prim = -1, and the pair of triangle k replaces the result iff
+ * t < best || (t == best && k < prim), so the answer does not depend on the tree.  tmax <= 0 finds nothing.
+ * Traversal: drt_renderer_sphere_cast's slab test with the query's extent in place of the radius.  ext_lo = qmin - q0 and
+ * ext_hi = qmax - q0 with qmin, qmax drt_renderer_overlap_triangles' bounds; inv_d = 1 / d per component; per axis
+ * t0 = ((bmin - ext_hi) - q0) inv_d, t1 = ((bmax - ext_lo) - q0) inv_d, enter = the largest of fminf(t0, t1), exit = the smallest of
+ * fmaxf(t1, t0) (a NaN operand, 0 * inf, is dropped).  A node is visited iff enter <= exit && exit >= 0 && enter <= best.  The root is
+ * pushed iff it passes and the cast is valid; a popped entry is dropped unless its enter <= best still holds; a leaf tests its
+ * triangles in order; an interior node pushes each child that passes, the farther one first (enter1 > enter2 -> child 1); the limit is
+ * 64 levels.  The node test is taken in absolute coordinates and the pair relative to q0: a contact whose widened box the fp32 slab test
+ * misses by a rounding is not found.  d = 0 degenerates to the static overlap test, as the sphere cast's zero direction does: every det
+ * is 0, inv_d is +-inf, and the result is the lowest-numbered triangle that the predicate does not separate, with t = 0, or a miss.
+ * Modes: DRT_TRICAST_FIRST is the search above.  DRT_TRICAST_ANY ends a cast at the first pair with t < best in traversal order and
+ * records that pair: not the first contact.  Its purpose is the boolean prim >= 0.
+ * Result: drt_tri_hit {point, t, normal, prim, u, v, feature, pad}, 48 bytes.  The contact is recomputed once, after the traversal,
+ * from the winning (prim, candidate), by the candidate's own operations:
+ *   0..2   u = fabsf(nu) / ad, v = fabsf(nv) / ad, c = (p0 + e1 u) + e2 v, normal = cross(e1, e2)
+ *   3..5   c = the vertex p0, p1 or p2, (u, v) = (0, 0), (1, 0), (0, 1), normal = nq
+ *   6..14  w = fabsf(nw) / ad, c = b + eb w, (u, v) = (w, 0) on scene edge 0, (1 - w, w) on edge 1, (0, 1 - w) on edge 2, one
+ *          subtraction, normal = cross(ea, eb)
+ * point = q0 + c is the contact point on the scene triangle (which does not move) and (u, v) its barycentrics there, v0 + e1 u + e2 v.
+ * normal is unnormalised and flipped against the motion: if dot(normal, d) > 0 every component is negated, so dot(normal, d) <= 0.  A
+ * start overlap (bit 16) has no contact: point, normal, u and v are zeros, t = 0.  pad = 0.  The miss record (nothing touched in
+ * [0, tmax), an invalid cast, an empty scene) is all zero with t = tmax, the motion's own word, prim = -1 and feature = -1.  A result
+ * depends on its cast and the scene only.  (Beyond the working range a field can be a NaN, inf / inf; which NaN is not specified.)
+ * What this is not: a pair that is coplanar and slides in its common plane is seen only by the start overlap -- every det is 0 there --
+ * as drt_renderer_intersect_triangles has no coplanar records either; there is no tolerance and no thickness -- a contact exactly on a
+ * seam (a vertex onto an edge, an edge onto a vertex) is found by whichever neighbouring candidate's closed test passes, and in fp32
+ * in rare cases by none; no rotation; no penetration depth -- t = 0 with bit 16 says that the conservative predicate does not separate
+ * the pair at the start, and nothing about how deep; alpha cut-outs are ignored; one answer per cast.
+ * Conventions are drt_renderer_triangle_distance's: the argument checks in that order (the handles, the mode, n == 0 is a no-op, NULL
+ * tris, motions or out, alignment -- all three 16-byte --, n < 2^31, a pending batch, device memory on the renderer's device),
+ * hip_stream NULL = the renderer's stream, the call only enqueues, in order with the other queries (the same event), a refitted device
+ * copy is the one queried, DRT_ERR_UNSUPPORTED beyond 64 levels, DRT_ERR_INVALID while an asynchronous batch is pending, legal on a
+ * sharded renderer, and the framebuffer, accumulation, sample count, counters, kernel info and kernel span are not touched. */
+typedef struct drt_motion { float d[3]; float tmax; } drt_motion;   /* 16 B */
+typedef struct drt_tri_hit { float point[3]; float t; float normal[3]; int32_t prim; float u, v; int32_t feature; int32_t pad; } drt_tri_hit;   /* 48 B */
+#define DRT_TRICAST_FIRST 0
+#define DRT_TRICAST_ANY   1
+int           drt_renderer_triangle_cast(drt_renderer *r, const drt_scene *scene, const drt_tri *tris, const drt_motion *motions,
+                                         drt_tri_hit *out, uint32_t n, int32_t mode, void *hip_stream);
 
 /* ---- first-hit guide buffers and the a-trous denoiser (new; the reference's TODO list, RayGen.cuh:13-21, starts with "DLSS 3.5
  * like features") ----

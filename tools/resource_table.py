@@ -37,6 +37,9 @@ def pretty(name):
     m = re.search(r"tri_distance_kernelILb(\d)E", name)
     if m:
         return "tri_distance_kernel<%s>" % ("ANY" if m.group(1) == "1" else "NEAREST")
+    m = re.search(r"tri_cast_kernelILb(\d)E", name)
+    if m:
+        return "tri_cast_kernel<%s>" % ("ANY" if m.group(1) == "1" else "FIRST")
     m = re.search(r"tri_overlap_kernelILb(\d)E", name)
     if m:
         return "tri_overlap_kernel<%s>" % ("ANY" if m.group(1) == "1" else "LIST")
@@ -55,7 +58,8 @@ def main():
     rows = []
     for src, extra in (("kernel_path_pool.hip", ()), ("kernel_path_pool.hip", ("-DDRT_POOL_EXT_TU",)), ("kernel_wave_queue.hip", ()),
                        ("render_kernels.hip", ()), ("kernel_bvh_build.hip", ()), ("kernel_sphere_cast.hip", ()), ("kernel_near_list.hip", ()),
-                       ("kernel_overlap.hip", ()), ("kernel_tri_overlap.hip", ()), ("kernel_intersect.hip", ()), ("kernel_tri_distance.hip", ())):
+                       ("kernel_overlap.hip", ()), ("kernel_tri_overlap.hip", ()), ("kernel_intersect.hip", ()), ("kernel_tri_distance.hip", ()),
+                       ("kernel_tri_cast.hip", ())):
         for r in remarks(src, extra):
             if "VGPRs" in r and not (extra and "ILi" in r["name"] and int(re.search(r"ILi(\d+)E", r["name"]).group(1)) < 16):
                 rows.append(r)
