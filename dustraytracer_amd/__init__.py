@@ -336,6 +336,9 @@ _sig("drt_renderer_plane_sections", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P,
 _sig("drt_renderer_intersect_triangles", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P)
 _sig("drt_renderer_triangle_distance", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, C.c_int32, _P)
 _sig("drt_renderer_triangle_cast", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, C.c_int32, _P)
+_sig("drt_renderer_surface_lookup", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P)
+_sig("drt_renderer_surface_weights", C.c_int, _P, _P, _P, _P)
+_sig("drt_renderer_sample_surface", C.c_int, _P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P)
 _sig("drt_scene_edge_adjacency", C.c_int, _P, _P, C.c_uint32)
 _sig("drt_renderer_chain_sections", C.c_int, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _P)
 _sig("drt_tri_edge_adjacency", C.c_int, _P, C.c_uint32, _P, C.c_uint32)
@@ -650,6 +653,11 @@ MeshDistance = collections.namedtuple("MeshDistance", "d2 query prim point_q poi
 TRICAST_FIRST, TRICAST_ANY = 0, 1                                        # drt.h DRT_TRICAST_*
 TriHits = collections.namedtuple("TriHits", "t prim point normal u v feature")   # first contacts of translating triangles (Renderer.triangleCast)
 MeshHit = collections.namedtuple("MeshHit", "t query prim point normal feature")   # the earliest contact of a batch (Renderer.meshCast)
+# what lies on the surface at references (Renderer.surface): material -1 = no such triangle
+Surface = collections.namedtuple("Surface", "position normal shading uv albedo emissive alpha roughness refractive_index material load_index texture "
+                                            "metallic transmission")
+SurfaceSamples = collections.namedtuple("SurfaceSamples", "prim u v")   # references drawn on the mesh by area (Renderer.sampleSurface)
+SURFACE_SCAN_BLOCK = 256                                                 # drt.h DRT_SURFACE_SCAN_BLOCK
 SectionList = collections.namedtuple("SectionList", "splits p q prim code")   # every segment where planes cut the mesh, CSR (Renderer.planeSections)
 SECTION_LIST, SECTION_ANY = 0, 1                                        # drt.h DRT_SECTION_*
 CutList = collections.namedtuple("CutList", "splits p q prim code")     # every segment where query triangles cut the mesh, CSR (Renderer.intersectTriangles)
@@ -1564,6 +1572,108 @@ class Renderer:
         if from_numpy:
             return MeshHit(*(x.cpu().numpy().copy() if x.dim() else x.cpu().numpy()[()] for x in res))
         return res
+
+    def surface(self, scene, refs, u=None, v=None, normals=None):
+        """What lies on the surface at references (prim, u, v) (drt_renderer_surface_lookup): Surface(position, normal, shading [.., 3],
+        uv [.., 2], albedo, emissive [.., 3], alpha, roughness, refractive_index, material, load_index, texture int32, metallic,
+        transmission bool), of the references' shape.  refs: anything with .prim, .u and .v of one shape -- the results of traceRays,
+        nearest, sphereCast, triangleCast, kNearest, sampleSurface ... -- or prim with u and v as three arrays.  prim outside the
+        mesh (a miss, -1): zeros with material = load_index = texture = -1.  u and v are used as given and extrapolate outside the
+        triangle.  position and normal (the stored face normal, not turned) are the device copy's: after refit(scene, positions) the
+        moved mesh's.  albedo and alpha are what the ALBEDO view shows: the flat albedo, or the nearest texel of the texture, as the
+        reference has -- no filtering, no normal maps, no tangents.  shading is the interpolated vertex normals and is not
+        normalised; normals: [n_tris, 3, 3] float32 in load order (a device tensor or numpy, the array refit takes) to use instead of
+        the host scene's, which None means also after a refit.  Device tensors in, device tensors out (enqueued on the current torch
+        stream); numpy in, numpy out."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        if u is None and v is None:
+            if not all(hasattr(refs, f) for f in ("prim", "u", "v")):
+                raise DrtError(ERR_INVALID, "refs: something with .prim, .u and .v expected, or prim, u and v")
+            prim, u, v = refs.prim, refs.u, refs.v
+        elif u is None or v is None:
+            raise DrtError(ERR_INVALID, "refs: prim, u and v expected")
+        else:
+            prim = refs
+        parts = []
+        from_numpy = isinstance(prim, np.ndarray)
+        for name, x, kind in (("prim", prim, "i"), ("u", u, "f"), ("v", v, "f")):
+            if not (isinstance(x, np.ndarray) or torch.is_tensor(x)):
+                raise DrtError(ERR_INVALID, "refs: %s: a numpy array or a torch tensor expected" % name)
+            if isinstance(x, np.ndarray) != from_numpy:
+                raise DrtError(ERR_INVALID, "refs: mix of numpy arrays and device tensors")
+            want = (np.int32 if from_numpy else torch.int32) if kind == "i" else (np.float32 if from_numpy else torch.float32)
+            if x.dtype != want:
+                raise DrtError(ERR_INVALID, "refs: %s: dtype %s, %s expected" % (name, x.dtype, "int32" if kind == "i" else "float32"))
+            if not from_numpy and x.device != dev:
+                raise DrtError(ERR_INVALID, "refs: %s: on %s, the renderer is on %s" % (name, x.device, dev))
+            if tuple(x.shape) != tuple(prim.shape):
+                raise DrtError(ERR_INVALID, "refs: %s: shape %s, prim has %s" % (name, tuple(x.shape), tuple(prim.shape)))
+            parts.append(x)
+        if from_numpy:                           # (after every check: nothing touches the device for a bad argument)
+            parts = [torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in parts]
+        shape = tuple(prim.shape)
+        n_tris = _lib.drt_scene_triangle_count(scene._h)
+        if normals is not None:
+            if isinstance(normals, np.ndarray):
+                normals = torch.from_numpy(np.ascontiguousarray(normals, np.float32)).to(dev)
+            elif not torch.is_tensor(normals):
+                raise DrtError(ERR_INVALID, "normals: a numpy array or a torch tensor expected")
+            if normals.dtype != torch.float32 or normals.device != dev or normals.numel() != 9 * n_tris:
+                raise DrtError(ERR_INVALID, "normals: %s %s with %d values, float32 [%d, 3, 3] on %s expected"
+                               % (normals.dtype, normals.device, normals.numel(), n_tris, dev))
+            normals = normals.contiguous()
+        packed = torch.zeros((parts[0].numel(), 4), dtype=torch.float32, device=dev)        # drt_hit {t, prim, u, v}
+        packed.view(torch.int32)[:, 1] = parts[0].reshape(-1)
+        packed[:, 2], packed[:, 3] = parts[1].reshape(-1), parts[2].reshape(-1)
+        n = packed.shape[0]
+        out = torch.empty((n, 24), dtype=torch.float32, device=dev)                         # drt_surface
+        if n:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(_lib.drt_renderer_surface_lookup(self._h, scene._h, packed.data_ptr(), normals.data_ptr() if normals is not None and n_tris else None,
+                                                    out.data_ptr(), n, stream))
+        if from_numpy:
+            h = out.cpu().numpy()
+            i = h.view(np.int32)
+            f = lambda a: a.copy().reshape(shape + a.shape[1:])
+            return Surface(f(h[:, 0:3]), f(h[:, 4:7]), f(h[:, 8:11]), f(h[:, 16:18]), f(h[:, 12:15]), f(h[:, 20:23]), f(h[:, 7]), f(h[:, 18]), f(h[:, 23]),
+                           f(i[:, 3]), f(i[:, 11]), f(i[:, 15]), f((i[:, 19] & 1) != 0), f((i[:, 19] & 2) != 0))
+        i = out.view(torch.int32)
+        f = lambda a: a.reshape(shape + tuple(a.shape[1:]))
+        return Surface(f(out[:, 0:3]), f(out[:, 4:7]), f(out[:, 8:11]), f(out[:, 16:18]), f(out[:, 12:15]), f(out[:, 20:23]), f(out[:, 7]), f(out[:, 18]),
+                       f(out[:, 23]), f(i[:, 3]), f(i[:, 11]), f(i[:, 15]), f((i[:, 19] & 1) != 0), f((i[:, 19] & 2) != 0))
+
+    def sampleSurface(self, scene, n, seed=0, first=0, as_torch=False):
+        """n references drawn on the mesh with probability proportional to area (drt_renderer_sample_surface): SurfaceSamples(prim [n]
+        int32, u, v [n] float32) with u, v >= 0 and u + v <= 1; they feed surface() as they are -- surface(scene, smp).position is a
+        point cloud of the mesh as it stands on the device, after a refit the moved one.  Sample k has index first + k of the stream
+        `seed` and depends on (seed, index) and the scene only, so first= continues a stream; first + n <= 2^32.  A triangle smaller
+        than 2^-36 of the largest is never drawn; a mesh without area gives prim -1 everywhere.  Independent hashes: not stratified,
+        no blue noise.  as_torch=True: device tensors, the work enqueued on the current torch stream; else numpy arrays."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        n, seed, first = int(n), int(seed), int(first)
+        if n < 0 or not 0 <= seed < 1 << 32 or not 0 <= first < 1 << 32 or first + n > 1 << 32:
+            raise DrtError(ERR_INVALID, "sampleSurface: n >= 0, seed and first in [0, 2^32) and first + n <= 2^32 expected")
+        out = torch.empty((n, 4), dtype=torch.float32, device=dev)
+        if n:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(_lib.drt_renderer_sample_surface(self._h, scene._h, seed, first, out.data_ptr(), n, stream))
+        if not as_torch:
+            h = out.cpu().numpy()
+            return SurfaceSamples(h.view(np.int32)[:, 1].copy(), h[:, 2].copy(), h[:, 3].copy())
+        return SurfaceSamples(out.view(torch.int32)[:, 1], out[:, 2], out[:, 3])
+
+    def surfaceWeights(self, scene, as_torch=False):
+        """The table sampleSurface draws from (drt_renderer_surface_weights): [n_tris] inclusive sums of the triangles' integer weights,
+        |cross(e1, e2)| of the device copy scaled so that the largest lies in [2^34, 2^35) and truncated; the last entry is the total.
+        numpy uint64, or with as_torch=True a device int64 tensor (the values are below 2^63), enqueued on the current torch stream."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        out = torch.empty(_lib.drt_scene_triangle_count(scene._h), dtype=torch.int64, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _check(_lib.drt_renderer_surface_weights(self._h, scene._h, out.data_ptr() if out.numel() else None, stream))
+        return out if as_torch else out.cpu().numpy().view(np.uint64)
 
     def selfIntersections(self, scene, positions=None):
         """Where the scene's mesh cuts itself: int32 [P, 2], the pairs i < j of triangle indices (tree order, as every query reports

@@ -1,4 +1,4 @@
-// renderer_state.hpp -- what the translation units of the C ABI share (drt_capi.cpp, drt_capi_filters.cpp, drt_capi_adaptive.cpp, drt_capi_section.cpp, drt_capi_contour.cpp, drt_capi_topology.cpp, drt_capi_intersect.cpp): the renderer's state,
+// renderer_state.hpp -- what the translation units of the C ABI share (drt_capi.cpp, drt_capi_filters.cpp, drt_capi_adaptive.cpp, drt_capi_section.cpp, drt_capi_contour.cpp, drt_capi_topology.cpp, drt_capi_intersect.cpp, drt_capi_surface.cpp): the renderer's state,
 // the owners of its device memory, pinned memory and events, error reporting, the steps several entry points take.  Not exported.
 #pragma once
 #include "../../include/drt.h"
@@ -227,6 +227,15 @@ struct drt_renderer {
     DeviceArray<drt::AdaptiveTotals> ad_totals;
     DeviceArray<drt_path_ray> ad_rays;
     DeviceArray<float4> ad_samples;
+    // surface lookups and sampling (drt_capi_surface.cpp): sf_normals = the host scene's vertex normals, float[n_tris][3][3] in tree
+    // order, and sf_order = the load index of every triangle, both made by the first lookup after an upload and dropped with the scene
+    // copy, as the topology labels are; the table and the scratch of a sample call (sf_cdf: n_tris words, sf_blocks: one per workgroup
+    // of the scan, sf_amax: one word), grown on demand and recomputed by every call
+    bool sf_built = false;
+    DeviceArray<float> sf_normals;
+    DeviceArray<int32_t> sf_order;
+    DeviceArray<unsigned long long> sf_cdf, sf_blocks;
+    DeviceArray<uint32_t> sf_amax;
 
     drt_renderer() = default;
     ~drt_renderer() {                          // the members release what they own, on this device
@@ -249,6 +258,8 @@ struct drt_renderer {
         adj_built = false;
         topo_labels.release(); topo_counts.release(); topo_boundary.release();
         topo_built = false;
+        sf_normals.release(); sf_order.release();
+        sf_built = false;
         uploaded_scene = nullptr;
     }
     void free_upscale() {

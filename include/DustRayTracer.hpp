@@ -376,6 +376,24 @@ public:
                       int32_t mode = DRT_TRICAST_FIRST, void *stream = nullptr) {
         drt::check(drt_renderer_triangle_cast(handle, scene.handle, tris, motions, out, n, mode, stream));
     }
+    // new: what lies on the surface at each reference {t, prim, u, v} -- the output of TraceRays and the other queries as it stands --
+    // a drt_surface per reference (drt_renderer_surface_lookup): position, the stored face normal, the interpolated vertex normals
+    // (NOT normalised; `normals`: a device float[n_tris][3][3] in load order, nullptr = the host scene's), uv, albedo and alpha by the
+    // reference's nearest-texel rule, the material's other fields, the load index.  prim outside [0, n_tris): the miss record, zeros
+    // with material = load_index = texture = -1.  Device arrays, refs and out 16-byte aligned, enqueued on `stream`.
+    void SurfaceLookup(const Scene &scene, const drt_hit *refs, drt_surface *out, uint32_t n, const float *normals = nullptr,
+                       void *stream = nullptr) {
+        drt::check(drt_renderer_surface_lookup(handle, scene.handle, refs, normals, out, n, stream));
+    }
+    // new: the inclusive table of integer area weights the samples are drawn from, a device uint64[n_tris] (drt_renderer_surface_weights)
+    void SurfaceWeights(const Scene &scene, uint64_t *cdf, void *stream = nullptr) {
+        drt::check(drt_renderer_surface_weights(handle, scene.handle, cdf, stream));
+    }
+    // new: n references {0, prim, u, v} drawn on the mesh with probability proportional to area, samples first .. first + n - 1 of the
+    // stream `seed` (drt_renderer_sample_surface); they feed SurfaceLookup as they are.  Independent hashes: not stratified.
+    void SampleSurface(const Scene &scene, uint32_t seed, drt_hit *out, uint32_t n, uint32_t first = 0, void *stream = nullptr) {
+        drt::check(drt_renderer_sample_surface(handle, scene.handle, seed, first, out, n, stream));
+    }
     // new: the segments where each query plane dot(n, x) = d cuts the mesh, a drt_plane {n[3], d} (drt_renderer_plane_sections): one
     // drt_section {p[3], prim, q[3], code} per cut triangle in ascending triangle index, p -> q counter-clockwise about n on a closed
     // mesh with outward faces; the miss record is zeros with prim = -1.  Modes (DRT_SECTION_LIST / DRT_SECTION_ANY), segments, counts

@@ -33,8 +33,9 @@ extern "C" {
  * (drt_renderer_nearest_list), the box-overlap entry point (drt_renderer_overlap_boxes), the triangle-overlap entry point
  * (drt_renderer_overlap_triangles), the plane-section entry point (drt_renderer_plane_sections), the intersection-segment entry
  * point (drt_renderer_intersect_triangles), the intersection-curve entry points (drt_tri_edge_adjacency,
- * drt_renderer_chain_intersections), the triangle-distance entry point (drt_renderer_triangle_distance) and the triangle-cast entry
- * point (drt_renderer_triangle_cast) are additions to it */
+ * drt_renderer_chain_intersections), the triangle-distance entry point (drt_renderer_triangle_distance), the triangle-cast entry
+ * point (drt_renderer_triangle_cast) and the surface entry points (drt_renderer_surface_lookup, drt_renderer_surface_weights,
+ * drt_renderer_sample_surface) are additions to it */
 #define DRT_ABI_VERSION 2
 
 typedef enum {
@@ -1086,6 +1087,84 @@ typedef struct drt_tri_hit { float point[3]; float t; float normal[3]; int32_t p
 #define DRT_TRICAST_ANY   1
 int           drt_renderer_triangle_cast(drt_renderer *r, const drt_scene *scene, const drt_tri *tris, const drt_motion *motions,
                                          drt_tri_hit *out, uint32_t n, int32_t mode, void *hip_stream);
+
+/* ---- surface lookups and area-weighted sampling (new; the reference has neither) ----
+ * Every query above answers with a triangle index and two barycentrics.  drt_renderer_surface_lookup turns such a reference into what
+ * lies on the surface there, read from the renderer's device copy of the scene; drt_renderer_sample_surface draws references on the
+ * mesh with probability proportional to area.  Neither traverses the BVH.  Both are stated bit for bit: fp32 with one rounding per
+ * operation, in the order written.
+ *
+ * drt_renderer_surface_lookup.  refs: n drt_hit {t, prim, u, v} (16 bytes, 16-byte aligned) -- the output of drt_renderer_trace_rays
+ * and drt_renderer_list_hits as it stands; t is not read.  out: n drt_surface, 96 bytes, 16-byte aligned, written with six 16-byte
+ * stores.
+ *   valid      0 <= prim < n_tris.  Anything else (a query's miss -1, an index beyond the mesh) gets the miss record: all zero bits
+ *              except material = load_index = texture = -1.
+ *   (u, v)     are used as given: no clamp, outside the triangle every field extrapolates.  w = 1.0f - u - v (Intersection.cu's).
+ *   position   (v0 + u e1) + v e2 per component, of the device copy's v0, e1 = v1 - v0, e2 = v2 - v0: after drt_renderer_refit the
+ *              moved triangle.
+ *   normal     the stored face normal, as is -- not turned, there is no ray; of a zero-area triangle a NaN, which NaN is not specified.
+ *   uv         (w uv0 + u uv1) + v uv2 per component (RayGen.cuh:116).
+ *   albedo,    a material without a texture: its flat albedo, alpha = 1.  Otherwise the reference's getPixel / getAlpha
+ *   alpha      (Texture.cu:33-75): with f = c - floorf(c) per component, x = (int)(f.x width), y = (int)(f.y height), the texel
+ *              y width + x of the renderer's own pool, every texture followed by width + 1 zero texels (uv = 1 or a tiny negative
+ *              one reads them, as the renderer does); albedo = (c / 255)^2 per channel for 3 and 4 channels, (0, 0, 1) for any other
+ *              count; alpha = a / 255 with 4 channels, else 1.  This is what the ALBEDO view and drt_renderer_render_guides show.
+ *   departure  the caller supplies (u, v), so uv can be a NaN or an infinity, which the renderer never meets: a fractional part f
+ *              that fails f >= 0 && f <= 1 is taken as 0 before the conversion.  A finite uv is unaffected; nothing is read outside
+ *              the pool.
+ *   material   the triangle's material id; texture = its albedo_tex, or -1 if that is negative; emissive, roughness,
+ *              refractive_index as drt_scene_add_material_ex set them; flags bit 0 = metallic, bit 1 = transmission.
+ *   shading    (w N0 + u N1) + v N2 of the three vertex normals: NOT normalised and not turned.  normals = NULL: the HOST scene's
+ *              vertex normals (drt_scene_get_triangles), also after a drt_renderer_refit that was given others -- the device keeps only
+ *              their average.  normals != NULL: a device array float[n_tris][3][3] in LOAD order, the array drt_renderer_refit takes
+ *              (4-byte aligned, n_tris * 36 bytes), read through drt_scene_get_triangle_order; used instead and not retained.
+ *   load_index drt_scene_get_triangle_order's entry of prim.
+ * The first lookup after a scene upload uploads the host scene's vertex normals and the load-order table into buffers of its own.
+ *
+ * drt_renderer_surface_weights writes the table the samples are drawn from: cdf, a device uint64[n_tris], 16-byte aligned.
+ *   a_k        c = cross(e1, e2) of the device copy, a = sqrtf((c.x c.x + c.y c.y) + c.z c.z), the correctly rounded sqrt: twice the
+ *              area.  A non-finite a (a NaN or an infinity in the triangle, or an overflow) counts as 0.
+ *   amax       the maximum of a_k.  amax == 0: every q is 0.  Otherwise e = frexp's exponent of amax (amax = m 2^e, 0.5 <= m < 1,
+ *              subnormals included).
+ *   q_k        (uint64_t)ldexp((double)a_k, 35 - e), truncated; the scaling is exact in double.  q_k < 2^36, so no sum below 2^28
+ *              triangles overflows; a triangle smaller than amax 2^-36 has weight 0.
+ *   cdf[k]     q_0 + ... + q_k.  total = cdf[n_tris - 1].  Integers: the same bytes whatever computes them and in whatever order
+ *              (on the device a three-phase scan over blocks of DRT_SURFACE_SCAN_BLOCK triangles; no workgroup waits for another).
+ * A mesh scaled by a power of two has the same table.  n_tris == 0 is a no-op.
+ *
+ * drt_renderer_sample_surface.  Sample k of a call has index i = first + k; first + n <= 2^32.  pcg = the reference's pcg_hash
+ * (Random.cu:6-11).  s = pcg(i ^ pcg(seed)), h1 = pcg(s), h2 = pcg(h1), h3 = pcg(h2), h4 = pcg(h3).
+ *   prim       R = (uint64_t)h1 << 32 | h2, target = the high 64 bits of R total; prim = the smallest k with cdf[k] > target.  A
+ *              triangle of weight 0 is never drawn.  total == 0 (no triangle, or none with an area): the miss record {0, -1, 0, 0}.
+ *   (u, v)     a = h3 >> 8, b = h4 >> 8; if a + b > 2^24 then a = 2^24 - a and b = 2^24 - b; u = a 2^-24, v = b 2^-24.  So u, v >= 0,
+ *              u + v <= 1, and w = 1 - u - v is exact and >= 0.
+ *   record     drt_hit {t = 0, prim, u, v}: it feeds drt_renderer_surface_lookup as it is.
+ * A sample depends on (seed, i) and the scene only: a batch split in two with `first` gives the same records.  The table is computed
+ * again by every call (one pass over the triangles), from the device copy: after drt_renderer_refit the moved mesh is sampled.
+ *
+ * What this is not: the nearest texel only, as the reference has -- no filtering, no mip levels; no normal maps and no tangents;
+ * shading is not normalised; no stratified or blue-noise sampling -- independent hashes; no drt_group_* form and no command line.
+ * Conventions are drt_renderer_trace_rays': the argument checks in that order (the handles, n == 0 is a no-op, NULL refs or out,
+ * alignment, n < 2^31, a pending batch, device memory on the renderer's device -- a normals allocation shorter than n_tris * 36 bytes
+ * and a table shorter than n_tris * 8 are refused where the runtime can tell), hip_stream NULL = the renderer's stream, the call only
+ * enqueues, in order with the other queries (the same event), the scene is uploaded as for rendering -- a scene without a BVH is
+ * refused, but there is no limit of 64 levels: nothing here traverses --, DRT_ERR_INVALID while an
+ * asynchronous batch is pending, legal on a sharded renderer, and the framebuffer, accumulation, sample count, counters, kernel info
+ * and kernel span are not touched. */
+typedef struct drt_surface {
+    float position[3]; int32_t material;      /* material id, -1 = no such triangle                         */
+    float normal[3];   float   alpha;         /* stored face normal, as is;  texel alpha or 1                */
+    float shading[3];  int32_t load_index;    /* interpolated vertex normals, NOT normalised;  triangleOrder */
+    float albedo[3];   int32_t texture;       /* what the ALBEDO view shows;  albedo_tex or -1               */
+    float uv[2];       float roughness; uint32_t flags;   /* bit 0 metallic, bit 1 transmission             */
+    float emissive[3]; float refractive_index;
+} drt_surface;                                /* 96 B */
+#define DRT_SURFACE_SCAN_BLOCK 256
+int           drt_renderer_surface_lookup(drt_renderer *r, const drt_scene *scene, const drt_hit *refs, const float *normals,
+                                          drt_surface *out, uint32_t n, void *hip_stream);
+int           drt_renderer_surface_weights(drt_renderer *r, const drt_scene *scene, uint64_t *cdf, void *hip_stream);   /* device uint64[n_tris] */
+int           drt_renderer_sample_surface(drt_renderer *r, const drt_scene *scene, uint32_t seed, uint32_t first, drt_hit *out,
+                                          uint32_t n, void *hip_stream);
 
 /* ---- first-hit guide buffers and the a-trous denoiser (new; the reference's TODO list, RayGen.cuh:13-21, starts with "DLSS 3.5
  * like features") ----
