@@ -339,6 +339,8 @@ _sig("drt_renderer_triangle_cast", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, C.c_
 _sig("drt_renderer_surface_lookup", C.c_int, _P, _P, _P, _P, _P, C.c_uint32, _P)
 _sig("drt_renderer_surface_weights", C.c_int, _P, _P, _P, _P)
 _sig("drt_renderer_sample_surface", C.c_int, _P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P)
+_sig("drt_renderer_ambient_occlusion", C.c_int, _P, _P, _P, C.c_uint32, _P, _P, _P)
+_sig("drt_debug_ambient_stats", C.c_int, _P, C.c_int32, _P)
 _sig("drt_scene_edge_adjacency", C.c_int, _P, _P, C.c_uint32)
 _sig("drt_renderer_chain_sections", C.c_int, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _P)
 _sig("drt_tri_edge_adjacency", C.c_int, _P, C.c_uint32, _P, C.c_uint32)
@@ -658,6 +660,9 @@ Surface = collections.namedtuple("Surface", "position normal shading uv albedo e
                                             "metallic transmission")
 SurfaceSamples = collections.namedtuple("SurfaceSamples", "prim u v")   # references drawn on the mesh by area (Renderer.sampleSurface)
 SURFACE_SCAN_BLOCK = 256                                                 # drt.h DRT_SURFACE_SCAN_BLOCK
+# cosine-weighted visibility at surface points (Renderer.ambientOcclusion): open -1 = a skipped point; sums = the exact integer record
+AmbientOcclusion = collections.namedtuple("AmbientOcclusion", "open visibility bent sums")
+AO_MAX_SAMPLES = 4096
 SectionList = collections.namedtuple("SectionList", "splits p q prim code")   # every segment where planes cut the mesh, CSR (Renderer.planeSections)
 SECTION_LIST, SECTION_ANY = 0, 1                                        # drt.h DRT_SECTION_*
 CutList = collections.namedtuple("CutList", "splits p q prim code")     # every segment where query triangles cut the mesh, CSR (Renderer.intersectTriangles)
@@ -1674,6 +1679,124 @@ class Renderer:
         stream = torch.cuda.current_stream(dev).cuda_stream
         _check(_lib.drt_renderer_surface_weights(self._h, scene._h, out.data_ptr() if out.numel() else None, stream))
         return out if as_torch else out.cpu().numpy().view(np.uint64)
+
+    def ambientOcclusion(self, scene, refs=None, points=None, normals=None, samples=64, max_dist=float("inf"), bias=0.001, seed=0, first=0,
+                         side=1.0, facing=None):
+        """How much of the hemisphere above surface points is open (drt_renderer_ambient_occlusion): ambient occlusion, sky-view
+        factor, accessibility.  Per point `samples` (1 .. 4096) occlusion rays from point + normal * bias in the renderer's bounce
+        directions normalize(normal + unit-sphere draw), none longer than max_dist (inf = sky visibility); alpha cut-outs are seen
+        through as in occluded.  Returns AmbientOcclusion(open int32 [..] -- the number of open samples, -1 = a skipped point --,
+        visibility float32 [..] = open / samples (NaN where skipped), bent float32 [.., 3] = sums / (65536 max(open, 1)): the mean open
+        direction, not normalised, sums int32 [.., 3]: the exact integer record), of the points' shape.  The record is integer sums:
+        the same bytes on every run.
+        refs: anything with .prim, .u and .v -- the results of traceRays, nearest, sampleSurface ... -- whose position and face normal
+        surface() looks up; a reference outside the mesh (a miss) is skipped.  Or points= and normals= [.., 3] float32, packed as
+        given: pass unit normals for a cosine-weighted answer.  side (a scalar or [..]) multiplies the normals: -1 looks below the
+        surface.  facing= directions [.., 3]: every normal is turned against its direction by the renderer's rule, negated where
+        dot(normal, direction) > 0 -- pass the rays that found the points.  max_dist and bias: scalars or [..]; a point whose max_dist
+        is negative or a NaN is skipped.  Sample streams are (seed, first + index): first= continues a batch, first + N <= 2^32.
+        No distance falloff, no weighting beyond the cosine of the draw, independent hashes -- not stratified --, no indirect light
+        (radiance does that), no filtering across points; the absolute bias and the triangle test's 1e-6 apply as in traceRays.
+        Device tensors in, device tensors out (enqueued on the current torch stream); numpy in, numpy out."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+
+        def bad(msg):
+            return DrtError(ERR_INVALID, "ambientOcclusion: " + msg)
+
+        samples, seed, first = int(samples), int(seed), int(first)
+        if not 1 <= samples <= AO_MAX_SAMPLES:
+            raise bad("samples %d: 1 .. 4096 expected" % samples)
+        if not 0 <= seed < 1 << 32 or not 0 <= first < 1 << 32:
+            raise bad("seed and first in [0, 2^32) expected")
+        if (refs is None) == (points is None):
+            raise bad("refs, or points= and normals=, expected")
+        if refs is not None:
+            if normals is not None:
+                raise bad("normals= come with points=; the normals of refs are the mesh's")
+            if not all(hasattr(refs, f) for f in ("prim", "u", "v")):
+                raise bad("refs: something with .prim, .u and .v expected")
+            lead = refs.prim
+        else:
+            if normals is None:
+                raise bad("points= come with normals=")
+            lead = points
+        if not (isinstance(lead, np.ndarray) or torch.is_tensor(lead)):
+            raise bad("a numpy array or a torch tensor expected")
+        from_numpy = isinstance(lead, np.ndarray)
+        shape = tuple(lead.shape) if refs is not None else tuple(lead.shape[:-1])
+
+        def vectors(x, name):                    # [.., 3] float32 of the points' shape, still where it was given
+            if isinstance(x, np.ndarray) != from_numpy or not (isinstance(x, np.ndarray) or torch.is_tensor(x)):
+                raise bad("%s: a %s expected, as the points are" % (name, "numpy array" if from_numpy else "torch tensor"))
+            if x.dtype != (np.float32 if from_numpy else torch.float32):
+                raise bad("%s: dtype %s, float32 expected" % (name, x.dtype))
+            if tuple(x.shape) != shape + (3,):
+                raise bad("%s: shape %s, %s expected" % (name, tuple(x.shape), shape + (3,)))
+            if not from_numpy and x.device != dev:
+                raise bad("%s: on %s, the renderer is on %s" % (name, x.device, dev))
+            return x
+
+        def per_point(x, name):                  # a scalar, or [..] float32 of the points' shape
+            if isinstance(x, (int, float, np.floating, np.integer)):
+                return float(x)
+            if isinstance(x, np.ndarray) or torch.is_tensor(x):
+                if tuple(x.shape) != shape:
+                    raise bad("%s: shape %s, a scalar or %s expected" % (name, tuple(x.shape), shape))
+                if not isinstance(x, np.ndarray) and x.device != dev:
+                    raise bad("%s: on %s, the renderer is on %s" % (name, x.device, dev))
+                return x
+            raise bad("%s: a scalar, a numpy array or a torch tensor expected" % name)
+
+        if refs is None:
+            points, normals = vectors(points, "points"), vectors(normals, "normals")
+        if facing is not None:
+            facing = vectors(facing, "facing")
+        max_dist, bias, side = per_point(max_dist, "max_dist"), per_point(bias, "bias"), per_point(side, "side")
+        n = 1
+        for extent in shape:
+            n *= int(extent)
+        if first + n > 1 << 32:
+            raise bad("first + N must not exceed 2^32")
+
+        def on_device(x, tail=()):               # (after every check: nothing touches the device for a bad argument)
+            if isinstance(x, float):
+                return x
+            if isinstance(x, np.ndarray):
+                x = torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+            return x.to(torch.float32).reshape((n,) + tail)
+
+        if refs is not None:
+            ref3 = SurfaceSamples(*(torch.from_numpy(np.ascontiguousarray(x)).to(dev) if isinstance(x, np.ndarray) else x
+                                    for x in (refs.prim, refs.u, refs.v)))
+            found = self.surface(scene, ref3)
+            pos, nrm = found.position.reshape(n, 3), found.normal.reshape(n, 3)
+            missed = found.material.reshape(n) < 0
+        else:
+            pos, nrm, missed = on_device(points, (3,)), on_device(normals, (3,)), None
+        side = on_device(side)
+        nrm = nrm * (side if isinstance(side, float) else side[:, None])
+        if facing is not None:
+            f = on_device(facing, (3,))
+            against = ((nrm[:, 0] * f[:, 0] + nrm[:, 1] * f[:, 1]) + nrm[:, 2] * f[:, 2]) > 0
+            nrm = torch.where(against[:, None], -nrm, nrm)
+        packed = torch.empty((n, 8), dtype=torch.float32, device=dev)                       # drt_ao_point {p, max_dist, n, bias}
+        packed[:, 0:3], packed[:, 4:7] = pos, nrm
+        packed[:, 3], packed[:, 7] = on_device(max_dist), on_device(bias)
+        if missed is not None:
+            packed[:, 3] = torch.where(missed, torch.full_like(packed[:, 3], -1.0), packed[:, 3])
+        out = torch.empty((n, 4), dtype=torch.int32, device=dev)                            # drt_ao_result {open, bent[3]}
+        if n:
+            params = (C.c_uint32 * 4)(samples, seed, first, 0)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(_lib.drt_renderer_ambient_occlusion(self._h, scene._h, packed.data_ptr(), n, C.addressof(params), out.data_ptr(), stream))
+        n_open, sums = out[:, 0], out[:, 1:4]
+        visibility = torch.where(n_open < 0, torch.full((n,), float("nan"), dtype=torch.float32, device=dev), n_open.to(torch.float32) / samples)
+        bent = sums.to(torch.float32) / (65536.0 * n_open.clamp(min=1).to(torch.float32))[:, None]
+        res = AmbientOcclusion(n_open.reshape(shape), visibility.reshape(shape), bent.reshape(shape + (3,)), sums.reshape(shape + (3,)))
+        if from_numpy:
+            return AmbientOcclusion(*(x.cpu().numpy().copy() for x in res))
+        return res
 
     def selfIntersections(self, scene, positions=None):
         """Where the scene's mesh cuts itself: int32 [P, 2], the pairs i < j of triangle indices (tree order, as every query reports

@@ -1,4 +1,4 @@
-// renderer_state.hpp -- what the translation units of the C ABI share (drt_capi.cpp, drt_capi_filters.cpp, drt_capi_adaptive.cpp, drt_capi_section.cpp, drt_capi_contour.cpp, drt_capi_topology.cpp, drt_capi_intersect.cpp, drt_capi_surface.cpp): the renderer's state,
+// renderer_state.hpp -- what the translation units of the C ABI share (drt_capi.cpp, drt_capi_filters.cpp, drt_capi_adaptive.cpp, drt_capi_section.cpp, drt_capi_contour.cpp, drt_capi_topology.cpp, drt_capi_intersect.cpp, drt_capi_surface.cpp, drt_capi_ambient.cpp): the renderer's state,
 // the owners of its device memory, pinned memory and events, error reporting, the steps several entry points take.  Not exported.
 #pragma once
 #include "../../include/drt.h"
@@ -236,6 +236,11 @@ struct drt_renderer {
     DeviceArray<int32_t> sf_order;
     DeviceArray<unsigned long long> sf_cdf, sf_blocks;
     DeviceArray<uint32_t> sf_amax;
+    // ambient occlusion (drt_capi_ambient.cpp): the 64-bit claim heads of kernel_ambient.hip (the tile count of a call can pass 2^32;
+    // kRqShards heads, ambient.hpp's kAoHeadStride words apart, zeroed on the stream before every launch) -- the HBM stack is rq_stack --
+    // and the two counters of the counting build (drt_debug_ambient_stats)
+    DeviceArray<unsigned long long> ao_heads, ao_stats;
+    bool ao_stats_on = false;
 
     drt_renderer() = default;
     ~drt_renderer() {                          // the members release what they own, on this device

@@ -394,6 +394,16 @@ public:
     void SampleSurface(const Scene &scene, uint32_t seed, drt_hit *out, uint32_t n, uint32_t first = 0, void *stream = nullptr) {
         drt::check(drt_renderer_sample_surface(handle, scene.handle, seed, first, out, n, stream));
     }
+    // new: ambient occlusion -- for each drt_ao_point {p, max_dist, n, bias} `samples` occlusion rays from p + n * bias in the renderer's
+    // bounce directions normalize(n + unit-sphere draw), none longer than max_dist, and per point a drt_ao_result {open, bent[3]}: the
+    // number of open samples and the integer sum of their directions * 65536 (drt_renderer_ambient_occlusion).  Pass unit normals for a
+    // cosine-weighted answer; max_dist < 0 or NaN skips a point ({-1, 0, 0, 0}).  Sample streams are (seed, first + index): `first`
+    // continues a batch.  Device arrays, 16-byte aligned, enqueued on `stream`; no falloff, not stratified.
+    void AmbientOcclusion(const Scene &scene, const drt_ao_point *points, drt_ao_result *out, uint32_t n, uint32_t samples = 64,
+                          uint32_t seed = 0, uint32_t first = 0, void *stream = nullptr) {
+        const drt_ao_params params = { samples, seed, first, 0u };
+        drt::check(drt_renderer_ambient_occlusion(handle, scene.handle, points, n, &params, out, stream));
+    }
     // new: the segments where each query plane dot(n, x) = d cuts the mesh, a drt_plane {n[3], d} (drt_renderer_plane_sections): one
     // drt_section {p[3], prim, q[3], code} per cut triangle in ascending triangle index, p -> q counter-clockwise about n on a closed
     // mesh with outward faces; the miss record is zeros with prim = -1.  Modes (DRT_SECTION_LIST / DRT_SECTION_ANY), segments, counts

@@ -34,8 +34,8 @@ extern "C" {
  * (drt_renderer_overlap_triangles), the plane-section entry point (drt_renderer_plane_sections), the intersection-segment entry
  * point (drt_renderer_intersect_triangles), the intersection-curve entry points (drt_tri_edge_adjacency,
  * drt_renderer_chain_intersections), the triangle-distance entry point (drt_renderer_triangle_distance), the triangle-cast entry
- * point (drt_renderer_triangle_cast) and the surface entry points (drt_renderer_surface_lookup, drt_renderer_surface_weights,
- * drt_renderer_sample_surface) are additions to it */
+ * point (drt_renderer_triangle_cast), the surface entry points (drt_renderer_surface_lookup, drt_renderer_surface_weights,
+ * drt_renderer_sample_surface) and the ambient-occlusion entry point (drt_renderer_ambient_occlusion) are additions to it */
 #define DRT_ABI_VERSION 2
 
 typedef enum {
@@ -1165,6 +1165,68 @@ int           drt_renderer_surface_lookup(drt_renderer *r, const drt_scene *scen
 int           drt_renderer_surface_weights(drt_renderer *r, const drt_scene *scene, uint64_t *cdf, void *hip_stream);   /* device uint64[n_tris] */
 int           drt_renderer_sample_surface(drt_renderer *r, const drt_scene *scene, uint32_t seed, uint32_t first, drt_hit *out,
                                           uint32_t n, void *hip_stream);
+
+/* ---- ambient occlusion (new; cosine-weighted visibility at surface points -- the reference shades only along its paths) ----
+ * How much of the hemisphere above a surface point is open: ambient occlusion, sky-view factor, accessibility, and the bent normal.
+ * For every point S occlusion rays are made where they are used, in the renderer's own bounce directions, traced by
+ * drt_renderer_occluded's traversal and reduced per point; no ray is stored.  Stated bit for bit: fp32 with one rounding per
+ * operation, in the order written; dot(a, b) = a.x b.x + a.y b.y + a.z b.z, left to right (helper_math.cuh:1264);
+ * normalize(v) = v * (1.0f / sqrtf(dot(v, v))) (helper_math.cuh:1325, :78-81), division and sqrtf correctly rounded.
+ *
+ * A query point is drt_ao_point {p[3], max_dist, n[3], bias}: 32 bytes, the layout of drt_ray, 16-byte aligned.  Per call
+ * drt_ao_params {samples, seed, first, flags}: samples = S with 1 <= S <= 4096; first continues a stream as
+ * drt_renderer_sample_surface's does, first + n <= 2^32; flags must be 0.  pcg = the reference's pcg_hash (Random.cu:6-11).
+ * For point i of the call and sample j in [0, S):
+ *   h          pcg((first + i) ^ pcg(seed))
+ *   state      pcg(j ^ h)
+ *   fuzz       randomUnitSphereVec3(state) (Random.cu:50-58): candidates ((float)state / 2^32) * 2 - 1 per component after
+ *              state = pcg(state), x, then y, then z, normalised, until len * len < 1 with len = sqrtf(dot(c, c)); with the renderer's
+ *              guard: the 1024th candidate is kept whatever its length.  The renderer's diffuse bounce draws it the same way.
+ *   d          normalize(n + fuzz) (RayGen.cuh:133-134)
+ *   o          p + n * bias per component (RayGen.cuh:121 with bias for 0.001)
+ *   occluded   iff drt_renderer_occluded says so for the ray {o, tmin = 0, d, tmax = max_dist}: the same traversal, the root skipped
+ *              if its entry distance e has e < 0 || e > tmax, a child pushed iff e >= 0 && !(e > tmax), a triangle counts iff
+ *              t > tmin && t < tmax && AnyHit -- alpha cut-outs are seen through as there.  Otherwise the sample is open.
+ * n is used as given: pass a unit normal for a cosine-weighted answer (fuzz lies on the unit sphere, so d is then distributed as the
+ * cosine of its angle to n).  No guard is added: a NaN anywhere in o or d hits nothing, as in drt_renderer_occluded, and the sample
+ * counts as open; n + fuzz = 0 makes d a NaN.
+ *
+ * The answer per point is drt_ao_result {open, bent[3]}: 16 bytes, 16-byte aligned, int32 each.
+ *   open       the number of open samples.
+ *   bent[k]    the sum over the open samples of (int32_t)(d[k] * 65536.0f): the product is exact, the cast truncates.  A product that
+ *              is a NaN or not below 2^31 in magnitude adds 0 (the cast has no value there).  |d[k]| <= 1 up to rounding, so
+ *              |bent[k]| <= 4096 * 65536 = 2^28: it cannot overflow.  bent / (65536 open) is the mean open direction, the bent normal,
+ *              not normalised.
+ *   skipped    a point with !(max_dist >= 0) (negative or a NaN) costs no rays; its record is {-1, 0, 0, 0}.  max_dist = 0: every
+ *              sample is open (t < 0 never holds).  max_dist = +inf: sky visibility.
+ * Both fields are integer sums, so a record is the same bytes whatever order, tiling or hardware computes it: that is why bent is not a
+ * float.  A record depends on (seed, first + i, S), its point and the scene only: a batch split in two with `first` gives the same
+ * records.  After drt_renderer_refit the moved mesh occludes.
+ *
+ * On the device the work unit is a tile of 64 lanes: for S >= 64 samples [64 t, min(64 t + 64, S)) of one point; for S in {1, 2, 4, 8,
+ * 16, 32} 64 / S consecutive points with S lanes each; for any other S < 64 one point with idle lanes.  The tile count is a 64-bit
+ * number.  One lane per point writes the whole record with one 16-byte store (S <= 64) or adds to it with integer atomics (S > 64); a
+ * pass before the tracing kernel writes the skipped points' records.  There are no floating-point atomics.
+ *
+ * What this is not: no distance falloff and no weighting beyond the cosine of the draw; no stratified or low-discrepancy directions --
+ * independent hashes; no indirect light -- drt_renderer_radiance does that; no filtering across points; the absolute bias and the ray
+ * family's 1e-6 apply as in drt_renderer_trace_rays (the "working range" paragraph above says what that means for small meshes); no
+ * drt_group_* form and no command line.
+ * Conventions are drt_renderer_occluded's, with every argument checked before any device work, in this order: the handles and params,
+ * samples 0 or > 4096, flags != 0, n == 0 is a no-op, NULL pts or out, 16-byte alignment, n < 2^31, first + n <= 2^32, a scene without
+ * a BVH, a pending asynchronous batch (DRT_ERR_INVALID each); then pts and out must be device memory on the renderer's device.
+ * hip_stream NULL = the renderer's stream; the call only enqueues, in order with the other queries (the same event); the scene is
+ * uploaded as for rendering; DRT_ERR_UNSUPPORTED for trees deeper than 64 levels; legal on a sharded renderer; the framebuffer,
+ * accumulation, sample count, counters, kernel info and kernel span are not touched.
+ * drt_debug_ambient_stats switches the tracing kernel's counting build on (enable != 0, counters zeroed) or off and reads, after the
+ * queries in flight, {trips of the waves' traversal loops, lanes that took a step in them}: lane utilisation = out[1] / (64 out[0]).
+ * Results do not change. */
+typedef struct drt_ao_point  { float p[3]; float max_dist; float n[3]; float bias; } drt_ao_point;       /* 32 B */
+typedef struct drt_ao_params { uint32_t samples; uint32_t seed; uint32_t first; uint32_t flags; } drt_ao_params;
+typedef struct drt_ao_result { int32_t open; int32_t bent[3]; } drt_ao_result;                           /* 16 B */
+int           drt_renderer_ambient_occlusion(drt_renderer *r, const drt_scene *scene, const drt_ao_point *pts, uint32_t n,
+                                             const drt_ao_params *params, drt_ao_result *out, void *hip_stream);
+int           drt_debug_ambient_stats(drt_renderer *r, int32_t enable, uint64_t out[2]);
 
 /* ---- first-hit guide buffers and the a-trous denoiser (new; the reference's TODO list, RayGen.cuh:13-21, starts with "DLSS 3.5
  * like features") ----

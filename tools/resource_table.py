@@ -49,6 +49,9 @@ def pretty(name):
     m = re.search(r"intersect_kernelILb(\d)E", name)
     if m:
         return "intersect_kernel<%s>" % ("FILL" if m.group(1) == "1" else "COUNT")
+    m = re.search(r"ambient_kernelILb(\d)E", name)
+    if m:
+        return "ambient_kernel<%s>" % ("counting build" if m.group(1) == "1" else "plain")
     m = re.search(r"\d+(\w+_kernel)", name)
     return m.group(1) if m else name
 
@@ -59,7 +62,7 @@ def main():
     for src, extra in (("kernel_path_pool.hip", ()), ("kernel_path_pool.hip", ("-DDRT_POOL_EXT_TU",)), ("kernel_wave_queue.hip", ()),
                        ("render_kernels.hip", ()), ("kernel_bvh_build.hip", ()), ("kernel_sphere_cast.hip", ()), ("kernel_near_list.hip", ()),
                        ("kernel_overlap.hip", ()), ("kernel_tri_overlap.hip", ()), ("kernel_intersect.hip", ()), ("kernel_tri_distance.hip", ()),
-                       ("kernel_tri_cast.hip", ()), ("kernel_surface.hip", ())):
+                       ("kernel_tri_cast.hip", ()), ("kernel_surface.hip", ()), ("kernel_ambient.hip", ())):
         for r in remarks(src, extra):
             if "VGPRs" in r and not (extra and "ILi" in r["name"] and int(re.search(r"ILi(\d+)E", r["name"]).group(1)) < 16):
                 rows.append(r)
