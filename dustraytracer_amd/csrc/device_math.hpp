@@ -213,12 +213,17 @@ DRT_DEV bool tri_intersect(const Ray &ray, f3 v0, f3 e1, f3 e2, float &t_out, f3
 // Same test, straight-line: every quantity is computed, the four rejections are combined at the end.
 // A rejected lane may have divided by a tiny or zero det; its u, v, t are then garbage and never used.
 // NaN behaves as in the branchy form: comparisons with NaN are false, so only `t > eps` rejects it.
+// GUARDED = false: the caller knows |det| <= 2^99 for this lane and this triangle (pool_index.hpp pool_safe_dir), or det is
+// NaN: the refined v_rcp_f32 alone -- the quotient inside the range, NaN for NaN, and a NaN t is rejected whatever its payload.
+template <bool GUARDED = true>
 DRT_DEV bool tri_intersect_flat(const Ray &ray, f3 v0, f3 e1, f3 e2, float &t, float &u, float &v) {
     f3 pvec = cross(ray.dir, e2);
     float det = dot(e1, pvec);
     // det > -eps && det < eps  <=>  |det| < eps (NaN: false either way): one compare, the absolute value is an operand modifier
     int ok = !(__builtin_fabsf(det) < DRT_TRIANGLE_EPSILON);
-    float inv_det = exact_rcp_not_tiny(det);          // !ok covers |det| < 1e-6: whatever comes back there is not used
+    float inv_det;                                     // !ok covers |det| < 1e-6: whatever comes back there is not used
+    if (GUARDED) inv_det = exact_rcp_not_tiny(det);
+    else { const float r = __builtin_amdgcn_rcpf(det); inv_det = __builtin_fmaf(__builtin_fmaf(-det, r, 1.0f), r, r); }
     f3 tvec = ray.orig - v0;
     u = inv_det * dot(tvec, pvec);
     f3 qvec = cross(tvec, e1);

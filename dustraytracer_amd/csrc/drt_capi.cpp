@@ -24,6 +24,7 @@
 #include "section.hpp"
 #include "bvh_build_device.hpp"
 #include "png_decode.hpp"
+#include "pool_index.hpp"
 
 using namespace drt;
 
@@ -78,6 +79,14 @@ static int copy_scene(drt_renderer *r, const drt_scene *scene) {
     r->scene_has_alpha = ps.any_alpha_texture;
     r->leaves_ascending = section_leaves_ascending(ps);
     path_pool_leaf_classes(ps.leaves, r->pool_t_class);
+    {   // the T step's reciprocal guard is decided per batch from the largest |edge component| (pool_index.hpp); NaN must not hide in a max
+        float max_edge = 0.0f;
+        bool finite = true;
+        for (const TriHot &t : ps.tri_hot)
+            for (int c = 0; c < 3; c++)
+                for (const float e : { t.e1[c], t.e2[c] }) { finite = finite && std::isfinite(e); max_edge = std::max(max_edge, std::fabs(e)); }
+        r->pool_safe_dir = finite ? pool_safe_dir(max_edge) : 0.0f;
+    }
     if (r->tune.t_class_set) std::memcpy(r->pool_t_class, r->tune.t_class, sizeof r->pool_t_class);
     if (r->tune.pool_verbose) std::fprintf(stderr, "path_pool leaf classes: %u %u %u\n", r->pool_t_class[0], r->pool_t_class[1], r->pool_t_class[2]);
     r->uploaded_scene = scene;
@@ -742,7 +751,7 @@ static int render_batch_impl(drt_renderer *r, const drt_camera *cam, const drt_s
             }
             unsigned int *const queue_head = r->tile_counter.ptr + (size_t)(r->counters_used++) * kQueueHeadBlockWords;
             if (choice.family == Tracer::path_pool)
-                HIP_TRY(launch_path_pool(r->view, fp, r->bvh_depth, choice, r->pool_t_class, r->tune, r->pool_scratch, queue_head, r->samples.ptr, launch_status,
+                HIP_TRY(launch_path_pool(r->view, fp, r->bvh_depth, choice, r->pool_t_class, r->pool_safe_dir, r->tune, r->pool_scratch, queue_head, r->samples.ptr, launch_status,
                                          r->num_cus, r->stream, &r->shape));
             else
                 HIP_TRY(launch_wave_queue(r->view, fp, r->bvh_depth, choice, r->tune, queue_head, r->samples.ptr, r->num_cus, r->stream, &r->shape, r->wq_cache));
@@ -1280,6 +1289,7 @@ int drt_renderer_refit(drt_renderer *r, const drt_scene *scene, const float *pos
     a.leaves = r->rf_leaves.ptr; a.n_leaves = (uint32_t)r->rf_leaves.count;
     a.levels = r->rf_levels.ptr; a.height_begin = r->rf_height_begin.ptr;
     a.root_box = r->rf_out.ptr; a.error = reinterpret_cast<unsigned int *>(r->rf_out.ptr + 6);
+    r->pool_safe_dir = 0.0f;                     // the edges are rewritten on the device: path_pool keeps its guarded T loop until the scene is uploaded again
     HIP_TRY(launch_refit(a, r->rf_heights, r->rf_top_nodes, s, &r->rf_launches));
     HIP_TRY(hipEventRecord(r->ev_rf_stop, s));
     float out[8];

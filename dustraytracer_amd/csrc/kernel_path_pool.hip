@@ -44,6 +44,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 #include <utility>
 
 #include "device_access.hpp"
@@ -195,6 +196,7 @@ struct PoolParams {
     float4 *aux_next;          // HBM, [workgroup][path][2]: material-model builds with sunlight: what B decided about the continuation ray, kept across the shadow traversal
     unsigned int *status;      // device word: != 0 after an aborted launch
     unsigned long long *stats; // STATS build: per queue {batches, lanes, ticks} (3 x kNQ), then claim ticks, idle polls, lost claims, wave ticks
+    float t_safe_dir;          // a ray with no |direction component| above this keeps |det| <= 2^99 on every staged triangle (pool_index.hpp pool_safe_dir); 0: none does
 };
 
 // FLAGS: 1 = statistics, 2 = sunlight (a shadow ray per shaded hit, RayGen.cuh:124-128), 4 = alpha cut-outs (AnyHit.cuh:8-28),
@@ -732,6 +734,7 @@ __global__ __launch_bounds__(pool_max_threads(FLAGS)) __attribute__((amdgpu_wave
             }
         } else if (q >= QT0 && q < QB) {
             // ============ T: the triangles of one leaf, two per step (Intersection.cu:4-36, BVHTraversal.cuh:46-57) ============
+            const float k_t_safe_dir = PA().t_safe_dir;              // (scalar load, in flight with the state's LDS loads)
             Ray ray = make_ray(mk3(0, 0, 0), mk3(0, 0, 1));
             float hit_t = FLT_MAX;
             uint32_t hit_prim = 0, meta = 0;
@@ -784,6 +787,21 @@ __global__ __launch_bounds__(pool_max_threads(FLAGS)) __attribute__((amdgpu_wave
                 // (kScenePad).  (Not advancing on a lane's last step instead costs a compare per step: measured 0.3-0.6 % slower.)
                 int left = end - cur;                                     // triangles still to test (<= 0: through)
                 uint32_t addr = lds_hot + __umul24((uint32_t)cur, 48u);
+                // The reciprocal's range guard, decided once for the batch: a lane whose ray has no direction
+                // component above PoolParams::t_safe_dir cannot see |det| > 2^99 on any staged triangle -- its own leaf's, the next
+                // leaf's, the zeroed pad (pool_index.hpp pool_safe_dir has the bound) -- so when every lane of the batch is such a
+                // lane the loop runs with the refined v_rcp_f32 alone: per triangle one compare, one exec-mask save and one branch
+                // fewer.  (A NaN component is dropped by v_max: such a lane may count as safe, its det is NaN, and NaN in gives NaN
+                // out on both paths.)  The statistics builds keep the one loop they count, and so do the sunlight builds: a second
+                // copy of a loop that holds the shadow ray's exit and the alpha test cost them 5 VGPRs and SGPR spills.
+                bool all_safe = false;
+                if (!STATS && !SUN) {
+                    const float dir_max = fmaxf(fmaxf(__builtin_fabsf(ray.dir.x), __builtin_fabsf(ray.dir.y)), __builtin_fabsf(ray.dir.z));
+                    all_safe = pp_ballot(active && !(dir_max <= k_t_safe_dir)) == 0;
+                }
+                // the loop, with the guard (a batch with a lane that is not safe; every statistics build) or without it
+                auto t_loop = [&](auto guard) {
+                constexpr bool GUARDED = decltype(guard)::value;
                 for (;;) {
                     const bool go = left > 0;
                     if (pp_ballot(go) == 0) break;
@@ -792,8 +810,8 @@ __global__ __launch_bounds__(pool_max_threads(FLAGS)) __attribute__((amdgpu_wave
                     // (fetching the next pair while this one is tested was measured: 80 VGPRs, cornell -4 %, room -2.6 %)
                     const TriTest ta = fetch_tri_at(addr), tb = fetch_tri_at(addr + 48u);
                     float t0, u0, v0, t1, u1, v1;
-                    const bool h0 = tri_intersect_flat(ray, ta.v0, ta.e1, ta.e2, t0, u0, v0) & go;
-                    const bool h1 = tri_intersect_flat(ray, tb.v0, tb.e1, tb.e2, t1, u1, v1) & two;
+                    const bool h0 = tri_intersect_flat<GUARDED>(ray, ta.v0, ta.e1, ta.e2, t0, u0, v0) & go;
+                    const bool h1 = tri_intersect_flat<GUARDED>(ray, tb.v0, tb.e1, tb.e2, t1, u1, v1) & two;
                     const int i = cur, j = cur + 1;
                     if (SUN && shadow) {                                  // RayTest: any accepted hit ends the traversal (:105-117)
                         const bool occ0 = h0 && (!ALPHA || alpha_test(i, mk3(1.0f - u0 - v0, u0, v0)));
@@ -809,6 +827,9 @@ __global__ __launch_bounds__(pool_max_threads(FLAGS)) __attribute__((amdgpu_wave
                     const int step = go ? 2 : 0;
                     cur += step; left -= step; addr += (uint32_t)step * 48u;
                 }
+                };
+                if (all_safe) t_loop(std::false_type{});
+                else t_loop(std::true_type{});
             }
             if (active) {
                 if (SUN && occluded) { meta |= kOccluded; if (!HBM) st1(meta_at(id), meta); }      // (hbm-scene: store_trav writes meta)
@@ -1159,7 +1180,7 @@ bool path_pool_fits(const SceneView &sc, int bvh_depth, size_t scene_lds_bytes, 
            (scene_lds_bytes <= kLdsSceneBytes && pool_layout(256u, 256u, stack_entries, pool_scene_bytes(sc), 0u, (uint32_t)kNQ).total <= 160u * 1024u);
 }
 
-hipError_t launch_path_pool(const SceneView &sc, const FrameParams &fp, int bvh_depth, const TracerChoice &choice, const uint32_t t_class[3], const Tuning &tune,
+hipError_t launch_path_pool(const SceneView &sc, const FrameParams &fp, int bvh_depth, const TracerChoice &choice, const uint32_t t_class[3], float t_safe_dir, const Tuning &tune,
                             PoolScratch &scratch, unsigned int *sample_counter, void *samples, unsigned int *status, int num_cus,
                             hipStream_t stream, LaunchShape *shape) {
     if (fp.width == 0 || fp.local_rows == 0 || fp.n_frames == 0) return hipSuccess;
@@ -1267,6 +1288,7 @@ hipError_t launch_path_pool(const SceneView &sc, const FrameParams &fp, int bvh_
     pp.n_fuse_loop = (uint32_t)std::max(1, tune.n_fuse_loop); pp.n_fuse_min = (uint32_t)std::max(1, std::min(tune.n_fuse_min, 64));
     pp.cold_in_lds = cold_bytes > 0 ? 1u : 0u;
     pp.dir_tries = (uint32_t)std::max(1, tune.dir_tries);
+    pp.t_safe_dir = t_safe_dir;
     pp.status = status; pp.stats = tune.stats;
     // one pool fills with P samples at once: never more workgroups than that leaves work for.  When the caller keeps several
     // launches in flight (drt_renderer_set_frames_in_flight) each gets its share of the workgroup slots, so that they run side

@@ -77,7 +77,8 @@ constexpr int kPoolSampleShards = DRT_SAMPLE_SHARDS, kPoolSampleShardStride = 32
 bool path_pool_fits(const SceneView &scene, int bvh_depth, size_t scene_lds_bytes, bool hbm_scene);
 void path_pool_leaf_classes(const std::vector<LeafRange> &leaves, uint32_t out[3]);
 struct PoolScratch { void *aux = nullptr, *aux_slot = nullptr, *aux_light = nullptr, *aux_next = nullptr, *aux_stack = nullptr; size_t slots = 0, next_slots = 0, stack_slots = 0; };     // HBM part of the path state, owned by the renderer
-hipError_t launch_path_pool(const SceneView &scene, const FrameParams &frame, int bvh_depth, const TracerChoice &choice, const uint32_t t_class[3], const Tuning &tune,
+// t_safe_dir: pool_safe_dir (pool_index.hpp) of the largest |edge component| among the scene's triangles as they stand in device memory; 0 when that is not known.
+hipError_t launch_path_pool(const SceneView &scene, const FrameParams &frame, int bvh_depth, const TracerChoice &choice, const uint32_t t_class[3], float t_safe_dir, const Tuning &tune,
                             PoolScratch &scratch, unsigned int *sample_counter, void *samples, unsigned int *status, int num_cus, hipStream_t stream, LaunchShape *shape);
 
 // debug: d_out2[0] += #floats in [first_bits, first_bits+count) where exact_rcp != 1.0f/x (which 0) or exact_sqrt != sqrtf (which 1),

@@ -132,6 +132,7 @@ struct drt_renderer {
     drt::WaveQueueCache wq_cache;             // measured choice among wave_queue's launch packagings
     drt::PoolScratch pool_scratch;
     uint32_t pool_t_class[3] = { 0, 0, 0 };   // leaf-size classes of the uploaded scene (path_pool's T queues)
+    float pool_safe_dir = 0.0f;               // pool_safe_dir (pool_index.hpp) of the uploaded triangles' largest |edge component|; 0 once a refit has rewritten them on the device
     bool scene_has_alpha = false;
     int vote_node = 12, vote_shade = 44, vote_dir = 4, vote_spec = 8;
     int leaf_chain = -1;                              // DRT_LEAF_CHAIN: -1 = by tree depth (<= 4 levels), 0 / 1 = forced

@@ -132,7 +132,8 @@ def census(flags, keep=None):
     table = collections.defaultdict(lambda: collections.Counter())
     sites = collections.defaultdict(set)
     for (addr, mn), st in zip(insts, stacks):
-        frames = [(st[i], st[i + 1]) for i in range(0, len(st) - 1, 2)]      # (function, file:line:col), innermost first
+        # (function, file:line:col), innermost first; a template's arguments are not part of the name (tri_intersect_flat<true>)
+        frames = [(st[i].split("<")[0], st[i + 1]) for i in range(0, len(st) - 1, 2)]
         outer_line = 0
         for fn, loc in frames:                                              # outermost frame inside the kernel source
             f, l = loc.rsplit(":", 2)[0:2]
