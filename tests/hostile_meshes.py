@@ -275,9 +275,9 @@ def aimed_boxes(g, kind, twin, seed, per=6):
     return np.concatenate([ov.pack(_f32(center), _f32(half), _f32(rot)), straddle]).astype(np.float32)
 
 
-def aimed_triangles(g, kind, twin, seed, per=6):
-    """Query triangles [N, 3, 3]: small ones (up to 1 % of the extent) around points of the thin triangles' segments, every fourth
-    one itself a segment; the thin triangles themselves; and triangles through the centroid of each duplicate pair."""
+def aimed_triangle_parts(g, kind, twin, seed, per=6):
+    """The three parts of aimed_triangles, each [n, 3, 3] float32: the small triangles around the segments, the thin triangles
+    themselves (in the order of segments()), and the triangles through the duplicate pairs' centroids."""
     rng = np.random.default_rng(seed)
     ext = _extent(g)
     prim, a, b = segments(g, kind)
@@ -290,7 +290,13 @@ def aimed_triangles(g, kind, twin, seed, per=6):
     mid = (g.v0[t] + (g.e1[t] + g.e2[t]) / np.float32(3)).astype(np.float64)
     across = mid[:, None, :] + rng.uniform(-1, 1, (len(t), 3, 3)) * 0.02 * ext
     across[:, 0] = mid                                             # one vertex in the pair's plane: a touch
-    return np.concatenate([q, own, across]).astype(np.float32)
+    return q.astype(np.float32), own.astype(np.float32), across.astype(np.float32)
+
+
+def aimed_triangles(g, kind, twin, seed, per=6):
+    """Query triangles [N, 3, 3]: small ones (up to 1 % of the extent) around points of the thin triangles' segments, every fourth
+    one itself a segment; the thin triangles themselves; and triangles through the centroid of each duplicate pair."""
+    return np.concatenate(aimed_triangle_parts(g, kind, twin, seed, per))
 
 
 def aimed_planes(g, kind, seed):
