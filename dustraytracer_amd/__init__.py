@@ -341,6 +341,10 @@ _sig("drt_renderer_surface_weights", C.c_int, _P, _P, _P, _P)
 _sig("drt_renderer_sample_surface", C.c_int, _P, _P, C.c_uint32, C.c_uint32, _P, C.c_uint32, _P)
 _sig("drt_renderer_ambient_occlusion", C.c_int, _P, _P, _P, C.c_uint32, _P, _P, _P)
 _sig("drt_debug_ambient_stats", C.c_int, _P, C.c_int32, _P)
+_sig("drt_renderer_winding_numbers", C.c_int, _P, _P, _P, C.c_uint32, C.c_float, _P, _P)
+_sig("drt_renderer_winding_inside", C.c_int, _P, _P, _P, C.c_uint32, C.c_float, C.c_float, _P, _P)
+_sig("drt_renderer_winding_signed_distance", C.c_int, _P, _P, _P, C.c_uint32, C.c_float, C.c_float, _P, _P)
+_sig("drt_debug_winding_moments", C.c_int, _P, _P, _P, C.c_size_t, _P)
 _sig("drt_scene_edge_adjacency", C.c_int, _P, _P, C.c_uint32)
 _sig("drt_renderer_chain_sections", C.c_int, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _P)
 _sig("drt_tri_edge_adjacency", C.c_int, _P, C.c_uint32, _P, C.c_uint32)
@@ -2393,6 +2397,97 @@ class Renderer:
         z, y, x = torch.meshgrid(axes[2], axes[1], axes[0], indexing="ij")
         near = self.signedDistance(scene, torch.stack([x, y, z], dim=-1).reshape(-1, 3), rule=rule)
         return (near.side * torch.sqrt(near.d2)).reshape(res[2], res[1], res[0])
+
+    @staticmethod
+    def _winding_beta(beta):
+        try:
+            beta = float(beta)
+        except (TypeError, ValueError):
+            beta = float("nan")
+        if not beta >= 0.0:
+            raise DrtError(ERR_INVALID, "beta %r: a number >= 0 (or inf) expected" % (beta,))
+        return beta
+
+    def windingNumbers(self, scene, points, beta=2.0):
+        """The generalised winding number of each point (drt_renderer_winding_numbers): float32 [N], the triangles' signed solid
+        angles at the point over 4 pi -- 1 inside and 0 outside a closed outward mesh, and a value that degrades smoothly, instead of
+        flipping, where the mesh has holes.  Evaluated on the tree: a node farther than beta of its radii is replaced by one dipole
+        term (first order); beta=inf is the exact sum over all triangles, beta=0 the root's dipole alone.  points [N, 3] float32 (or
+        packed [N, 4]; max_dist is ignored).  Device tensors in, device tensors out (enqueued on the current torch stream); numpy in,
+        numpy out.  After refit(scene, positions) the moved geometry is the one queried.  A point with a NaN or an infinity answers
+        NaN.  What it is not: first order only; a point on the surface has no defined answer; orientation is still assumed per
+        connected patch; no RendererGroup and no command line."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        beta = self._winding_beta(beta)
+        packed, from_numpy = _point_batch(torch, dev, points, float("inf"))
+        n = packed.shape[0]
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+        if n:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(_lib.drt_renderer_winding_numbers(self._h, scene._h, packed.data_ptr(), n, beta, out.data_ptr(), stream))
+        return out.cpu().numpy() if from_numpy else out
+
+    def windingInside(self, scene, points, beta=2.0, threshold=0.5):
+        """windingNumbers(scene, points, beta) >= threshold as bool [N] (drt_renderer_winding_inside): the inside test that a missing
+        triangle or a hole does not break.  A point with a NaN or an infinity is outside."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        beta = self._winding_beta(beta)
+        packed, from_numpy = _point_batch(torch, dev, points, float("inf"))
+        n = packed.shape[0]
+        out = torch.empty(n, dtype=torch.uint8, device=dev)
+        if n:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(_lib.drt_renderer_winding_inside(self._h, scene._h, packed.data_ptr(), n, beta, float(threshold), out.data_ptr(), stream))
+        res = out != 0
+        return res.cpu().numpy() if from_numpy else res
+
+    def windingSignedDistance(self, scene, points, max_dist=float("inf"), beta=2.0, threshold=0.5):
+        """nearest(scene, points, max_dist) with side = -1 where windingNumbers(scene, points, beta) >= threshold, +1 elsewhere
+        (drt_renderer_winding_signed_distance); miss records carry the sign too.  The signed distance is side * sqrt(d2)."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        beta = self._winding_beta(beta)
+        packed, from_numpy = _point_batch(torch, dev, points, max_dist)
+        n = packed.shape[0]
+        out = torch.empty((n, 8), dtype=torch.float32, device=dev)
+        if n:
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            _check(_lib.drt_renderer_winding_signed_distance(self._h, scene._h, packed.data_ptr(), n, beta, float(threshold), out.data_ptr(), stream))
+        if from_numpy:
+            h = out.cpu().numpy()
+            return Nearest(h[:, 0:3].copy(), h[:, 3].copy(), h.view(np.int32)[:, 4].copy(), h[:, 5].copy(), h[:, 6].copy(), h[:, 7].copy())
+        return Nearest(out[:, 0:3], out[:, 3], out.view(torch.int32)[:, 4], out[:, 5], out[:, 6], out[:, 7])
+
+    def windingGrid(self, scene, resolution, lo=None, hi=None, beta=2.0):
+        """A winding-number field: float32 [Z, Y, X] device tensor of windingNumbers at the cell centres of a grid over the box (lo, hi),
+        by default the scene's bounds, laid out as sdfGrid's.  resolution: an int or (X, Y, Z).  The points are made on the device."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        beta = self._winding_beta(beta)
+        res = (int(resolution),) * 3 if isinstance(resolution, (int, np.integer)) else tuple(int(v) for v in resolution)
+        if len(res) != 3 or min(res) < 1:
+            raise DrtError(ERR_INVALID, "resolution: a positive int or three of them expected")
+        if lo is None or hi is None:
+            nodes = scene.m_BVHNodes
+            if len(nodes) == 0:
+                raise DrtError(ERR_INVALID, "windingGrid: an empty scene has no bounds; give lo and hi")
+            lo = nodes[-1]["bmin"] if lo is None else lo                      # the root is the last node
+            hi = nodes[-1]["bmax"] if hi is None else hi
+        lo, hi = np.asarray(lo, np.float32).reshape(3), np.asarray(hi, np.float32).reshape(3)
+        axes = [float(lo[k]) + (torch.arange(res[k], dtype=torch.float32, device=dev) + 0.5) * (float(hi[k] - lo[k]) / res[k]) for k in range(3)]
+        z, y, x = torch.meshgrid(axes[2], axes[1], axes[0], indexing="ij")
+        return self.windingNumbers(scene, torch.stack([x, y, z], dim=-1).reshape(-1, 3), beta=beta).reshape(res[2], res[1], res[0])
+
+    def debugWindingMoments(self, scene):
+        """The node moments the winding calls use for this renderer's copy of `scene` (drt_debug_winding_moments): float32 [nodes, 8]
+        = {N[3], r2, p[3], pad}, the interior nodes in the host scene's node order, then the leaves in node order."""
+        count = C.c_uint32(0)
+        _check(_lib.drt_debug_winding_moments(self._h, scene._h, None, 0, C.byref(count)))
+        out = np.zeros((count.value, 8), np.float32)
+        _check(_lib.drt_debug_winding_moments(self._h, scene._h, out.ctypes.data, out.size, C.byref(count)))
+        return out
 
     def renderGuides(self, cam, scene, frame_index=1, as_torch=False):
         """First-hit guide buffers of frame `frame_index` (drt_renderer_render_guides): Guides(albedo [H, W, 3], normal [H, W, 3],

@@ -1229,6 +1229,27 @@ static RefitPlan refit_plan(const HostScene &h) {
     return p;
 }
 
+}  // extern "C"
+
+// The uploaded scene's plan on the device, made once per upload: the first refit needs it, and so does the first winding call.
+int drt::refit_metadata(drt_renderer *r, const drt_scene *scene) {
+    if (r->rf_built) return DRT_OK;
+    RefitPlan plan;
+    try { plan = refit_plan(scene->host); } catch (...) { return from_exception(); }
+    HIP_TRY(r->rf_order.upload(plan.order));
+    HIP_TRY(r->rf_avg.upload(plan.avg_normal));
+    HIP_TRY(r->rf_ext.upload(std::vector<float>(6 * (size_t)plan.n_nodes, 0.f)));
+    HIP_TRY(r->rf_leaves.upload(plan.leaves));
+    HIP_TRY(r->rf_levels.upload(plan.inner));
+    HIP_TRY(r->rf_height_begin.upload(plan.height_begin));
+    HIP_TRY(r->rf_out.upload(std::vector<float>(8, 0.f)));
+    r->rf_heights = plan.height_begin;
+    r->rf_built = true;
+    return DRT_OK;
+}
+
+extern "C" {
+
 // device memory of the renderer's device that holds `bytes` bytes from p on (as far as the runtime can tell)
 static bool device_range_on_renderer(const drt_renderer *r, const void *p, size_t bytes) {
     if (((uintptr_t)p & 3u) != 0 || !on_renderer_device(r, p)) return false;
@@ -1251,19 +1272,8 @@ int drt_renderer_refit(drt_renderer *r, const drt_scene *scene, const float *pos
         if (p && !device_range_on_renderer(r, p, bytes))
             return fail(DRT_ERR_INVALID, "positions and normals must be float[n][3][3] in device memory on the renderer's device");
     if (int rc = upload_scene(r, scene)) return rc;
-    if (!r->rf_built) {
-        RefitPlan plan;
-        try { plan = refit_plan(scene->host); } catch (...) { return from_exception(); }
-        HIP_TRY(r->rf_order.upload(plan.order));
-        HIP_TRY(r->rf_avg.upload(plan.avg_normal));
-        HIP_TRY(r->rf_ext.upload(std::vector<float>(6 * (size_t)plan.n_nodes, 0.f)));
-        HIP_TRY(r->rf_leaves.upload(plan.leaves));
-        HIP_TRY(r->rf_levels.upload(plan.inner));
-        HIP_TRY(r->rf_height_begin.upload(plan.height_begin));
-        HIP_TRY(r->rf_out.upload(std::vector<float>(8, 0.f)));
-        r->rf_heights = plan.height_begin;
-        r->rf_built = true;
-    }
+    if (int rc = refit_metadata(r, scene)) return rc;
+    r->wn_valid = false;                         // the winding moments are those of the positions that go
     HIP_TRY(r->ev_rf_start.create());
     HIP_TRY(r->ev_rf_stop.create());
     HIP_TRY(r->ev_rf_dep.create(hipEventDisableTiming));

@@ -1,4 +1,4 @@
-// renderer_state.hpp -- what the translation units of the C ABI share (drt_capi.cpp, drt_capi_filters.cpp, drt_capi_adaptive.cpp, drt_capi_section.cpp, drt_capi_contour.cpp, drt_capi_topology.cpp, drt_capi_intersect.cpp, drt_capi_surface.cpp, drt_capi_ambient.cpp): the renderer's state,
+// renderer_state.hpp -- what the translation units of the C ABI share (drt_capi.cpp, drt_capi_filters.cpp, drt_capi_adaptive.cpp, drt_capi_section.cpp, drt_capi_contour.cpp, drt_capi_topology.cpp, drt_capi_intersect.cpp, drt_capi_surface.cpp, drt_capi_ambient.cpp, drt_capi_winding.cpp): the renderer's state,
 // the owners of its device memory, pinned memory and events, error reporting, the steps several entry points take.  Not exported.
 #pragma once
 #include "../../include/drt.h"
@@ -17,6 +17,7 @@
 #include "radiance.hpp"
 #include "adaptive.hpp"
 #include "refit.hpp"
+#include "winding.hpp"
 #include "scene_host.hpp"
 
 #pragma GCC visibility push(hidden)
@@ -242,6 +243,12 @@ struct drt_renderer {
     // and the two counters of the counting build (drt_debug_ambient_stats)
     DeviceArray<unsigned long long> ao_heads, ao_stats;
     bool ao_stats_on = false;
+    // generalised winding numbers (drt_capi_winding.cpp): one 32-byte moment per tree node (winding.hpp) and the sums a parent adds up,
+    // made on the stream of the first winding call after an upload or a refit (wn_valid), kept until the next one, dropped with the
+    // scene copy; the passes read the refit plan (rf_leaves, rf_levels, rf_heights)
+    DeviceArray<drt::WindingMoment> wn_moments;
+    DeviceArray<float4> wn_sums;
+    bool wn_valid = false;
 
     drt_renderer() = default;
     ~drt_renderer() {                          // the members release what they own, on this device
@@ -266,6 +273,8 @@ struct drt_renderer {
         topo_built = false;
         sf_normals.release(); sf_order.release();
         sf_built = false;
+        wn_moments.release(); wn_sums.release();
+        wn_valid = false;
         uploaded_scene = nullptr;
     }
     void free_upscale() {
@@ -304,6 +313,8 @@ bool on_renderer_device(const drt_renderer *r, const void *p);
 int query_order(drt_renderer *r, hipStream_t s);
 int query_recorded(drt_renderer *r, hipStream_t s);
 int traversal_scratch(drt_renderer *r, hipStream_t s, bool occluded, bool heads);
+// The uploaded scene's refit plan on the device (refit.hpp: the leaves, the interior nodes by height), made once per upload
+int refit_metadata(drt_renderer *r, const drt_scene *scene);
 // What a call on a finished frame starts with: a frame size, no pending batch, not sharded (`who`, e.g. "the denoiser needs", opens
 // the message; nullptr = the caller calls whole_frame later), the renderer's device selected, no stale HIP error
 int stage_open(drt_renderer *r, const char *who);

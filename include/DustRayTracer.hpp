@@ -328,6 +328,22 @@ public:
                         void *stream = nullptr) {
         drt::check(drt_renderer_signed_distance(handle, scene.handle, points, out, n, rule, stream));
     }
+    // new: generalised winding numbers, the inside test for meshes that are open or unevenly oriented -- w = the triangles' signed solid
+    // angles at each point over 4 pi, on the tree with one dipole per far subtree (drt_renderer_winding_numbers); one byte w >= threshold
+    // (drt_renderer_winding_inside); Nearest's records with side = -1 where w >= threshold, else +1
+    // (drt_renderer_winding_signed_distance).  beta: a node is replaced by its dipole beyond beta radii, +inf = the exact sum; first
+    // order only.  Device arrays, enqueued on `stream`.
+    void WindingNumbers(const Scene &scene, const drt_point *points, float *out, uint32_t n, float beta = 2.0f, void *stream = nullptr) {
+        drt::check(drt_renderer_winding_numbers(handle, scene.handle, points, n, beta, out, stream));
+    }
+    void WindingInside(const Scene &scene, const drt_point *points, uint8_t *out, uint32_t n, float beta = 2.0f, float threshold = 0.5f,
+                       void *stream = nullptr) {
+        drt::check(drt_renderer_winding_inside(handle, scene.handle, points, n, beta, threshold, out, stream));
+    }
+    void WindingSignedDistance(const Scene &scene, const drt_point *points, drt_nearest *out, uint32_t n, float beta = 2.0f,
+                               float threshold = 0.5f, void *stream = nullptr) {
+        drt::check(drt_renderer_winding_signed_distance(handle, scene.handle, points, n, beta, threshold, out, stream));
+    }
     // new: the triangles each ray passes through, sorted by (t, prim) (drt_renderer_list_hits): ray i's records go to
     // hits[offsets[i] .. offsets[i+1]), clamped to hits_capacity, miss records behind them; counts[i] = all of them, stored or not.
     // counts may be null, hits may be null iff hits_capacity == 0.  Device arrays, enqueued on `stream`.

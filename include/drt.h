@@ -35,7 +35,8 @@ extern "C" {
  * point (drt_renderer_intersect_triangles), the intersection-curve entry points (drt_tri_edge_adjacency,
  * drt_renderer_chain_intersections), the triangle-distance entry point (drt_renderer_triangle_distance), the triangle-cast entry
  * point (drt_renderer_triangle_cast), the surface entry points (drt_renderer_surface_lookup, drt_renderer_surface_weights,
- * drt_renderer_sample_surface) and the ambient-occlusion entry point (drt_renderer_ambient_occlusion) are additions to it */
+ * drt_renderer_sample_surface), the ambient-occlusion entry point (drt_renderer_ambient_occlusion) and the winding-number entry
+ * points (drt_renderer_winding_numbers / _winding_inside / _winding_signed_distance) are additions to it */
 #define DRT_ABI_VERSION 2
 
 typedef enum {
@@ -1255,6 +1256,76 @@ typedef struct drt_ao_result { int32_t open; int32_t bent[3]; } drt_ao_result;  
 int           drt_renderer_ambient_occlusion(drt_renderer *r, const drt_scene *scene, const drt_ao_point *pts, uint32_t n,
                                              const drt_ao_params *params, drt_ao_result *out, void *hip_stream);
 int           drt_debug_ambient_stats(drt_renderer *r, int32_t enable, uint64_t out[2]);
+
+/* ---- generalised winding numbers (new; inside tests and signed distance for meshes that are open or unevenly oriented) ----
+ * w(q) = the sum over the triangles of the signed solid angle each subtends at q, divided by 4 pi (Jacobson et al. 2013): exactly 1
+ * inside and 0 outside a closed mesh with outward faces, and on a mesh with holes a value that degrades smoothly instead of flipping,
+ * so that w >= 0.5 is an inside test that a missing triangle does not break.  It is evaluated on the renderer's tree (Barill et al.
+ * 2018, first order): a subtree that is far from the point is replaced by one dipole term from a per-node moment.  Stated bit for
+ * bit: fp32 with one rounding per operation, in the order written, a + b + c + d = ((a + b) + c) + d; dot(a, b) = a.x b.x + a.y b.y +
+ * a.z b.z; cross(a, b) = (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x); division and sqrtf correctly rounded; |v| =
+ * sqrtf(dot(v, v)).
+ *
+ * Triangle term, on the stored (v0, e1, e2) of a triangle, for the point q:
+ *   a = v0 - q, b = a + e1, c = a + e2
+ *   det = dot(a, cross(e1, e2)) -- the triangle's own winding e1 x e2, as drt_renderer_crossings uses it, not the stored face normal
+ *   den = |a| * |b| * |c| + dot(a, b) * |c| + dot(b, c) * |a| + dot(c, a) * |b|
+ *   omega = 2.0f * atan2(det, den), in steradians (van Oosterom and Strackee 1983)
+ * A triangle with det == 0 contributes exactly 0 -- an edge-on view, a zero-area triangle, q in the triangle's plane -- so atan2(0, x)
+ * is never evaluated.
+ * atan2(y, x) is the project's own, one division and a fixed polynomial in plain fp32 + * / (the library's atan2f is not used: it
+ * cannot be restated to the bit), for y != 0:
+ *   ax = |x|, ay = |y|; swap = ay > ax; mx = swap ? ay : ax; mn = swap ? ax : ay
+ *   big = mn > 0.414213562f * mx
+ *   t = big ? (mn - mx) / (mn + mx) : mn / mx;  s = t * t
+ *   r = (((8.05374449538e-2f * s - 1.38776856032e-1f) * s + 1.99777106478e-1f) * s - 3.33329491539e-1f) * s * t + t
+ *   if big: r = 0.785398163f + r;  if swap: r = 1.57079633f - r;  if x < 0: r = 3.14159265f - r;  if y < 0: r = -r
+ * (the coefficients are those of the Cephes library's atanf for |t| <= tan(pi / 8)).  A NaN in x or y gives a NaN; so does inf / inf.
+ *
+ * Node moment, 32 bytes per tree node, interior and leaf: drt_winding_moment {N[3], r2, p[3], pad}, pad = 0.  Per triangle
+ * n_t = 0.5f * cross(e1, e2), area_t = |n_t|, c_t = v0 + (e1 + e2) / 3.0f.  A leaf sums its triangles in ascending tree index from
+ * zeros: N = N + n_t, A = A + area_t, S = S + area_t * c_t, per component.  A parent is child 1 + child 2, in that order, for N, A and
+ * S.  Then p = S / A per component, the area-weighted centroid; if !(A > 0), or A or a component of p is not finite, p = 0.5f * (lo + hi),
+ * the centre of the node's box as the tree stores it: the child box in the parent's record, or the root box.  r2 = dx dx + dy dy + dz dz
+ * with dx = max(|p.x - lo.x|, |hi.x - p.x|) and so on: the squared distance from p to the farthest corner of that box.  Every moment is
+ * therefore the same bytes whatever computes it.  The moments are made from the device's triangles and boxes by the first winding call
+ * after an upload or a drt_renderer_refit, on that call's stream, and kept until the next one: a refitted copy answers for the moved mesh.
+ *
+ * Evaluation of a point: a depth-first walk from the root, child 1 before child 2, over a stack that never holds more entries than the
+ * tree has levels.  One fp32 accumulator, in steradians, starts at 0 and is added to in visit order.  For a visited node, the root or a
+ * leaf as a whole included, d = p - q and dd = dot(d, d):
+ *   iff dd > (beta * beta) * r2   the node is replaced by its dipole: accumulator += dot(d, N) / (dd * sqrtf(dd))
+ *   otherwise                     an interior node is descended; a leaf adds omega of its triangles in ascending index.
+ * w = accumulator * 0.0795774715f: the 1 / (4 pi) is applied once, at the end.  beta = +inf never approximates (inf * 0 is a NaN and
+ * the comparison fails, which is the intended reading): the exact sum over all triangles.  beta = 0 answers with the root's dipole
+ * alone.  beta = 2 is the default of the wrappers.  A point with a NaN or an infinity answers NaN without walking; an empty scene
+ * answers 0.  Alpha cut-outs are ignored; drt_point's max_dist is ignored by the first two entry points.
+ * Results: drt_renderer_winding_numbers writes the float w; drt_renderer_winding_inside one byte, w >= threshold ? 1 : 0 (a NaN is 0);
+ * drt_renderer_winding_signed_distance runs drt_renderer_nearest and then, on the same stream, replaces the last word, side, of every
+ * record by w >= threshold ? -1 : +1, in miss records too; the first seven words are unchanged.  Results are written with ordinary
+ * stores; there are no floating-point atomics and no sums across lanes: a point's answer depends on its own walk only, so a batch in
+ * any order, size or tiling gives the same bytes.
+ *
+ * What this is not: first order only -- the dipole's error falls as 1 / beta^2 and the second-order terms of Barill et al. are not
+ * built; a point on the surface has no defined answer; orientation is still assumed per connected patch -- a patch with flipped
+ * faces subtracts; fp32 throughout, so the determinant of a triangle that is far away and seen edge-on cancels; no drt_group_* form
+ * and no command line.  drt_renderer_inside's rules stay 0 and 1: this is a separate entry point.
+ * Conventions are drt_renderer_nearest's, with every argument checked before any device work, in this order: the handles, a negative
+ * or NaN beta, n == 0 is a no-op, NULL points or out, points and drt_nearest records 16-byte aligned and floats 4-byte aligned,
+ * n < 2^31, a pending asynchronous batch (DRT_ERR_INVALID each); then points and out must be device memory on the renderer's device.
+ * hip_stream NULL = the renderer's stream; the call only enqueues, in order with the other queries (the same event);
+ * DRT_ERR_UNSUPPORTED for trees deeper than 64 levels; legal on a sharded renderer; the framebuffer, accumulation, sample count,
+ * counters, kernel info and kernel span are not touched.
+ * drt_debug_winding_moments reads the moments back (making them if they are stale): *count = interior nodes + leaves, and into out,
+ * if it is not NULL and holds 8 * *count floats, the interior nodes' records in the host scene's node order followed by the leaves'. */
+typedef struct drt_winding_moment { float N[3]; float r2; float p[3]; float pad; } drt_winding_moment;     /* 32 B */
+int           drt_renderer_winding_numbers(drt_renderer *r, const drt_scene *scene, const drt_point *points, uint32_t n, float beta,
+                                           float *out, void *hip_stream);
+int           drt_renderer_winding_inside(drt_renderer *r, const drt_scene *scene, const drt_point *points, uint32_t n, float beta,
+                                          float threshold, uint8_t *out, void *hip_stream);
+int           drt_renderer_winding_signed_distance(drt_renderer *r, const drt_scene *scene, const drt_point *points, uint32_t n, float beta,
+                                                   float threshold, drt_nearest *out, void *hip_stream);
+int           drt_debug_winding_moments(drt_renderer *r, const drt_scene *scene, float *out, size_t out_floats, uint32_t *count);
 
 /* ---- first-hit guide buffers and the a-trous denoiser (new; the reference's TODO list, RayGen.cuh:13-21, starts with "DLSS 3.5
  * like features") ----

@@ -52,6 +52,12 @@ def pretty(name):
     m = re.search(r"ambient_kernelILb(\d)E", name)
     if m:
         return "ambient_kernel<%s>" % ("counting build" if m.group(1) == "1" else "plain")
+    m = re.search(r"winding_kernelILi(\d)E", name)
+    if m:
+        return "winding_kernel<%s>" % ("number", "inside", "side")[int(m.group(1))]
+    m = re.search(r"\d+(winding_moments_\w+?)ENS", name)
+    if m:
+        return m.group(1)
     m = re.search(r"\d+(\w+_kernel)", name)
     return m.group(1) if m else name
 
@@ -62,7 +68,8 @@ def main():
     for src, extra in (("kernel_path_pool.hip", ()), ("kernel_path_pool.hip", ("-DDRT_POOL_EXT_TU",)), ("kernel_wave_queue.hip", ()),
                        ("render_kernels.hip", ()), ("kernel_bvh_build.hip", ()), ("kernel_sphere_cast.hip", ()), ("kernel_near_list.hip", ()),
                        ("kernel_overlap.hip", ()), ("kernel_tri_overlap.hip", ()), ("kernel_intersect.hip", ()), ("kernel_tri_distance.hip", ()),
-                       ("kernel_tri_cast.hip", ()), ("kernel_surface.hip", ()), ("kernel_ambient.hip", ())):
+                       ("kernel_tri_cast.hip", ()), ("kernel_surface.hip", ()), ("kernel_ambient.hip", ()),
+                       ("kernel_winding.hip", ())):
         for r in remarks(src, extra):
             if "VGPRs" in r and not (extra and "ILi" in r["name"] and int(re.search(r"ILi(\d+)E", r["name"]).group(1)) < 16):
                 rows.append(r)
