@@ -216,6 +216,11 @@ class AdaptiveInfo(C.Structure):
         return "AdaptiveInfo(samples=%d, active_pixels=%d, max_count=%d, ms=%.3f)" % (self.samples, self.active_pixels, self.max_count, self.ms)
 
 
+class _Grid(C.Structure):
+    """include/drt.h drt_grid: the lattice of an isosurface's field (host memory)."""
+    _fields_ = [("lo", C.c_float * 3), ("cell", C.c_float * 3), ("dims", C.c_uint32 * 3)]
+
+
 class Counters(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("samples", "rays", "node_visits", "inner_visits", "tri_tests",
                                            "hits_textured", "hits_flat", "shadow_rays", "inner_visits_shadow",
@@ -345,6 +350,7 @@ _sig("drt_renderer_winding_numbers", C.c_int, _P, _P, _P, C.c_uint32, C.c_float,
 _sig("drt_renderer_winding_inside", C.c_int, _P, _P, _P, C.c_uint32, C.c_float, C.c_float, _P, _P)
 _sig("drt_renderer_winding_signed_distance", C.c_int, _P, _P, _P, C.c_uint32, C.c_float, C.c_float, _P, _P)
 _sig("drt_debug_winding_moments", C.c_int, _P, _P, _P, C.c_size_t, _P)
+_sig("drt_renderer_isosurface", C.c_int, _P, _P, _P, C.c_float, C.c_float, C.c_int32, _P, _P, C.c_uint32, _P, _P)
 _sig("drt_scene_edge_adjacency", C.c_int, _P, _P, C.c_uint32)
 _sig("drt_renderer_chain_sections", C.c_int, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _P)
 _sig("drt_tri_edge_adjacency", C.c_int, _P, C.c_uint32, _P, C.c_uint32)
@@ -742,6 +748,53 @@ class CurveList(collections.namedtuple("CurveList", "chain_splits closed p q que
         import torch
         d = self.q.to(torch.float64) - self.p.to(torch.float64)
         return _segment_sums(torch, torch.sqrt((d * d).sum(dim=1)), self.chain_splits.to(torch.int64))
+
+
+class Isosurface(collections.namedtuple("Isosurface", "splits tris cube code")):
+    """The triangles of an isosurface (Renderer.isosurface / remesh): row r -- the cubes along x of one (y, z) -- owns the triangles
+    splits[r]:splits[r + 1] of tris [M, 3, 3] float32, cube [M] (the linear cube index) and code [M] (tetrahedron | case << 4), both
+    int32, in ascending cube, tetrahedron and table order.  Triangle soup: no vertex index buffer; shared vertices are bit-equal, so
+    triEdgeAdjacency(tris) recovers the connectivity.  Device tensors (tris a strided view of the 48-byte records) or numpy arrays."""
+
+    def records(self):
+        """The packed 48-byte records [M, 12] float32 (drt_iso_tri, laid out as drt_tri), as overlapTriangles, intersectTriangles,
+        triangleDistance and triangleCast take them: for device tensors the fill's own output, not a copy."""
+        if isinstance(self.tris, np.ndarray):
+            rec = np.zeros((len(self.tris), 12), np.float32)
+            rec[:, 0:9] = self.tris.reshape(-1, 9)
+            rec.view(np.int32)[:, 9], rec.view(np.int32)[:, 10] = self.cube, self.code
+            return rec
+        import torch
+        m = self.tris.shape[0]
+        if m and self.tris.stride() == (12, 3, 1):
+            return torch.as_strided(self.tris, (m, 12), (12, 1), self.tris.storage_offset())
+        rec = torch.zeros((m, 12), dtype=torch.float32, device=self.tris.device)
+        rec[:, 0:9] = self.tris.reshape(m, 9)
+        rec.view(torch.int32)[:, 9], rec.view(torch.int32)[:, 10] = self.cube, self.code
+        return rec
+
+    def faceNormals(self):
+        """float32 [M, 3]: cross(v1 - v0, v2 - v0) normalised, zeros for a zero-area triangle.  They point to the side where
+        f >= level (away from it with flip).  Face normals only: there are no gradient normals."""
+        if isinstance(self.tris, np.ndarray):
+            n = np.cross(self.tris[:, 1] - self.tris[:, 0], self.tris[:, 2] - self.tris[:, 0]).astype(np.float32)
+            length = np.sqrt((n * n).sum(axis=1, keepdims=True))
+            return np.where(length > 0, n / np.where(length > 0, length, 1), 0).astype(np.float32)
+        import torch
+        n = torch.linalg.cross(self.tris[:, 1] - self.tris[:, 0], self.tris[:, 2] - self.tris[:, 0], dim=1)
+        length = torch.sqrt((n * n).sum(dim=1, keepdim=True))
+        return torch.where(length > 0, n / torch.where(length > 0, length, torch.ones_like(length)), torch.zeros_like(n))
+
+    def toScene(self, albedo=(0.8, 0.8, 0.8)):
+        """A Scene of the triangles (Scene.setGeometry) with face normals at the vertices, zero uvs and one material of `albedo`.
+        The caller builds the BVH."""
+        host = (lambda a: a) if isinstance(self.tris, np.ndarray) else (lambda a: a.detach().cpu().numpy())
+        tris = np.ascontiguousarray(host(self.tris), np.float32)
+        nrm = np.repeat(host(self.faceNormals())[:, None, :], 3, axis=1)
+        sc = Scene()
+        sc.addMaterial(tuple(float(c) for c in albedo))
+        sc.setGeometry(tris, nrm, np.zeros((len(tris), 3, 2), np.float32), np.zeros(len(tris), np.int32))
+        return sc
 
 
 def triEdgeAdjacency(tris):
@@ -2479,6 +2532,145 @@ class Renderer:
         axes = [float(lo[k]) + (torch.arange(res[k], dtype=torch.float32, device=dev) + 0.5) * (float(hi[k] - lo[k]) / res[k]) for k in range(3)]
         z, y, x = torch.meshgrid(axes[2], axes[1], axes[0], indexing="ij")
         return self.windingNumbers(scene, torch.stack([x, y, z], dim=-1).reshape(-1, 3), beta=beta).reshape(res[2], res[1], res[0])
+
+    @staticmethod
+    def _iso_arguments(level, lo, hi, border):
+        """(level, lo [3], hi [3], border or NaN) of isosurface, checked: finite numbers."""
+        def number(v, what):
+            try:
+                v = float(v)
+            except (TypeError, ValueError):
+                v = float("nan")
+            if not np.isfinite(v):
+                raise DrtError(ERR_INVALID, "%s: a finite number expected" % what)
+            return v
+
+        level = number(level, "level %r" % (level,))
+        border = float("nan") if border is None else number(border, "border %r" % (border,))
+        try:
+            lo, hi = np.asarray(lo, np.float32).reshape(-1), np.asarray(hi, np.float32).reshape(-1)
+        except (TypeError, ValueError):
+            raise DrtError(ERR_INVALID, "lo and hi: three finite numbers each expected")
+        if lo.shape != (3,) or hi.shape != (3,) or not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+            raise DrtError(ERR_INVALID, "lo and hi: three finite numbers each expected")
+        return level, lo, hi, border
+
+    def _iso_passes(self, field, grid, level, border, flip):
+        """(splits [R + 1] int32, records [M, 12] float32) on the field's device: drt_renderer_isosurface's count, a cumulative sum on
+        the device, the one read-back of the total, the fill."""
+        import torch
+        dev = field.device
+        pad = 0 if np.isnan(border) else 2
+        rows = (grid.dims[1] - 1 + pad) * (grid.dims[2] - 1 + pad)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        counts = torch.empty(rows, dtype=torch.int32, device=dev)
+        _check(_lib.drt_renderer_isosurface(self._h, field.data_ptr(), C.byref(grid), level, border, 1 if flip else 0, None, None, 0,
+                                            counts.data_ptr(), stream))
+        splits = torch.zeros(rows + 1, dtype=torch.int64, device=dev)
+        splits[1:] = torch.cumsum(counts.to(torch.int64), dim=0)
+        total = int(splits[-1].item())           # the one synchronisation: the result's size
+        if total >= 2 ** 31:
+            raise DrtError(ERR_INVALID, "%d triangles in all: fewer than 2^31 expected (extract the field in parts)" % total)
+        splits = splits.to(torch.int32)
+        rec = torch.empty((total, 12), dtype=torch.float32, device=dev)       # drt_iso_tri: v[3][3], cube, code, 0
+        if total:
+            _check(_lib.drt_renderer_isosurface(self._h, field.data_ptr(), C.byref(grid), level, border, 1 if flip else 0, splits.data_ptr(),
+                                                rec.data_ptr(), total, None, stream))
+        return splits, rec
+
+    def isosurface(self, field, level, lo, hi, flip=False, border=None):
+        """A watertight triangle mesh of the surface f = level of a field (drt_renderer_isosurface): marching tetrahedra on the
+        six-tetrahedron split of every cube of neighbouring samples.  field: float32 [Z, Y, X] whose sample (i, j, k) lies at
+        lo + (idx + 0.5) * cell per component, cell = (hi - lo) / (X, Y, Z) in float32 -- what sdfGrid and windingGrid return for
+        the same lo, hi.  A sample is above iff f >= level; a vertex on a lattice edge is always interpolated from the end with the
+        smaller index, so every cube that shares the edge computes the same bits, and the mesh is a closed, consistently oriented
+        2-manifold wherever it does not leave the grid.  Face normals point to the above side -- outward for a signed distance that
+        is negative inside; flip=True reverses every triangle, for fields that are large inside, such as winding numbers.
+        border=b (a finite number): one virtual layer of samples with that value surrounds the grid, so with b on the outside class
+        every surface closes, whatever the field; None: a surface that reaches the grid's edge is open there.  A tetrahedron with a
+        NaN or an infinity at a corner emits nothing.
+        Isosurface(splits [R + 1] int32, tris [M, 3, 3] float32, cube [M], code [M] int32): row r (the cubes along x of one (y, z))
+        owns [splits[r], splits[r + 1]); ascending cube, tetrahedron and table order, the same bytes on every run.  A count, a
+        cumulative sum on the device, and a fill; the total is read back between them to size the result: that read is this call's
+        one synchronisation with the device.  A device tensor in, device tensors out (enqueued on the current torch stream; tris is
+        a strided view of the 48-byte records); numpy in, numpy out.  Needs no scene.
+        What it is not: no vertex index buffer -- triangle soup with bit-equal shared positions, triEdgeAdjacency recovers the
+        connectivity; a sample exactly equal to level is above, and zero-area triangles with zero-length edges appear there, which
+        edgeAdjacency marks -2 -- shift level by an ulp or accept them; no gradient normals -- Isosurface.faceNormals gives face
+        normals; roughly twice the triangles of marching cubes; the surface of the piecewise-linear interpolant and no better; no
+        simplification, no smoothing and no dual or sharp-feature methods; no RendererGroup and no command line."""
+        level, lo, hi, border = self._iso_arguments(level, lo, hi, border)
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        if isinstance(field, np.ndarray):
+            if field.dtype != np.float32:
+                raise DrtError(ERR_INVALID, "field: dtype %s, float32 expected" % field.dtype)
+            from_numpy = True
+        elif torch.is_tensor(field):
+            if field.dtype != torch.float32:
+                raise DrtError(ERR_INVALID, "field: dtype %s, torch.float32 expected" % field.dtype)
+            if field.device != dev:
+                raise DrtError(ERR_INVALID, "field: on %s, the renderer is on %s" % (field.device, dev))
+            from_numpy = False
+        else:
+            raise DrtError(ERR_INVALID, "field: a numpy array or a torch tensor expected")
+        if field.ndim != 3:
+            raise DrtError(ERR_INVALID, "field: shape %s, [Z, Y, X] expected" % (tuple(field.shape),))
+        least = 2 if np.isnan(border) else 1
+        if min(field.shape) < least:
+            raise DrtError(ERR_INVALID, "field: shape %s, at least %d samples per axis expected" % (tuple(field.shape), least))
+        f = torch.from_numpy(np.ascontiguousarray(field)).to(dev) if from_numpy else field.contiguous()
+        grid = _Grid()
+        res = (int(f.shape[2]), int(f.shape[1]), int(f.shape[0]))
+        cell = ((hi - lo) / np.asarray(res, np.float32)).astype(np.float32)
+        grid.lo[:], grid.cell[:], grid.dims[:] = [float(v) for v in lo], [float(v) for v in cell], res
+        splits, rec = self._iso_passes(f, grid, level, border, bool(flip))
+        words = rec.view(torch.int32)
+        res = Isosurface(splits, rec[:, 0:9].unflatten(1, (3, 3)), words[:, 9], words[:, 10])
+        if from_numpy:
+            return Isosurface(*(x.cpu().numpy().copy() for x in res))
+        return res
+
+    def remesh(self, scene, resolution, field="winding", level=None, margin=1, **kw):
+        """A closed, uniformly tessellated mesh of `scene`'s surface, also where the scene has holes: the Isosurface of a field of the
+        scene sampled on a grid.  resolution: an int or (X, Y, Z), the cells across the scene's bounds; the grid is padded by
+        `margin` (>= 0) cells of that size on every side, so that the field is sampled outside the mesh.  field="winding":
+        windingGrid, level 0.5 by default and flip=True -- a scan with missing triangles comes out closed; field="sdf": sdfGrid,
+        level 0 by default (level = +-d is an offset surface).  The grid gets a border on the outside class, so the result is closed
+        whatever the field.  Further keywords go to windingGrid (beta) or sdfGrid (rule).  Device tensors come back; the scene needs
+        its BVH."""
+        if field not in ("winding", "sdf"):
+            raise DrtError(ERR_INVALID, "field = %r: 'winding' or 'sdf' expected" % (field,))
+        res = (resolution,) * 3 if isinstance(resolution, (int, np.integer)) and not isinstance(resolution, bool) else resolution
+        try:
+            ok = len(res) == 3 and all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) and v >= 1 for v in res)
+        except TypeError:
+            ok = False
+        if not ok:
+            raise DrtError(ERR_INVALID, "resolution = %r: a positive int or three of them expected" % (resolution,))
+        if isinstance(margin, bool) or not isinstance(margin, (int, np.integer)) or margin < 0:
+            raise DrtError(ERR_INVALID, "margin = %r: a non-negative integer expected" % (margin,))
+        if level is None:
+            level = 0.5 if field == "winding" else 0.0
+        try:
+            level = float(level)
+        except (TypeError, ValueError):
+            level = float("nan")
+        if not np.isfinite(level):
+            raise DrtError(ERR_INVALID, "level: a finite number expected")
+        nodes = scene.m_BVHNodes
+        if len(nodes) == 0:
+            raise DrtError(ERR_INVALID, "remesh: an empty scene has no bounds")
+        lo, hi = np.asarray(nodes[-1]["bmin"], np.float32), np.asarray(nodes[-1]["bmax"], np.float32)      # the root is the last node
+        res = np.asarray([int(v) for v in res], np.int64)
+        cell = ((hi - lo) / res.astype(np.float32)).astype(np.float32)
+        lo, hi = (lo - np.float32(margin) * cell).astype(np.float32), (hi + np.float32(margin) * cell).astype(np.float32)
+        res = tuple(int(v) for v in res + 2 * int(margin))
+        if field == "winding":
+            grid = self.windingGrid(scene, res, lo, hi, **kw)
+            return self.isosurface(grid, level, lo, hi, flip=True, border=min(0.0, level - 1.0))      # outside: w = 0, below
+        grid = self.sdfGrid(scene, res, lo, hi, **kw)
+        return self.isosurface(grid, level, lo, hi, border=level + float(cell.max()))                 # outside: farther out, above
 
     def debugWindingMoments(self, scene):
         """The node moments the winding calls use for this renderer's copy of `scene` (drt_debug_winding_moments): float32 [nodes, 8]

@@ -15,6 +15,7 @@
 #pragma once
 #include <cmath>
 #include <cstdint>
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -343,6 +344,16 @@ public:
     void WindingSignedDistance(const Scene &scene, const drt_point *points, drt_nearest *out, uint32_t n, float beta = 2.0f,
                                float threshold = 0.5f, void *stream = nullptr) {
         drt::check(drt_renderer_winding_signed_distance(handle, scene.handle, points, n, beta, threshold, out, stream));
+    }
+    // new: a watertight triangle mesh from a float32 [Z][Y][X] field by marching tetrahedra (drt_renderer_isosurface): one drt_iso_tri
+    // {v[3][3], cube, code, 0} per triangle in ascending cube, tetrahedron and table order, shared vertices bit-equal, normals towards
+    // f >= level (flip = 1: away from it).  Rows are the cubes along x of one (y, z): row r's records go to out[offsets[r] ..
+    // offsets[r + 1]), clamped to out_capacity, miss records (cube = 0xffffffff) behind them; counts[r] = all of them, stored or not.
+    // out null iff out_capacity == 0 (a pure count; offsets may be null then); border NaN = none.  No scene and no tree; triangle soup,
+    // no index buffer.  `grid` is host memory, the arrays are device arrays, out 16-byte aligned, enqueued on `stream`.
+    void Isosurface(const float *field, const drt_grid &grid, float level, const uint32_t *offsets, drt_iso_tri *out, uint32_t out_capacity,
+                    uint32_t *counts, bool flip = false, float border = std::numeric_limits<float>::quiet_NaN(), void *stream = nullptr) {
+        drt::check(drt_renderer_isosurface(handle, field, &grid, level, border, flip ? 1 : 0, offsets, out, out_capacity, counts, stream));
     }
     // new: the triangles each ray passes through, sorted by (t, prim) (drt_renderer_list_hits): ray i's records go to
     // hits[offsets[i] .. offsets[i+1]), clamped to hits_capacity, miss records behind them; counts[i] = all of them, stored or not.

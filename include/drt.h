@@ -36,7 +36,8 @@ extern "C" {
  * drt_renderer_chain_intersections), the triangle-distance entry point (drt_renderer_triangle_distance), the triangle-cast entry
  * point (drt_renderer_triangle_cast), the surface entry points (drt_renderer_surface_lookup, drt_renderer_surface_weights,
  * drt_renderer_sample_surface), the ambient-occlusion entry point (drt_renderer_ambient_occlusion) and the winding-number entry
- * points (drt_renderer_winding_numbers / _winding_inside / _winding_signed_distance) are additions to it */
+ * points (drt_renderer_winding_numbers / _winding_inside / _winding_signed_distance) are additions to it; so is the isosurface
+ * entry point (drt_renderer_isosurface) */
 #define DRT_ABI_VERSION 2
 
 typedef enum {
@@ -1326,6 +1327,71 @@ int           drt_renderer_winding_inside(drt_renderer *r, const drt_scene *scen
 int           drt_renderer_winding_signed_distance(drt_renderer *r, const drt_scene *scene, const drt_point *points, uint32_t n, float beta,
                                                    float threshold, drt_nearest *out, void *hip_stream);
 int           drt_debug_winding_moments(drt_renderer *r, const drt_scene *scene, float *out, size_t out_floats, uint32_t *count);
+
+/* ---- isosurface extraction (new; a watertight triangle mesh from a 3-D field -- the step that turns drt_renderer_signed_distance's
+ * and drt_renderer_winding_numbers' grids, or any field of the caller's, back into a surface) ----
+ * Marching tetrahedra on the six-tetrahedron Kuhn split of every cube around its 0 -> 7 diagonal.  Neighbouring cubes agree on every
+ * face diagonal, so the output is a closed, consistently oriented 2-manifold by construction wherever it does not leave the grid;
+ * there are no ambiguous cases, and the whole table is the 16 rows below.  The call needs no scene and no tree.
+ * All arithmetic is fp32 with one rounding per operation, in the order written.
+ * Field: float32 [Z][Y][X] on the renderer's device, x fastest; drt_grid {lo[3], cell[3], dims[3] = (X, Y, Z)} is a small POD read on
+ * the host.  Sample (i, j, k) lies at lo + ((float)idx + 0.5f) * cell per component -- the conversion, the add of 0.5f, the multiply
+ * and the add are each rounded on their own.  That is the layout of the Python wrapper's sdfGrid, whose grids pass straight in with
+ * cell = (hi - lo) / res per component in fp32.
+ * Cubes: one per 2x2x2 block of neighbouring samples; its corners are numbered c = dx + 2 dy + 4 dz.  Without a border there are
+ * (X-1)(Y-1)(Z-1) cubes and cube (cx, cy, cz) has its corner 0 at sample (cx, cy, cz).  The linear cube index is cx + nx * (cy + ny * cz)
+ * with nx, ny the cubes per axis.  Its tetrahedra, in this order, by corner: (0,1,3,7) (0,1,5,7) (0,2,3,7) (0,2,6,7) (0,4,5,7) (0,4,6,7).
+ * The local vertices 0, 1, 2, 3 of a tetrahedron are its corners in that order, so a smaller local number is a smaller corner number
+ * and a smaller linear sample index.
+ * Class: a corner is above iff f >= level (closed, the planes' convention; -0.0 >= 0.0 is above), otherwise below.  A tetrahedron
+ * with a corner that fails fabsf(f) <= FLT_MAX (a NaN or an infinity) emits nothing; the cube's other tetrahedra are not affected.
+ * Case: 4 bits, bit j set iff local vertex j is above.
+ * Vertex: on a tetrahedron edge (p, q), p < q, whose ends differ in class, always interpolated from the end a = p with the smaller
+ * corner number to the other end b = q:  t = (level - fa) / (fb - fa),  P = pa + (pb - pa) * t per component, pa and pb the sample
+ * positions above.  Every tetrahedron and every cube that shares a lattice edge therefore computes the same bits; no vertex is taken
+ * from a neighbour's arithmetic.
+ * Edges are numbered 0 = (0,1), 1 = (0,2), 2 = (0,3), 3 = (1,2), 4 = (1,3), 5 = (2,3) by local vertex.  Table, case: triangles of
+ * three edge numbers each, triangle 0 then triangle 1 (a 2-2 split is a quad split along a fixed diagonal):
+ *    0: --                  1: (0,2,1)             2: (0,3,4)             3: (1,3,4) (1,4,2)
+ *    4: (1,5,3)             5: (2,5,3) (2,3,0)     6: (0,1,5) (0,5,4)     7: (2,5,4)
+ *    8: (2,4,5)             9: (0,4,5) (0,5,1)    10: (3,5,2) (3,2,0)    11: (1,3,5)
+ *   12: (1,2,4) (1,4,3)    13: (0,4,3)            14: (0,1,2)            15: --
+ * The table is written for a tetrahedron of positive orientation.  Tetrahedra 1, 2 and 5 are mirror images: the second and third
+ * vertex of each of their triangles change places.  flip = 1 makes them change places once more, in every tetrahedron.  With flip = 0
+ * and positive cell components the geometric normal cross(v1 - v0, v2 - v0) points to the above side: a signed distance field that is
+ * negative inside gives outward faces.  flip = 1 is for fields that are large inside, such as winding numbers.  (A negative component
+ * of cell mirrors the lattice and with it the orientation.)
+ * Order: ascending cube index (z, then y, then x), then tetrahedron 0..5, then the table's triangle 0..1: the same bytes on every run.
+ * Record: a drt_iso_tri, 48 bytes, laid out as a drt_tri: v[3][3], then cube (the linear cube index), code = tetrahedron | case << 4,
+ * and a zero word.  A fill's output can be handed to drt_renderer_overlap_triangles and its relatives as it stands.  The miss record
+ * is cube = 0xffffffff and zeros everywhere else.
+ * Border: NaN means none.  A finite border puts one virtual layer of samples with that value around the grid on all six sides, at
+ * lattice indices -1 and dims[k], positioned by the same formula.  There are then (X+1)(Y+1)(Z+1) cubes, and cube (cx, cy, cz) has its
+ * corner 0 at lattice index (cx-1, cy-1, cz-1).  With a border on the outside class every surface closes inside the padded grid,
+ * whatever the field; without one a surface that reaches the grid's edge is open there.  Nothing of the padded field is materialised.
+ * Rows: a row is the run of cubes along x for one (cy, cz), row = cy + ny * cz; counts[row] is the number of triangles in the row and
+ * offsets holds rows + 1 values.  offsets / out / out_capacity / counts are exactly drt_renderer_plane_sections' segments with
+ * "row" for "plane" and 48-byte records: the clamped capacity cap_r, the first cap_r records stored, the miss record in the rest of
+ * the cap_r slots, nothing else in out written, counts[r] the total whether stored or not.  out is NULL iff out_capacity == 0: a pure
+ * count, which does not read offsets (it may be NULL).  counts may be NULL in a fill; both out and counts NULL is DRT_ERR_INVALID.
+ * Two passes give every triangle without a capacity guess: a count, an exclusive scan of the counts into offsets, a fill.
+ * Checks, each DRT_ERR_INVALID before any device work, in this order: NULL r, field or grid; flip other than 0 or 1; out and counts
+ * both NULL; out NULL without out_capacity 0 or the reverse; a fill without offsets; out 16-byte aligned and field, offsets and counts
+ * 4-byte aligned; an infinite border; every dims[k] >= 2 (>= 1 with a border); the sample count and the cube count < 2^31; level
+ * finite; lo and cell finite; a pending asynchronous batch; then field, offsets, out and counts must be device memory on the renderer's
+ * device.  hip_stream NULL = the renderer's stream; the call only enqueues.  The framebuffer, accumulation, sample count, counters,
+ * kernel info and kernel span are not touched.
+ * What this is not: no vertex index buffer -- it is triangle soup with bit-equal shared positions, and drt_tri_edge_adjacency recovers
+ * the connectivity; a sample exactly equal to level is above, t = 0 there, several edges yield the corner's own position, and
+ * zero-area triangles with zero-length edges appear, which the adjacency marks -2 -- shift level by an ulp or accept them; no gradient
+ * normals; marching tetrahedra emit roughly twice the triangles of marching cubes; the surface is that of the piecewise-linear
+ * interpolant and is no better; no simplification, no smoothing and no dual or sharp-feature methods; no drt_group_* form and no
+ * command line. */
+typedef struct drt_grid { float lo[3]; float cell[3]; uint32_t dims[3]; } drt_grid;                       /* 36 B, host memory */
+typedef struct drt_iso_tri { float v[3][3]; uint32_t cube; uint32_t code; uint32_t zero; } drt_iso_tri;   /* 48 B */
+int           drt_renderer_isosurface(drt_renderer *r, const float *field, const drt_grid *grid, float level, float border, int32_t flip,
+                                      const uint32_t *offsets, drt_iso_tri *out, uint32_t out_capacity, uint32_t *counts,
+                                      void *hip_stream);
 
 /* ---- first-hit guide buffers and the a-trous denoiser (new; the reference's TODO list, RayGen.cuh:13-21, starts with "DLSS 3.5
  * like features") ----
