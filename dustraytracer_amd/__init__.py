@@ -351,6 +351,9 @@ _sig("drt_renderer_winding_inside", C.c_int, _P, _P, _P, C.c_uint32, C.c_float, 
 _sig("drt_renderer_winding_signed_distance", C.c_int, _P, _P, _P, C.c_uint32, C.c_float, C.c_float, _P, _P)
 _sig("drt_debug_winding_moments", C.c_int, _P, _P, _P, C.c_size_t, _P)
 _sig("drt_renderer_isosurface", C.c_int, _P, _P, _P, C.c_float, C.c_float, C.c_int32, _P, _P, C.c_uint32, _P, _P)
+_sig("drt_renderer_weld", C.c_int, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_uint32, _P, _P)
+_sig("drt_renderer_vertex_normals", C.c_int, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_int32, _P, _P)
+_sig("drt_renderer_smooth_vertices", C.c_int, _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _P, _P, _P)
 _sig("drt_scene_edge_adjacency", C.c_int, _P, _P, C.c_uint32)
 _sig("drt_renderer_chain_sections", C.c_int, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _P)
 _sig("drt_tri_edge_adjacency", C.c_int, _P, C.c_uint32, _P, C.c_uint32)
@@ -791,6 +794,42 @@ class Isosurface(collections.namedtuple("Isosurface", "splits tris cube code")):
         host = (lambda a: a) if isinstance(self.tris, np.ndarray) else (lambda a: a.detach().cpu().numpy())
         tris = np.ascontiguousarray(host(self.tris), np.float32)
         nrm = np.repeat(host(self.faceNormals())[:, None, :], 3, axis=1)
+        sc = Scene()
+        sc.addMaterial(tuple(float(c) for c in albedo))
+        sc.setGeometry(tris, nrm, np.zeros((len(tris), 3, 2), np.float32), np.zeros(len(tris), np.int32))
+        return sc
+
+
+NORMAL_WEIGHTS = {"angle": 0, "area": 1}                                # Renderer.vertexNormals: drt.h DRT_NORMALS_*
+
+
+class IndexedMesh(collections.namedtuple("IndexedMesh", "vertices faces first")):
+    """A welded mesh (Renderer.weld / smooth): vertices [V, 3] float32, faces [N, 3] int32 -- the vertex id of every corner -- and first
+    [V] int32, the corner 3 t + k at which each vertex first appears.  Vertices are numbered by first appearance.  Device tensors or
+    numpy arrays."""
+
+    def triangles(self):
+        """float32 [N, 3, 3]: the positions gathered through faces -- triangle soup with bit-equal shared positions again, as every
+        other query takes it."""
+        if isinstance(self.vertices, np.ndarray):
+            return self.vertices[self.faces.astype(np.int64)]
+        import torch
+        return self.vertices[self.faces.to(torch.int64)]
+
+    def toScene(self, normals=None, albedo=(0.8, 0.8, 0.8)):
+        """A Scene of the triangles (Scene.setGeometry), zero uvs and one material of `albedo`.  normals: [V, 3] vertex normals, for
+        instance Renderer.vertexNormals(mesh), gathered per corner so that the renderer shades the mesh smooth; None: face normals
+        at the vertices, as Isosurface.toScene.  The caller builds the BVH."""
+        host = (lambda a: a) if isinstance(self.vertices, np.ndarray) else (lambda a: a.detach().cpu().numpy())
+        faces = host(self.faces).astype(np.int64)
+        tris = np.ascontiguousarray(host(self.vertices)[faces], np.float32)
+        if normals is None:
+            nrm = np.repeat(Isosurface(None, tris, None, None).faceNormals()[:, None, :], 3, axis=1)
+        else:
+            normals = normals if isinstance(normals, np.ndarray) else normals.detach().cpu().numpy()
+            if normals.dtype != np.float32 or normals.shape != host(self.vertices).shape:
+                raise DrtError(ERR_INVALID, "normals: float32 %s expected" % (tuple(host(self.vertices).shape),))
+            nrm = np.ascontiguousarray(normals[faces], np.float32)
         sc = Scene()
         sc.addMaterial(tuple(float(c) for c in albedo))
         sc.setGeometry(tris, nrm, np.zeros((len(tris), 3, 2), np.float32), np.zeros(len(tris), np.int32))
@@ -2671,6 +2710,156 @@ class Renderer:
             return self.isosurface(grid, level, lo, hi, flip=True, border=min(0.0, level - 1.0))      # outside: w = 0, below
         grid = self.sdfGrid(scene, res, lo, hi, **kw)
         return self.isosurface(grid, level, lo, hi, border=level + float(cell.max()))                 # outside: farther out, above
+
+    def _indexed(self, torch, mesh):
+        """(vertices [V, 3] float32, faces [N, 3] int32 on the renderer's device, contiguous, came_from_numpy) of an IndexedMesh or a
+        (vertices, faces, ...) tuple, checked."""
+        dev = torch.device("cuda", self._device)
+        try:
+            vertices, faces = mesh[0], mesh[1]
+        except (TypeError, IndexError, KeyError):
+            raise DrtError(ERR_INVALID, "mesh: an IndexedMesh or (vertices, faces) expected")
+        out = []
+        for a, what, np_dtype, dtype in ((vertices, "vertices", np.float32, torch.float32), (faces, "faces", np.int32, torch.int32)):
+            if isinstance(a, np.ndarray):
+                if a.dtype != np_dtype:
+                    raise DrtError(ERR_INVALID, "%s: dtype %s, %s expected" % (what, a.dtype, np.dtype(np_dtype).name))
+            elif torch.is_tensor(a):
+                if a.dtype != dtype:
+                    raise DrtError(ERR_INVALID, "%s: dtype %s, %s expected" % (what, a.dtype, dtype))
+                if a.device != dev:
+                    raise DrtError(ERR_INVALID, "%s: on %s, the renderer is on %s" % (what, a.device, dev))
+            else:
+                raise DrtError(ERR_INVALID, "%s: a numpy array or a torch tensor expected" % what)
+            if a.ndim != 2 or a.shape[1] != 3:
+                raise DrtError(ERR_INVALID, "%s: shape %s, [%s, 3] expected" % (what, tuple(a.shape), what[0].upper()))
+            out.append(a)
+        from_numpy = isinstance(vertices, np.ndarray)
+        if from_numpy != isinstance(faces, np.ndarray):
+            raise DrtError(ERR_INVALID, "vertices and faces: both numpy arrays or both torch tensors expected")
+        if 3 * out[1].shape[0] >= 2 ** 31 or out[0].shape[0] >= 2 ** 31:
+            raise DrtError(ERR_INVALID, "%d triangles, %d vertices: 3 N < 2^31 and V < 2^31 expected" % (out[1].shape[0], out[0].shape[0]))
+        if from_numpy:
+            return torch.from_numpy(np.ascontiguousarray(out[0])).to(dev), torch.from_numpy(np.ascontiguousarray(out[1])).to(dev), True
+        return out[0].contiguous(), out[1].contiguous(), False
+
+    def weld(self, tris):
+        """The index buffer of a triangle soup (drt_renderer_weld).  tris: an Isosurface, [N, 3, 3] float32 or a packed [N, 12]
+        (drt_tri).  Two corners are the same vertex iff their three 32-bit words are equal as integers -- triEdgeAdjacency's notion
+        of the same position: -0.0 and +0.0 differ, NaNs are compared by their bits, there is no tolerance and nothing is moved.
+        Vertices are numbered by first appearance.  IndexedMesh(vertices [V, 3] float32, faces [N, 3] int32, first [V] int32); the
+        result depends on the input bytes alone.  Made on the device in integers: a hash table of corner indices, a flag scan, a
+        scatter; V is read back to size the result, which is this call's one synchronisation.  A device tensor in, device tensors out
+        (enqueued on the current torch stream); numpy in, numpy out.  Needs no scene.
+        What it is not: no tolerance -- positions that differ in one bit stay apart; no cotangent weights, no feature preservation,
+        no boundary detection, no simplification, no vertex-to-triangle lists and no device edge adjacency from faces; no
+        RendererGroup and no command line."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        if isinstance(tris, Isosurface):
+            tris = tris.tris
+        if isinstance(tris, np.ndarray):
+            if tris.dtype != np.float32:
+                raise DrtError(ERR_INVALID, "tris: dtype %s, float32 expected" % tris.dtype)
+            t, from_numpy = tris, True
+        elif torch.is_tensor(tris):
+            if tris.dtype != torch.float32:
+                raise DrtError(ERR_INVALID, "tris: dtype %s, torch.float32 expected" % tris.dtype)
+            if tris.device != dev:
+                raise DrtError(ERR_INVALID, "tris: on %s, the renderer is on %s" % (tris.device, dev))
+            t, from_numpy = tris, False
+        else:
+            raise DrtError(ERR_INVALID, "tris: an Isosurface, a numpy array or a torch tensor expected")
+        shape = tuple(t.shape)
+        if not ((len(shape) == 2 and shape[1] == 12) or (len(shape) == 3 and shape[1:] == (3, 3))):
+            raise DrtError(ERR_INVALID, "tris: shape %s, [N, 3, 3] or a packed [N, 12] expected" % (shape,))
+        if 3 * shape[0] >= 2 ** 31:
+            raise DrtError(ERR_INVALID, "%d triangles: 3 N < 2^31 expected" % shape[0])
+        if from_numpy:
+            t = torch.from_numpy(np.ascontiguousarray(t)).to(dev)
+        if len(shape) == 2:
+            t, stride = t.contiguous(), 48
+        elif shape[0] and t.stride() == (12, 3, 1):        # a view of 48-byte records, as Isosurface.tris is: read in place
+            stride = 48
+        else:
+            t, stride = t.contiguous(), 36
+        n = shape[0]
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        faces = torch.empty((n, 3), dtype=torch.int32, device=dev)
+        first = torch.empty(3 * n, dtype=torch.int32, device=dev)
+        vertices = torch.empty((3 * n, 3), dtype=torch.float32, device=dev)
+        count = torch.zeros(1, dtype=torch.int32, device=dev)
+        _check(_lib.drt_renderer_weld(self._h, t.data_ptr() if n else None, n, stride, faces.data_ptr() if n else None,
+                                      first.data_ptr() if n else None, vertices.data_ptr() if n else None, 3 * n, count.data_ptr(), stream))
+        v = int(count.item())                    # the one synchronisation: the result's size
+        res = IndexedMesh(vertices[:v], faces, first[:v])
+        if from_numpy:
+            return IndexedMesh(*(x.cpu().numpy().copy() for x in res))
+        return res
+
+    def vertexNormals(self, mesh, weight="angle"):
+        """float32 [V, 3]: unit vertex normals of an IndexedMesh (drt_renderer_vertex_normals).  weight="angle": every triangle's
+        unit normal weighted by its interior angle at the vertex, which does not depend on how a surface is cut into triangles;
+        "area": the triangles' area vectors.  The sums are 64-bit fixed point added with integer atomics, so the bytes do not depend
+        on the order.  A triangle with an index outside [0, V), a coordinate that is not finite or no area adds nothing; a vertex
+        that nothing is added to gets zeros.  Device tensors in, a device tensor out (enqueued on the current torch stream); numpy
+        in, numpy out."""
+        if weight not in NORMAL_WEIGHTS:
+            raise DrtError(ERR_INVALID, "weight = %r: 'angle' or 'area' expected" % (weight,))
+        import torch                             # (only here: importing the package does not import torch)
+        vertices, faces, from_numpy = self._indexed(torch, mesh)
+        dev = vertices.device
+        out = torch.zeros_like(vertices)
+        _check(_lib.drt_renderer_vertex_normals(self._h, vertices.data_ptr(), vertices.shape[0], faces.data_ptr() if len(faces) else None,
+                                                faces.shape[0], NORMAL_WEIGHTS[weight], out.data_ptr(),
+                                                torch.cuda.current_stream(dev).cuda_stream))
+        return out.cpu().numpy() if from_numpy else out
+
+    def smooth(self, mesh, iterations=10, lam=0.5, mu=-0.53, fixed=None, factors=None):
+        """Laplacian / Taubin smoothing of an IndexedMesh (drt_renderer_smooth_vertices): an IndexedMesh with the same faces and
+        first.  Every step moves a vertex by a factor f towards the mean of its triangles' other vertices (the umbrella operator,
+        every edge of a closed manifold counted twice); `iterations` times the pair (lam, mu) -- Taubin's lambda | mu, which does
+        not shrink as plain Laplacian smoothing does -- or, with mu=None, `iterations` steps of lam; factors=[...] gives the steps'
+        factors outright, |f| <= 1 each.  fixed: bool or uint8 [V], vertices that stay, for instance a boundary.  The sums are 64-bit
+        fixed point, so the bytes do not depend on the order; shared vertices stay shared, so a watertight mesh stays watertight.
+        What it is not: no cotangent weights, no feature preservation, no boundary detection (pass fixed, e.g. from boundaryLoops),
+        no simplification."""
+        if factors is None:
+            try:
+                ok = not isinstance(iterations, bool) and int(iterations) == iterations and iterations >= 0
+            except (TypeError, ValueError):
+                ok = False
+            if not ok:
+                raise DrtError(ERR_INVALID, "iterations = %r: a non-negative integer expected" % (iterations,))
+            factors = ([lam] if mu is None else [lam, mu]) * int(iterations)
+        try:
+            fac = np.asarray([float(f) for f in factors], np.float32)
+        except (TypeError, ValueError):
+            raise DrtError(ERR_INVALID, "factors: numbers expected")
+        if not (np.abs(fac) <= 1).all():
+            raise DrtError(ERR_INVALID, "factors %r: |f| <= 1 expected" % (fac.tolist(),))
+        import torch                             # (only here: importing the package does not import torch)
+        vertices, faces, from_numpy = self._indexed(torch, mesh)
+        dev = vertices.device
+        fx = None
+        if fixed is not None:
+            if isinstance(fixed, np.ndarray):
+                fx = torch.from_numpy(np.ascontiguousarray(fixed != 0).view(np.uint8)).to(dev)
+            elif torch.is_tensor(fixed):
+                if fixed.device != dev:
+                    raise DrtError(ERR_INVALID, "fixed: on %s, the renderer is on %s" % (fixed.device, dev))
+                fx = (fixed != 0).to(torch.uint8).contiguous()
+            else:
+                raise DrtError(ERR_INVALID, "fixed: a numpy array or a torch tensor expected")
+            if tuple(fx.shape) != (vertices.shape[0],):
+                raise DrtError(ERR_INVALID, "fixed: shape %s, [%d] expected" % (tuple(fx.shape), vertices.shape[0]))
+        out = torch.empty_like(vertices)
+        _check(_lib.drt_renderer_smooth_vertices(self._h, vertices.data_ptr(), vertices.shape[0], faces.data_ptr() if len(faces) else None,
+                                                 faces.shape[0], fac.ctypes.data if len(fac) else None, len(fac),
+                                                 fx.data_ptr() if fx is not None else None, out.data_ptr(),
+                                                 torch.cuda.current_stream(dev).cuda_stream))
+        first = mesh[2] if len(mesh) > 2 else None
+        return IndexedMesh(out.cpu().numpy() if from_numpy else out, mesh[1], first)
 
     def debugWindingMoments(self, scene):
         """The node moments the winding calls use for this renderer's copy of `scene` (drt_debug_winding_moments): float32 [nodes, 8]

@@ -249,6 +249,12 @@ struct drt_renderer {
     DeviceArray<drt::WindingMoment> wn_moments;
     DeviceArray<float4> wn_sums;
     bool wn_valid = false;
+    // vertex welding, vertex normals and smoothing (drt_capi_weld.cpp): the scratch of kernel_weld.hip (weld.hpp), grown on demand as
+    // sf_cdf is and recomputed by every call -- the table of corner indices, a word per corner, a word per workgroup of the scan; the
+    // 64-bit fixed-point sums (and the counts behind them), the words of the maxima, the two position buffers the steps ping-pong between
+    DeviceArray<uint32_t> wd_table, wd_rep, wd_blocks, wd_max;
+    DeviceArray<unsigned long long> wd_acc;
+    DeviceArray<float> wd_pos[2];
 
     drt_renderer() = default;
     ~drt_renderer() {                          // the members release what they own, on this device

@@ -355,6 +355,27 @@ public:
                     uint32_t *counts, bool flip = false, float border = std::numeric_limits<float>::quiet_NaN(), void *stream = nullptr) {
         drt::check(drt_renderer_isosurface(handle, field, &grid, level, border, flip ? 1 : 0, offsets, out, out_capacity, counts, stream));
     }
+    // new: the index buffer of a triangle soup (drt_renderer_weld): n triangles `stride` bytes apart (36: float [N][3][3]; 48: drt_tri /
+    // drt_iso_tri), corners with bit-equal positions become one vertex, numbered by first appearance.  faces int32 [n][3]; first [V] the
+    // representative corner and vertices [V][3] its position, the first `capacity` of them (vertices may be null; first null iff
+    // capacity == 0); vertex_count one word, always the total.  No scene and no tree; device arrays, enqueued on `stream`.
+    void Weld(const void *tris, uint32_t n, uint32_t stride, int32_t *faces, int32_t *first, float *vertices, uint32_t capacity,
+              uint32_t *vertex_count, void *stream = nullptr) {
+        drt::check(drt_renderer_weld(handle, tris, n, stride, faces, first, vertices, capacity, vertex_count, stream));
+    }
+    // new: vertex normals of an indexed mesh (drt_renderer_vertex_normals): float [V][3], angle-weighted (DRT_NORMALS_ANGLE) or
+    // area-weighted (DRT_NORMALS_AREA), summed in 64-bit fixed point so the bytes do not depend on the order; zeros for a vertex that no
+    // triangle with an area names.
+    void VertexNormals(const float *vertices, uint32_t n_vertices, const int32_t *faces, uint32_t n_tris, float *out,
+                       int32_t weight = DRT_NORMALS_ANGLE, void *stream = nullptr) {
+        drt::check(drt_renderer_vertex_normals(handle, vertices, n_vertices, faces, n_tris, weight, out, stream));
+    }
+    // new: Laplacian / Taubin smoothing of an indexed mesh (drt_renderer_smooth_vertices): one umbrella step per factor (host memory,
+    // |f| <= 1; {0.5, -0.53, ...} is Taubin's), vertices with fixed[v] != 0 stay (fixed may be null).  out may not alias vertices.
+    void SmoothVertices(const float *vertices, uint32_t n_vertices, const int32_t *faces, uint32_t n_tris, const float *factors,
+                        uint32_t n_factors, float *out, const uint8_t *fixed = nullptr, void *stream = nullptr) {
+        drt::check(drt_renderer_smooth_vertices(handle, vertices, n_vertices, faces, n_tris, factors, n_factors, fixed, out, stream));
+    }
     // new: the triangles each ray passes through, sorted by (t, prim) (drt_renderer_list_hits): ray i's records go to
     // hits[offsets[i] .. offsets[i+1]), clamped to hits_capacity, miss records behind them; counts[i] = all of them, stored or not.
     // counts may be null, hits may be null iff hits_capacity == 0.  Device arrays, enqueued on `stream`.

@@ -37,7 +37,8 @@ extern "C" {
  * point (drt_renderer_triangle_cast), the surface entry points (drt_renderer_surface_lookup, drt_renderer_surface_weights,
  * drt_renderer_sample_surface), the ambient-occlusion entry point (drt_renderer_ambient_occlusion) and the winding-number entry
  * points (drt_renderer_winding_numbers / _winding_inside / _winding_signed_distance) are additions to it; so is the isosurface
- * entry point (drt_renderer_isosurface) */
+ * entry point (drt_renderer_isosurface), and so are the welding entry points (drt_renderer_weld / _vertex_normals /
+ * _smooth_vertices) */
 #define DRT_ABI_VERSION 2
 
 typedef enum {
@@ -1392,6 +1393,78 @@ typedef struct drt_iso_tri { float v[3][3]; uint32_t cube; uint32_t code; uint32
 int           drt_renderer_isosurface(drt_renderer *r, const float *field, const drt_grid *grid, float level, float border, int32_t flip,
                                       const uint32_t *offsets, drt_iso_tri *out, uint32_t out_capacity, uint32_t *counts,
                                       void *hip_stream);
+
+/* ---- vertex welding, vertex normals and smoothing (new; the map from the corners of a triangle soup to vertices, made on the device
+ * and in integers, and the two scatters over it) ----
+ * The three calls need no scene and no tree; they work on any triangles in device memory, drt_renderer_isosurface's output included.
+ *
+ * drt_renderer_weld -- the index buffer.  Input: n triangles at tris, `stride` bytes apart: 36 (float [N][3][3]) or 48 (drt_tri /
+ * drt_iso_tri records; only the nine floats are read).  3 n < 2^31.  Corner c = 3 t + k is vertex k of triangle t.
+ * Same vertex: two corners are the same vertex iff their three 32-bit words are equal as integers -- drt_tri_edge_adjacency's notion
+ * of the same position, so the two tables always agree.  -0.0 and +0.0 are different vertices, NaNs are compared by their bits; there
+ * is no tolerance and nothing is moved.
+ * rep[c] is the smallest corner index with c's position.  Vertices are numbered in ascending rep, that is by first appearance.
+ * Outputs: faces int32 [n][3], the vertex id of every corner; first int32 [V], the representative corner of each vertex; vertices
+ * float [V][3], its position copied bit for bit (may be NULL); vertex_count, one device word that is always the total V.
+ * capacity is the room in first and vertices, in vertices: 3 n always suffices.  A smaller capacity stores the first `capacity`
+ * vertices only; faces and the count are still complete.  first is NULL iff capacity == 0.
+ * The result depends on the input bytes alone: the same bytes on every run, in every launch shape.  (How: an insert-only hash table of
+ * corner indices claimed by compare-and-swap and lowered by an integer minimum, a flag scan, a scatter; the hash decides nothing
+ * that can be observed.  The restatement is a unique() over the 12-byte positions, reordered by first index.)  n == 0 stores V = 0.
+ * Checks, each DRT_ERR_INVALID before any device work, in this order: NULL r or vertex_count; a stride other than 36 or 48; 3 n >= 2^31;
+ * NULL tris or faces with n > 0; first NULL without capacity 0 or the reverse; vertices without first; every pointer 4-byte aligned;
+ * a pending asynchronous batch; then every pointer must be device memory on the renderer's device.  The table and the flags are the
+ * renderer's scratch, grown on demand; running out of device memory is DRT_ERR_DEVICE.
+ *
+ * drt_renderer_vertex_normals -- float [V][3] from vertices float [V][3], faces int32 [N][3] and a weight.  fp32 with one rounding
+ * per operation, in the order written, unless float64 is named; cross(a, b) = (a.y b.z - a.z b.y, a.z b.x - a.x b.z, a.x b.y - a.y b.x)
+ * and dot(a, b) = a.x b.x + a.y b.y + a.z b.z, summed left to right.  The sums over a vertex's triangles are int64 fixed point, added
+ * with integer atomics: the same bytes in any order.
+ * Per triangle (v0, v1, v2): n = cross(v1 - v0, v2 - v0), l = sqrtf(dot(n, n)).  The triangle adds nothing if an index is outside
+ * [0, V) (a bounds check, never a fault), if a coordinate of it is not finite, or if l is 0 or not finite.
+ * DRT_NORMALS_ANGLE (0): u = n / l, three divisions.  At corner k, a = v[(k+1) % 3] - v[k], b = v[(k+2) % 3] - v[k] and
+ * angle = atan2(l, dot(a, b)), the atan2 of the winding numbers above; its precondition y != 0 holds because l > 0.  For a finite x it
+ * gives the interior angle; x = +inf (the dot product overflowed) gives 0 and x = -inf gives 3.14159265f; a NaN x (+inf - inf in the
+ * dot product) gives a NaN angle, and a corner whose angle is not finite adds nothing.  Otherwise component j adds
+ * (int64) trunc((double)(angle * u_j) * 2^28) to vertex faces[t][k]; angle * u_j is one fp32 product.
+ * DRT_NORMALS_AREA (1): M is the largest |n_j| over all contributing triangles, e = floor(log2 M); every vertex of the triangle
+ * gets (int64) trunc((double)n_j * 2^(28 - e)), the power of two applied in float64, which is exact.  M = 0 gives all zeros.
+ * Result, in float64 and rounded once to fp32: x / sqrt(x x + y y + z z) with x, y, z the sums converted to float64 (the squares
+ * summed left to right), and zeros if the length is 0 -- a vertex in no contributing triangle.
+ * Checks, in this order: NULL r; a weight other than 0 or 1; V == 0 is a no-op; NULL vertices or out; NULL faces with N > 0; 4-byte
+ * alignment; 3 N >= 2^31; V >= 2^31; a pending batch; device memory.
+ *
+ * drt_renderer_smooth_vertices -- Laplacian and Taubin smoothing: out float [V][3] from vertices, faces, `n_factors` factors in
+ * host memory and an optional fixed uint8 [V] in device memory.  Step s uses f = factors[s]; |f| <= 1, else DRT_ERR_INVALID.
+ * {0.5, 0.5, ...} is Laplacian smoothing, {0.5, -0.53, 0.5, -0.53, ...} Taubin's lambda | mu.  out may not alias vertices; the steps
+ * between ping-pong in the renderer's scratch.  No factors: out is a copy of vertices.
+ * A step over its input positions p:  M is the largest finite |coordinate| of p, e = floor(log2 M), k = 27 - e (M = 0: k = 0), and
+ * q(x) = (int64) trunc((double)x * 2^k), so |q| < 2^28 in every step.  A triangle with an index outside [0, V) or a coordinate that
+ * is not finite adds nothing.  Every other triangle (a, b, c) adds q(p_b) + q(p_c) to acc[a] per component, and cyclically for b and
+ * c, and adds 2 to cnt of each; a triangle that names a vertex twice is not special-cased.  Update, in float64 with one rounding
+ * per operation, then one rounding to fp32:  m = (double)acc / ((double)cnt * 2^k),  p' = (float)((double)p + (double)f * (m - (double)p)).
+ * A vertex keeps its bits if cnt = 0, if fixed is set for it, or if a coordinate of it is not finite.  (With f = 0 a coordinate -0.0
+ * becomes +0.0 where m - p is not negative: that is the formula.)  Shared vertices stay shared because there is one position per id:
+ * a smoothed watertight mesh is watertight by construction.
+ * Checks, in this order: NULL r; NULL factors with n_factors > 0; |f| > 1 or a NaN; V == 0 is a no-op; then
+ * drt_renderer_vertex_normals' from "NULL vertices or out" to "V >= 2^31"; out overlapping vertices; a pending batch; device memory.
+ *
+ * All three: hip_stream NULL = the renderer's stream; the call only enqueues, in order with the other queries (the same event),
+ * because the calls share the renderer's scratch; legal on a sharded renderer; the framebuffer, accumulation, sample count, counters,
+ * kernel info and kernel span are not touched.
+ * What this is not: no cotangent weights -- the umbrella operator shrinks and slides vertices along the surface; no feature
+ * preservation; no boundary detection -- pass fixed, for instance from drt_renderer_boundary_loops; no simplification; no
+ * vertex-to-triangle lists; no device edge adjacency from faces; welding is by bit-equal positions only, with no tolerance; no
+ * drt_group_* form and no command line. */
+#define DRT_NORMALS_ANGLE 0
+#define DRT_NORMALS_AREA 1
+int           drt_renderer_weld(drt_renderer *r, const void *tris, uint32_t n, uint32_t stride, int32_t *faces, int32_t *first,
+                                float *vertices, uint32_t capacity, uint32_t *vertex_count, void *hip_stream);
+int           drt_renderer_vertex_normals(drt_renderer *r, const float *vertices, uint32_t n_vertices, const int32_t *faces,
+                                          uint32_t n_tris, int32_t weight, float *out, void *hip_stream);
+int           drt_renderer_smooth_vertices(drt_renderer *r, const float *vertices, uint32_t n_vertices, const int32_t *faces,
+                                           uint32_t n_tris, const float *factors, uint32_t n_factors, const uint8_t *fixed, float *out,
+                                           void *hip_stream);
 
 /* ---- first-hit guide buffers and the a-trous denoiser (new; the reference's TODO list, RayGen.cuh:13-21, starts with "DLSS 3.5
  * like features") ----
