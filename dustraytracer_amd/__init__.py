@@ -354,6 +354,7 @@ _sig("drt_renderer_isosurface", C.c_int, _P, _P, _P, C.c_float, C.c_float, C.c_i
 _sig("drt_renderer_weld", C.c_int, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_uint32, _P, _P)
 _sig("drt_renderer_vertex_normals", C.c_int, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_int32, _P, _P)
 _sig("drt_renderer_smooth_vertices", C.c_int, _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _P, _P, _P)
+_sig("drt_renderer_simplify", C.c_int, _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_int32, _P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P)
 _sig("drt_scene_edge_adjacency", C.c_int, _P, _P, C.c_uint32)
 _sig("drt_renderer_chain_sections", C.c_int, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _P)
 _sig("drt_tri_edge_adjacency", C.c_int, _P, C.c_uint32, _P, C.c_uint32)
@@ -834,6 +835,19 @@ class IndexedMesh(collections.namedtuple("IndexedMesh", "vertices faces first"))
         sc.addMaterial(tuple(float(c) for c in albedo))
         sc.setGeometry(tris, nrm, np.zeros((len(tris), 3, 2), np.float32), np.zeros(len(tris), np.int32))
         return sc
+
+
+SIMPLIFY_PLACEMENTS = {"mean": 0, "quadric": 1}                         # Renderer.simplify: drt.h DRT_SIMPLIFY_*
+
+
+class SimplifiedMesh(collections.namedtuple("SimplifiedMesh", "vertices faces first cluster source")):
+    """A simplified mesh (Renderer.simplify): vertices [C, 3] float32, one per cluster; faces [M, 3] int32, the cluster ids of the
+    surviving triangles in input order; first [C] int32, the smallest input vertex of each cluster; cluster [V] int32, the cluster id
+    of every input vertex; source [M] int32, the input triangle of every output triangle.  The first three fields are an
+    IndexedMesh's, so vertexNormals, smooth and toScene(normals=) take it unchanged.  Device tensors or numpy arrays."""
+
+    triangles = IndexedMesh.triangles
+    toScene = IndexedMesh.toScene
 
 
 def triEdgeAdjacency(tris):
@@ -2860,6 +2874,126 @@ class Renderer:
                                                  torch.cuda.current_stream(dev).cuda_stream))
         first = mesh[2] if len(mesh) > 2 else None
         return IndexedMesh(out.cpu().numpy() if from_numpy else out, mesh[1], first)
+
+    @staticmethod
+    def _simplify_grid(vertices, resolution, cell, lo, hi):
+        """The drt_grid of Renderer.simplify's keywords; vertices: a float32 [V, 3] numpy array or None (an explicit box)."""
+        def bad(what):
+            return DrtError(ERR_INVALID, what)
+        if (resolution is None) == (cell is None):
+            raise bad("simplify: exactly one of resolution and cell expected")
+        if (lo is None) != (hi is None):
+            raise bad("lo and hi: both or neither expected")
+        if resolution is not None:
+            res = (resolution,) * 3 if isinstance(resolution, (int, np.integer)) and not isinstance(resolution, bool) else resolution
+            try:
+                ok = len(res) == 3 and all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) and v >= 1 for v in res)
+            except TypeError:
+                ok = False
+            if not ok:
+                raise bad("resolution = %r: a positive int or three of them expected" % (resolution,))
+            res = np.asarray([int(v) for v in res], np.int64)
+        else:
+            try:
+                cell = float(cell)
+            except (TypeError, ValueError):
+                cell = float("nan")
+            if not (np.isfinite(np.float32(cell)) and np.float32(cell) > 0):
+                raise bad("cell = %r: one finite edge length greater than 0 expected" % (cell,))
+        if lo is not None:
+            try:
+                lo, hi = np.asarray(lo, np.float32).reshape(3), np.asarray(hi, np.float32).reshape(3)
+            except (TypeError, ValueError):
+                raise bad("lo and hi: three numbers each expected")
+            if not (np.isfinite(lo).all() and np.isfinite(hi).all() and (hi > lo).all()):
+                raise bad("lo and hi: finite values with lo < hi expected")
+            if resolution is not None:
+                size = ((hi - lo) / res.astype(np.float32)).astype(np.float32)      # the isosurface's rule: nothing is padded
+            else:
+                size = np.full(3, cell, np.float32)
+                res = np.maximum(1, np.ceil((hi.astype(np.float64) - lo.astype(np.float64)) / np.float64(size[0]))).astype(np.int64)
+        else:
+            # the default box: lo = the smallest finite coordinate per axis, e = the largest - lo in float64, widened by 2^-16 of itself
+            # at the upper end so that (p - lo) / cell < dims also after the three fp32 roundings of the rule (2^-24 each)
+            finite = vertices[np.isfinite(vertices).all(axis=1)] if vertices is not None and len(vertices) else np.zeros((0, 3), np.float32)
+            if len(finite):
+                low = finite.min(axis=0).astype(np.float64)
+                e = finite.max(axis=0).astype(np.float64) - low
+            else:
+                low, e = np.zeros(3), np.zeros(3)
+            lo, pad = low.astype(np.float32), e * (1.0 + 2.0 ** -16)
+            if resolution is not None:
+                size = np.where(e > 0, pad / res, 1.0).astype(np.float32)             # a flat axis: one cell of size 1 holds it
+            else:
+                size = np.full(3, cell, np.float32)
+                res = np.maximum(1, np.ceil(pad / np.float64(size[0]))).astype(np.int64)
+        if not (np.isfinite(size).all() and (size > 0).all()):
+            raise bad("cell size %r: finite and greater than 0 expected (is the box too small or too large for float32?)" % (size.tolist(),))
+        if int(res[0]) * int(res[1]) * int(res[2]) >= 2 ** 31:
+            raise bad("a grid of %d x %d x %d cells: fewer than 2^31 expected" % tuple(int(v) for v in res))
+        grid = _Grid()
+        grid.lo[:], grid.cell[:], grid.dims[:] = [float(v) for v in lo], [float(v) for v in size], [int(v) for v in res]
+        return grid
+
+    def simplify(self, mesh, resolution=None, cell=None, lo=None, hi=None, placement="quadric"):
+        """A smaller mesh by vertex clustering (drt_renderer_simplify): the vertices in one cell of a grid become one vertex, and the
+        triangles that still have three different vertices survive, in input order.  mesh: an IndexedMesh or (vertices, faces), as
+        vertexNormals takes it.  resolution: an int or (X, Y, Z), the cells across [lo, hi]; or cell: one edge length, with the cell
+        counts derived from it.  lo, hi: the box; vertices outside it, and vertices that are not finite, stay as they are, so a box
+        over part of a mesh simplifies that part.  With an explicit box cell = (hi - lo) / resolution in float32, as for isosurface,
+        and a vertex on hi is outside.  The default box holds every finite vertex: lo is the smallest finite coordinate per axis
+        and the extent e = largest - lo is widened by e 2^-16 at the upper end (cell = e (1 + 2^-16) / resolution, or
+        ceil(e (1 + 2^-16) / cell) cells), more than the rule's three float32 roundings can take back; an axis without extent gets
+        one cell layer of size 1.
+        placement="quadric": the point of the cell that minimises the summed squared distances to the planes of the cluster's
+        triangles, area-weighted and drawn to the mean where the planes leave it free (Lindstrom), so corners and edges come back;
+        an optimum outside its cell falls back to the mean.  "mean": the mean of the members.  The sums are 64-bit fixed point
+        added with integer atomics and the finish is float64, so the result depends on the input bytes alone.
+        SimplifiedMesh(vertices [C, 3], faces [M, 3], first [C], cluster [V], source [M]); a closed oriented mesh in gives a mesh in
+        which every directed edge (a, b) appears as often as (b, a).  The call allocates V and N as capacities and reads the two
+        counts back once -- its one synchronisation -- then slices.  (The default box of device tensors is made on the device and
+        its six numbers are read back first, because the grid is host memory: pass lo and hi to avoid that second wait.)  Device
+        tensors in, device tensors out (enqueued on the current torch stream); numpy in, numpy out.  Needs no scene.
+        What it is not: no edge collapse, no error bound and no target count; duplicate and opposite triangle pairs stay;
+        non-manifold edges that clustering creates are not repaired; no attribute quadrics, no interpolated normals or uvs; no
+        adaptive cells; no RendererGroup and no command line."""
+        if placement not in SIMPLIFY_PLACEMENTS:
+            raise DrtError(ERR_INVALID, "placement = %r: 'mean' or 'quadric' expected" % (placement,))
+        if lo is not None and hi is not None:
+            grid = self._simplify_grid(None, resolution, cell, lo, hi)
+        else:
+            grid = None
+            self._simplify_grid(np.zeros((0, 3), np.float32), resolution, cell, lo, hi)      # the keywords' own errors first
+        import torch                             # (only here: importing the package does not import torch)
+        vertices, faces, from_numpy = self._indexed(torch, mesh)
+        dev = vertices.device
+        if grid is None:
+            if from_numpy:
+                host = np.ascontiguousarray(mesh[0])
+            elif len(vertices):                  # the box of the finite vertices, made on the device: six numbers come back
+                fin = torch.isfinite(vertices).all(dim=1, keepdim=True)
+                inf = torch.tensor(float("inf"), device=dev)
+                host = torch.stack([torch.where(fin, vertices, inf).amin(dim=0), torch.where(fin, vertices, -inf).amax(dim=0)]).cpu().numpy()
+            else:
+                host = np.zeros((0, 3), np.float32)
+            grid = self._simplify_grid(host, resolution, cell, None, None)
+        nv, nt = int(vertices.shape[0]), int(faces.shape[0])
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        cluster = torch.empty(nv, dtype=torch.int32, device=dev)
+        out_v = torch.empty((nv, 3), dtype=torch.float32, device=dev)
+        first = torch.empty(nv, dtype=torch.int32, device=dev)
+        out_f = torch.empty((nt, 3), dtype=torch.int32, device=dev)
+        source = torch.empty(nt, dtype=torch.int32, device=dev)
+        counts = torch.zeros(2, dtype=torch.int32, device=dev)
+        _check(_lib.drt_renderer_simplify(self._h, vertices.data_ptr() if nv else None, nv, faces.data_ptr() if nt else None, nt, C.byref(grid),
+                                          SIMPLIFY_PLACEMENTS[placement], cluster.data_ptr() if nv else None,
+                                          out_v.data_ptr() if nv else None, first.data_ptr() if nv else None, nv,
+                                          out_f.data_ptr() if nt else None, source.data_ptr() if nt else None, nt, counts.data_ptr(), stream))
+        c, m = (int(x) for x in counts.tolist())  # the one synchronisation: the result's sizes
+        res = SimplifiedMesh(out_v[:c], out_f[:m], first[:c], cluster, source[:m])
+        if from_numpy:
+            return SimplifiedMesh(*(x.cpu().numpy().copy() for x in res))
+        return res
 
     def debugWindingMoments(self, scene):
         """The node moments the winding calls use for this renderer's copy of `scene` (drt_debug_winding_moments): float32 [nodes, 8]

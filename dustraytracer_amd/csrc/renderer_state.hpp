@@ -255,6 +255,10 @@ struct drt_renderer {
     DeviceArray<uint32_t> wd_table, wd_rep, wd_blocks, wd_max;
     DeviceArray<unsigned long long> wd_acc;
     DeviceArray<float> wd_pos[2];
+    // mesh simplification (drt_capi_simplify.cpp): the scratch of kernel_simplify.hip (simplify.hpp) beyond what it shares with the
+    // welding calls above (the table, the representatives, the block totals, the maximum, the 64-bit sums) -- a key per vertex and a
+    // member count per cluster
+    DeviceArray<uint32_t> sp_key, sp_cnt;
 
     drt_renderer() = default;
     ~drt_renderer() {                          // the members release what they own, on this device

@@ -376,6 +376,17 @@ public:
                         uint32_t n_factors, float *out, const uint8_t *fixed = nullptr, void *stream = nullptr) {
         drt::check(drt_renderer_smooth_vertices(handle, vertices, n_vertices, faces, n_tris, factors, n_factors, fixed, out, stream));
     }
+    // new: mesh simplification by vertex clustering (drt_renderer_simplify): the vertices of one cell of `grid` become one vertex, placed
+    // at the cell's quadric optimum (DRT_SIMPLIFY_QUADRIC) or at the members' mean (DRT_SIMPLIFY_MEAN); vertices outside the grid stay.
+    // cluster int32 [V] the new id of every vertex; out_vertices [C][3] and first [C], the first vertex_capacity of them; out_faces
+    // [M][3] and source [M] (the input triangle), the first tri_capacity of them; counts two words, C then M, always the totals.
+    // A pair of outputs is null iff its capacity is 0.  No scene and no tree; device arrays, enqueued on `stream`.
+    void Simplify(const float *vertices, uint32_t n_vertices, const int32_t *faces, uint32_t n_tris, const drt_grid &grid, int32_t *cluster,
+                  float *out_vertices, int32_t *first, uint32_t vertex_capacity, int32_t *out_faces, int32_t *source, uint32_t tri_capacity,
+                  uint32_t *counts, int32_t placement = DRT_SIMPLIFY_QUADRIC, void *stream = nullptr) {
+        drt::check(drt_renderer_simplify(handle, vertices, n_vertices, faces, n_tris, &grid, placement, cluster, out_vertices, first,
+                                         vertex_capacity, out_faces, source, tri_capacity, counts, stream));
+    }
     // new: the triangles each ray passes through, sorted by (t, prim) (drt_renderer_list_hits): ray i's records go to
     // hits[offsets[i] .. offsets[i+1]), clamped to hits_capacity, miss records behind them; counts[i] = all of them, stored or not.
     // counts may be null, hits may be null iff hits_capacity == 0.  Device arrays, enqueued on `stream`.

@@ -38,7 +38,7 @@ extern "C" {
  * drt_renderer_sample_surface), the ambient-occlusion entry point (drt_renderer_ambient_occlusion) and the winding-number entry
  * points (drt_renderer_winding_numbers / _winding_inside / _winding_signed_distance) are additions to it; so is the isosurface
  * entry point (drt_renderer_isosurface), and so are the welding entry points (drt_renderer_weld / _vertex_normals /
- * _smooth_vertices) */
+ * _smooth_vertices), and so is the simplification entry point (drt_renderer_simplify) */
 #define DRT_ABI_VERSION 2
 
 typedef enum {
@@ -1465,6 +1465,79 @@ int           drt_renderer_vertex_normals(drt_renderer *r, const float *vertices
 int           drt_renderer_smooth_vertices(drt_renderer *r, const float *vertices, uint32_t n_vertices, const int32_t *faces,
                                            uint32_t n_tris, const float *factors, uint32_t n_factors, const uint8_t *fixed, float *out,
                                            void *hip_stream);
+
+/* ---- mesh simplification (new; vertex clustering on a grid with a mean or a quadric-optimal representative: one map from vertices
+ * to clusters, made on the device and in integers as the weld's map is, and the sums over it) ----
+ * drt_renderer_simplify needs no scene and no tree; it works on any indexed mesh in device memory, drt_renderer_weld's output
+ * included: vertices float [V][3], faces int32 [N][3].  Rossignac-Borrel cells with Lindstrom's placement: every grid cell that holds
+ * vertices becomes one vertex, and the triangles that still have three different vertices survive.  The result does not depend on
+ * any order of operations; there is no edge collapse.
+ * fp32 with one rounding per operation, in the order written, unless float64 is named; cross and dot as for the vertex normals above.
+ * Grid: the drt_grid POD of the isosurface call, read on the host: lo finite, cell finite and greater than 0, dims at least 1 and
+ * X Y Z < 2^31, with (X, Y, Z) = dims.
+ * Cell of a vertex: per axis f = (p - lo) / cell, two fp32 operations.  The vertex is in the grid iff its three coordinates are
+ * finite and 0 <= f < (float)dims on every axis; then i = (int)f (i < dims follows, also where (float)dims is rounded) and its key is
+ * ix + X (iy + Y iz).  Nothing is clamped.
+ * Clusters: in-grid vertices with the same key are one cluster; every other vertex -- outside the grid, or not finite -- is a cluster
+ * of its own, so a grid over part of a mesh simplifies that part and leaves the rest alone.  first[c] is the smallest input vertex in
+ * cluster c; clusters are numbered in ascending first; cluster[v] is total: every vertex gets an id.
+ * Position of a cluster: a cluster with one member copies that member's 12 bytes.  Any other cluster lies in a cell (ix, iy, iz) with
+ * the centre g = lo + ((float)i + 0.5f) * cell per component, the grid-sample rule above, and a member or a corner at p has
+ * r = (p - g) / cell per component.
+ * Mean: acc_a += (int64) trunc((double)r_a * 2^30) per component and cnt += 1 per member;  m_a = (double)acc_a / ((double)cnt * 2^30).
+ * Quadric: per triangle (v0, v1, v2): n = cross(v1 - v0, v2 - v0), l = sqrtf(dot(n, n)), u = n / l, three divisions.  A triangle
+ * contributes iff its indices are inside [0, V) (a bounds check, never a fault), its nine coordinates are finite and l is finite and
+ * greater than 0.  L is the largest l of the contributing triangles, e = floor(log2 L), and w = (float)((double)l * 2^-(e+1)): the power
+ * of two applied in float64, which is exact, then one rounding.  Each corner k of a contributing triangle whose vertex is in the grid
+ * and in a cluster c with more than one member adds, with r taken at that corner and s = dot(u, r):
+ *   (int64) trunc((double)((w * u_i) * u_j) * 2^30) to A_ij[c] for the six entries ij = 00, 01, 02, 11, 12, 22, and
+ *   (int64) trunc((double)((w * u_i) * s) * 2^30) to b_i[c].
+ * A triangle with two corners in one cluster is not special-cased: each corner adds.  All sums are int64, added with integer
+ * atomics: the same bytes in any order.
+ * Finish, in float64 with one rounding per operation; A_ij, b_i below are the sums converted to float64:
+ *   tr = (A00 + A11) + A22,  lam = tr * 2^-10,  a00 = A00 + lam, a11 = A11 + lam, a22 = A22 + lam, a01 = A01, a02 = A02, a12 = A12,
+ *   d_i = b_i + lam * m_i,
+ *   c0 = a11 * a22 - a12 * a12,  c1 = a01 * a22 - a12 * a02,  c2 = a01 * a12 - a11 * a02,  det = (a00 * c0 - a01 * c1) + a02 * c2,
+ *   e0 = d1 * a22 - a12 * d2,  e1 = d1 * a12 - a11 * d2,  e2 = a01 * d2 - d1 * a02,
+ *   x0 = ((d0 * c0 - a01 * e0) + a02 * e1) / det,  x1 = ((a00 * e0 - d0 * c1) + a02 * e2) / det,  x2 = ((d0 * c2 - a00 * e1) - a01 * e2) / det:
+ * Cramer's rule for (A + lam I) x = b + lam m, the minimiser of the summed squared plane distances, drawn to the mean where the planes
+ * leave it free.  If tr == 0, or any x_a is not finite, or any |x_a| > 0.5, then x = m: an optimum outside its cell is not trusted.
+ * DRT_SIMPLIFY_MEAN (0) is x = m throughout and reads no triangle for the positions; DRT_SIMPLIFY_QUADRIC (1) is the above.
+ * Position: (float)((double)g_a + x_a * (double)cell_a).
+ * Triangles: input triangle t survives iff its three indices are inside [0, V) and its three cluster ids differ pairwise.  Survivors
+ * keep input order; out_faces[m] holds the cluster ids and source[m] = t, so per-triangle attributes can follow.  Duplicate triangles
+ * are not removed, and that makes the boundary identity exact: a closed oriented input gives an output in which every directed edge
+ * (a, b) appears as often as (b, a).
+ * Outputs: cluster int32 [V]; out_vertices float [C][3] and first int32 [C]; out_faces int32 [M][3] and source int32 [M]; counts, two
+ * device words that are always complete: C, then M.  Only the first vertex_capacity clusters and the first tri_capacity triangles
+ * are stored (V and N always suffice); cluster and counts are always complete.  out_vertices and first are NULL iff vertex_capacity
+ * == 0, out_faces and source are NULL iff tri_capacity == 0.
+ * Consequences: a grid so fine that every cluster is a singleton returns vertices and the surviving faces byte for byte; the result
+ * depends on the input bytes alone: the same bytes on every run, in every launch shape.  (How: an insert-only hash table of vertex
+ * indices keyed by the cell, claimed by compare-and-swap and lowered by an integer minimum, a flag scan, a scatter -- the weld's
+ * shape; the hash decides nothing that can be observed.)
+ * Checks, each DRT_ERR_INVALID before any device work, in this order: NULL r, grid or counts; NULL vertices or cluster with V > 0; NULL
+ * faces with N > 0; out_vertices or first NULL without vertex_capacity 0 or the reverse; out_faces or source NULL without tri_capacity
+ * 0 or the reverse; a placement other than 0 or 1; lo not finite; cell not finite or not greater than 0; a dims below 1; X Y Z >= 2^31;
+ * V >= 2^31; 3 N >= 2^31.  V == 0 is a no-op that stores C = M = 0: of the checks below only those of counts apply to it.  Then every
+ * pointer 4-byte aligned; an output overlapping vertices or faces; a pending asynchronous batch; then every pointer must be device
+ * memory on the renderer's device.  The table, the keys and the sums are the renderer's scratch, grown on demand (96 bytes of sums
+ * per input vertex with quadric placement, 24 with mean); running out of device memory is DRT_ERR_DEVICE.
+ * hip_stream NULL = the renderer's stream; the call only enqueues, in order with the other queries (the same event), because it
+ * shares the renderer's scratch; legal on a sharded renderer; the framebuffer, accumulation, sample count, counters, kernel info and
+ * kernel span are not touched.
+ * What this is not: no edge collapse and no error-bounded or target-count simplification -- the grid is the only control; duplicate
+ * and opposite triangle pairs are not removed; clustering can create non-manifold edges and vertices where a cell holds two sheets of
+ * a surface, and they are not repaired; no attribute quadrics, no interpolated normals or uvs -- source says which input triangle an
+ * output triangle was; no adaptive (octree) cells; the cross product and dot(n, n) are fp32, so triangles with edges below about
+ * 2^-37 or above about 2^31 under- or overflow there and contribute nothing, and a cluster without contributions gets the mean; no
+ * drt_group_* form and no command line. */
+#define DRT_SIMPLIFY_MEAN 0
+#define DRT_SIMPLIFY_QUADRIC 1
+int           drt_renderer_simplify(drt_renderer *r, const float *vertices, uint32_t n_vertices, const int32_t *faces, uint32_t n_tris,
+                                    const drt_grid *grid, int32_t placement, int32_t *cluster, float *out_vertices, int32_t *first,
+                                    uint32_t vertex_capacity, int32_t *out_faces, int32_t *source, uint32_t tri_capacity,
+                                    uint32_t *counts, void *hip_stream);
 
 /* ---- first-hit guide buffers and the a-trous denoiser (new; the reference's TODO list, RayGen.cuh:13-21, starts with "DLSS 3.5
  * like features") ----
