@@ -355,6 +355,10 @@ _sig("drt_renderer_weld", C.c_int, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, C
 _sig("drt_renderer_vertex_normals", C.c_int, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_int32, _P, _P)
 _sig("drt_renderer_smooth_vertices", C.c_int, _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_uint32, _P, _P, _P)
 _sig("drt_renderer_simplify", C.c_int, _P, _P, C.c_uint32, _P, C.c_uint32, _P, C.c_int32, _P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P)
+_sig("drt_renderer_tri_adjacency", C.c_int, _P, _P, C.c_uint32, C.c_uint32, _P, _P, _P, C.c_uint32, _P, _P)
+_sig("drt_renderer_face_adjacency", C.c_int, _P, _P, C.c_uint32, _P, _P, _P, C.c_uint32, _P, _P)
+_sig("drt_renderer_boundary_vertices", C.c_int, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P)
+_sig("drt_renderer_adjacency_route", C.c_int, _P)
 _sig("drt_scene_edge_adjacency", C.c_int, _P, _P, C.c_uint32)
 _sig("drt_renderer_chain_sections", C.c_int, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _P)
 _sig("drt_tri_edge_adjacency", C.c_int, _P, C.c_uint32, _P, C.c_uint32)
@@ -837,6 +841,16 @@ class IndexedMesh(collections.namedtuple("IndexedMesh", "vertices faces first"))
         return sc
 
 
+class MeshEdges(collections.namedtuple("MeshEdges", "adj edge half_edge count")):
+    """Renderer.edgeAdjacency(mesh, edges=True): adj [N, 3] int32, the twin of every half-edge (-1 boundary, -2 every other case);
+    edge [N, 3] int32, the undirected edge of every half-edge, numbered by first appearance, -1 for a zero-length one; half_edge [E]
+    int32, the smallest half-edge of every edge; count = E.  Device tensors or numpy arrays."""
+
+    def euler(self, n_vertices):
+        """V - E + F: 2 per closed surface of genus 0."""
+        return int(n_vertices) - int(self.count) + int(self.adj.shape[0])
+
+
 SIMPLIFY_PLACEMENTS = {"mean": 0, "quadric": 1}                         # Renderer.simplify: drt.h DRT_SIMPLIFY_*
 
 
@@ -855,7 +869,8 @@ def triEdgeAdjacency(tris):
     tris -- [N, 3, 3] float32 or a packed [N, 12] (drt_tri) -- in the caller's order: the twin half-edge 3 * i' + e' of edge e (vertex e
     to vertex (e + 1) % 3) of triangle i by bit-equal positions, -1 on a boundary edge, -2 where the edge is non-manifold, flipped or
     of zero length.  What Renderer.chainIntersections takes as query_adj.  The table is made on the host: numpy in, numpy out; a
-    device tensor is copied to the host for it, and a device tensor comes back."""
+    device tensor is copied to the host for it, and a device tensor comes back.  Renderer.edgeAdjacency makes the same bytes on
+    the device, in milliseconds where this sorts for a second, and takes index buffers as well."""
     as_numpy = isinstance(tris, np.ndarray)
     if as_numpy:
         host = tris
@@ -2215,7 +2230,10 @@ class Renderer:
         if query_adj is None:
             if tris is None:
                 raise DrtError(ERR_INVALID, "one of tris and query_adj expected: the curve crosses queries through the query mesh's edge adjacency")
-            query_adj = triEdgeAdjacency(tris)
+            if torch.is_tensor(tris) and tris.device == dev and tris.dtype == torch.float32:
+                query_adj = self.edgeAdjacency(tris)      # made on the device: the same bytes
+            else:
+                query_adj = triEdgeAdjacency(tris)
         if isinstance(query_adj, np.ndarray):
             if query_adj.dtype != np.int32:
                 raise DrtError(ERR_INVALID, "query_adj: dtype %s, int32 expected" % query_adj.dtype)
@@ -2757,18 +2775,9 @@ class Renderer:
             return torch.from_numpy(np.ascontiguousarray(out[0])).to(dev), torch.from_numpy(np.ascontiguousarray(out[1])).to(dev), True
         return out[0].contiguous(), out[1].contiguous(), False
 
-    def weld(self, tris):
-        """The index buffer of a triangle soup (drt_renderer_weld).  tris: an Isosurface, [N, 3, 3] float32 or a packed [N, 12]
-        (drt_tri).  Two corners are the same vertex iff their three 32-bit words are equal as integers -- triEdgeAdjacency's notion
-        of the same position: -0.0 and +0.0 differ, NaNs are compared by their bits, there is no tolerance and nothing is moved.
-        Vertices are numbered by first appearance.  IndexedMesh(vertices [V, 3] float32, faces [N, 3] int32, first [V] int32); the
-        result depends on the input bytes alone.  Made on the device in integers: a hash table of corner indices, a flag scan, a
-        scatter; V is read back to size the result, which is this call's one synchronisation.  A device tensor in, device tensors out
-        (enqueued on the current torch stream); numpy in, numpy out.  Needs no scene.
-        What it is not: no tolerance -- positions that differ in one bit stay apart; no cotangent weights, no feature preservation,
-        no boundary detection, no simplification, no vertex-to-triangle lists and no device edge adjacency from faces; no
-        RendererGroup and no command line."""
-        import torch                             # (only here: importing the package does not import torch)
+    def _soup(self, torch, tris):
+        """(tensor on the renderer's device, stride 36 or 48, N, came_from_numpy) of a triangle soup -- an Isosurface, [N, 3, 3] float32
+        or a packed [N, 12] (drt_tri) -- checked; a view of 48-byte records is read in place."""
         dev = torch.device("cuda", self._device)
         if isinstance(tris, Isosurface):
             tris = tris.tris
@@ -2797,7 +2806,22 @@ class Renderer:
             stride = 48
         else:
             t, stride = t.contiguous(), 36
-        n = shape[0]
+        return t, stride, shape[0], from_numpy
+
+    def weld(self, tris):
+        """The index buffer of a triangle soup (drt_renderer_weld).  tris: an Isosurface, [N, 3, 3] float32 or a packed [N, 12]
+        (drt_tri).  Two corners are the same vertex iff their three 32-bit words are equal as integers -- triEdgeAdjacency's notion
+        of the same position: -0.0 and +0.0 differ, NaNs are compared by their bits, there is no tolerance and nothing is moved.
+        Vertices are numbered by first appearance.  IndexedMesh(vertices [V, 3] float32, faces [N, 3] int32, first [V] int32); the
+        result depends on the input bytes alone.  Made on the device in integers: a hash table of corner indices, a flag scan, a
+        scatter; V is read back to size the result, which is this call's one synchronisation.  A device tensor in, device tensors out
+        (enqueued on the current torch stream); numpy in, numpy out.  Needs no scene.
+        What it is not: no tolerance -- positions that differ in one bit stay apart; no cotangent weights, no feature preservation,
+        no simplification, no vertex-to-triangle lists; no boundary detection and no device edge adjacency from faces in this call
+        -- boundaryVertices and edgeAdjacency are those; no RendererGroup and no command line."""
+        import torch                             # (only here: importing the package does not import torch)
+        dev = torch.device("cuda", self._device)
+        t, stride, n, from_numpy = self._soup(torch, tris)
         stream = torch.cuda.current_stream(dev).cuda_stream
         faces = torch.empty((n, 3), dtype=torch.int32, device=dev)
         first = torch.empty(3 * n, dtype=torch.int32, device=dev)
@@ -2834,10 +2858,11 @@ class Renderer:
         first.  Every step moves a vertex by a factor f towards the mean of its triangles' other vertices (the umbrella operator,
         every edge of a closed manifold counted twice); `iterations` times the pair (lam, mu) -- Taubin's lambda | mu, which does
         not shrink as plain Laplacian smoothing does -- or, with mu=None, `iterations` steps of lam; factors=[...] gives the steps'
-        factors outright, |f| <= 1 each.  fixed: bool or uint8 [V], vertices that stay, for instance a boundary.  The sums are 64-bit
-        fixed point, so the bytes do not depend on the order; shared vertices stay shared, so a watertight mesh stays watertight.
-        What it is not: no cotangent weights, no feature preservation, no boundary detection (pass fixed, e.g. from boundaryLoops),
-        no simplification."""
+        factors outright, |f| <= 1 each.  fixed: bool or uint8 [V], vertices that stay, or "boundary" for boundaryVertices(mesh), the
+        ends of the open edges.  The sums are 64-bit fixed point, so the bytes do not depend on the order; shared vertices stay
+        shared, so a watertight mesh stays watertight.
+        What it is not: no cotangent weights, no feature preservation, no boundary detection of its own (fixed="boundary" calls
+        boundaryVertices), no simplification."""
         if factors is None:
             try:
                 ok = not isinstance(iterations, bool) and int(iterations) == iterations and iterations >= 0
@@ -2852,11 +2877,15 @@ class Renderer:
             raise DrtError(ERR_INVALID, "factors: numbers expected")
         if not (np.abs(fac) <= 1).all():
             raise DrtError(ERR_INVALID, "factors %r: |f| <= 1 expected" % (fac.tolist(),))
+        if isinstance(fixed, str) and fixed != "boundary":
+            raise DrtError(ERR_INVALID, "fixed = %r: an array, None or 'boundary' expected" % (fixed,))
         import torch                             # (only here: importing the package does not import torch)
         vertices, faces, from_numpy = self._indexed(torch, mesh)
         dev = vertices.device
         fx = None
-        if fixed is not None:
+        if isinstance(fixed, str):
+            fx = self._boundary_vertices(torch, vertices.shape[0], faces, None, False)
+        elif fixed is not None:
             if isinstance(fixed, np.ndarray):
                 fx = torch.from_numpy(np.ascontiguousarray(fixed != 0).view(np.uint8)).to(dev)
             elif torch.is_tensor(fixed):
@@ -2874,6 +2903,93 @@ class Renderer:
                                                  torch.cuda.current_stream(dev).cuda_stream))
         first = mesh[2] if len(mesh) > 2 else None
         return IndexedMesh(out.cpu().numpy() if from_numpy else out, mesh[1], first)
+
+    def _adjacency(self, torch, key, t, stride, n, edges):
+        """(adj [n, 3], edge [n, 3] or None, half_edge [E] or None, E) as device tensors: drt_renderer_tri_adjacency of the soup t
+        (key "position") or drt_renderer_face_adjacency of the faces t (key "index"), on the current torch stream."""
+        dev = torch.device("cuda", self._device)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        adj = torch.empty((n, 3), dtype=torch.int32, device=dev)
+        edge = half_edge = count = None
+        if edges:
+            edge = torch.empty((n, 3), dtype=torch.int32, device=dev)
+            half_edge = torch.empty(3 * n, dtype=torch.int32, device=dev)
+            count = torch.zeros(1, dtype=torch.int32, device=dev)
+        tail = (adj.data_ptr() if n else None, edge.data_ptr() if edges and n else None, half_edge.data_ptr() if edges and n else None,
+                3 * n if edges else 0, count.data_ptr() if edges else None, stream)
+        if key == "position":
+            _check(_lib.drt_renderer_tri_adjacency(self._h, t.data_ptr() if n else None, n, stride, *tail))
+        else:
+            _check(_lib.drt_renderer_face_adjacency(self._h, t.data_ptr() if n else None, n, *tail))
+        if not edges:
+            return adj, None, None, 0
+        e = int(count.item())                    # the one synchronisation: the result's size
+        return adj, edge, half_edge[:e], e
+
+    def edgeAdjacency(self, mesh, edges=False):
+        """int32 [N, 3]: the edge adjacency of a mesh, made on the device (drt_renderer_face_adjacency / drt_renderer_tri_adjacency).
+        mesh: an IndexedMesh, a SimplifiedMesh or a (vertices, faces) pair -- half-edges are matched by vertex index, no vertex is
+        read -- or a triangle soup, [N, 3, 3] float32, a packed [N, 12] or an Isosurface -- matched by bit-equal positions, the bytes
+        of triEdgeAdjacency(tris).  adj[t, e] is the twin half-edge 3 t' + e' of edge e (corner e to corner (e + 1) % 3) of triangle
+        t, -1 on a boundary edge, -2 where three or more triangles meet, two run the same way, or the edge has zero length.  By
+        index on weld(tris).faces and by position on tris the tables are equal.  edges=True: MeshEdges(adj, edge, half_edge, count)
+        with the undirected edges numbered by first appearance; its euler(n_vertices) is V - E + F.  Integers only: a hash table of
+        half-edge indices, two integer minima, a flag scan; the same bytes on every run.  Device tensors in, device tensors out
+        (enqueued on the current torch stream; edges=True reads E back); numpy in, numpy out.  Needs no scene.
+        What it is not: no vertex-to-triangle lists; no tolerance; no orientation repair -- triangles that disagree about an edge's
+        direction get -2; no RendererGroup."""
+        import torch                             # (only here: importing the package does not import torch)
+        soup = isinstance(mesh, Isosurface) or isinstance(mesh, np.ndarray) or torch.is_tensor(mesh)
+        if soup:
+            t, stride, n, from_numpy = self._soup(torch, mesh)
+            res = self._adjacency(torch, "position", t, stride, n, edges)
+        else:
+            _, faces, from_numpy = self._indexed(torch, mesh)
+            res = self._adjacency(torch, "index", faces, 12, faces.shape[0], edges)
+        if not edges:
+            return res[0].cpu().numpy() if from_numpy else res[0]
+        if from_numpy:
+            return MeshEdges(*(x.cpu().numpy().copy() for x in res[:3]), res[3])
+        return MeshEdges(*res)
+
+    def _boundary_vertices(self, torch, n_vertices, faces, adj, bad):
+        """uint8 [V] on the device: drt_renderer_boundary_vertices of faces (a device tensor) and adj (a device tensor or None: the
+        faces' own table)."""
+        dev = torch.device("cuda", self._device)
+        n = faces.shape[0]
+        if adj is None:
+            adj = self._adjacency(torch, "index", faces, 12, n, False)[0]
+        out = torch.empty(n_vertices, dtype=torch.uint8, device=dev)
+        _check(_lib.drt_renderer_boundary_vertices(self._h, faces.data_ptr() if n else None, adj.data_ptr() if n else None, n, n_vertices,
+                                                   1 if bad else 0, out.data_ptr() if n_vertices else None,
+                                                   torch.cuda.current_stream(dev).cuda_stream))
+        return out
+
+    def boundaryVertices(self, mesh, adj=None, bad=False):
+        """bool [V]: the vertices of an indexed mesh on its boundary (drt_renderer_boundary_vertices): True iff a half-edge with
+        adj == -1 starts or ends at the vertex; bad=True counts adj == -2 as well.  adj: int32 [N, 3], edgeAdjacency(mesh) if None.  A
+        triangle with an index outside [0, V) is skipped.  What smooth(fixed="boundary") keeps in place.  Device tensors in, a device
+        tensor out; numpy in, numpy out."""
+        import torch                             # (only here: importing the package does not import torch)
+        vertices, faces, from_numpy = self._indexed(torch, mesh)
+        dev = vertices.device
+        if adj is not None:
+            if isinstance(adj, np.ndarray):
+                if adj.dtype != np.int32:
+                    raise DrtError(ERR_INVALID, "adj: dtype %s, int32 expected" % adj.dtype)
+                adj = torch.from_numpy(np.ascontiguousarray(adj)).to(dev)
+            elif not torch.is_tensor(adj) or adj.dtype != torch.int32 or adj.device != dev:
+                raise DrtError(ERR_INVALID, "adj: a numpy array or a tensor on %s, int32, expected" % (dev,))
+            if adj.numel() != 3 * faces.shape[0]:
+                raise DrtError(ERR_INVALID, "adj: %d values for %d triangles, 3 per triangle expected" % (adj.numel(), faces.shape[0]))
+            adj = adj.contiguous()
+        out = self._boundary_vertices(torch, vertices.shape[0], faces, adj, bool(bad)).to(torch.bool)
+        return out.cpu().numpy() if from_numpy else out
+
+    def adjacencyRoute(self):
+        """How the uploaded scene's edge adjacency was made (drt_renderer_adjacency_route): 0 = there is no table yet, 1 = on the
+        host (DRT_ADJACENCY=host when the renderer was created), 2 = on the device."""
+        return int(_lib.drt_renderer_adjacency_route(self._h))
 
     @staticmethod
     def _simplify_grid(vertices, resolution, cell, lo, hi):

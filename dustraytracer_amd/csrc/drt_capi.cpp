@@ -489,6 +489,7 @@ drt_renderer *drt_renderer_create(int32_t device) {
     r->rq_refill_min = std::min(64, std::max(1, env_int("DRT_RQ_REFILL", r->rq_refill_min)));
     r->rf_top_nodes = std::max(0, env_int("DRT_REFIT_TOP", r->rf_top_nodes));
     r->section_waves = std::max(0, env_int("DRT_SECTION_WAVES", r->section_waves));
+    if (const char *route = std::getenv("DRT_ADJACENCY")) r->adjacency_host = std::strcmp(route, "host") == 0;
     if (r->ev_start.create() != hipSuccess || r->ev_stop.create() != hipSuccess ||
         r->ev_query.create(hipEventDisableTiming) != hipSuccess ||
         r->counters.alloc(sizeof(drt_counters) / sizeof(unsigned long long)) != hipSuccess ||

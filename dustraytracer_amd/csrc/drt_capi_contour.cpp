@@ -39,7 +39,7 @@ int drt_tri_edge_adjacency(const drt_tri *tris, uint32_t n, int32_t *out, uint32
 namespace {
 
 // drt_renderer_plane_sections' checks in its order (segs for planes, splits for offsets, slots for out, chains for counts; there is no
-// mode; query_adj, where there is one, goes with splits).  The adjacency is uploaded with the first call after a scene upload and
+// mode; query_adj, where there is one, goes with splits).  The adjacency is made (scene_adjacency) with the first call after a scene upload and
 // dropped with that upload.  curves: chains holds three words, not two per range, and kernel_curve.hip links.
 int chain_impl(drt_renderer *r, const drt_scene *scene, const void *segs, const uint32_t *splits, const int32_t *query_adj, bool curves,
                drt_chain_slot *slots, uint32_t *chains, uint32_t n, uint32_t total, void *hip_stream) {
@@ -63,12 +63,7 @@ int chain_impl(drt_renderer *r, const drt_scene *scene, const void *segs, const 
     if (int rc = upload_scene(r, scene)) return rc;
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : r->stream;
     if (int rc = query_order(r, s)) return rc;
-    if (!r->adj_built) {                       // the host scene's table: a device refit keeps the order and what is shared
-        std::vector<int32_t> adj;
-        try { adj = scene->host.edge_adjacency(); } catch (const std::exception &e) { return fail(DRT_ERR_INVALID, e.what()); }
-        HIP_TRY(r->d_adj.upload(adj));
-        r->adj_built = true;
-    }
+    if (int rc = scene_adjacency(r, scene, s)) return rc;      // the host scene's table: a device refit keeps the order and what is shared
     // scratch: grown only once the query in flight is over
     const size_t words = contour_scratch_words(total);
     if (words > r->contour_work.count) {

@@ -32,16 +32,11 @@ int topo_scratch(drt_renderer *r, size_t words) {
     return DRT_OK;
 }
 
-// What depends on the adjacency alone, for a scene with triangles: the table's device copy (as drt_renderer_chain_sections makes it),
+// What depends on the adjacency alone, for a scene with triangles: the table on the device (scene_adjacency, as drt_renderer_chain_sections makes it),
 // the labels, the counts and the boundary list.  Waits for `s` while it labels: the host looks at the step's mode between groups of
 // steps.  A device refit keeps all of it; free_scene drops it.
 int ensure_topology(drt_renderer *r, const drt_scene *scene, hipStream_t s) {
-    if (!r->adj_built) {
-        std::vector<int32_t> adj;
-        try { adj = scene->host.edge_adjacency(); } catch (const std::exception &e) { return fail(DRT_ERR_INVALID, e.what()); }
-        HIP_TRY(r->d_adj.upload(adj));
-        r->adj_built = true;
-    }
+    if (int rc = scene_adjacency(r, scene, s)) return rc;
     if (r->topo_built) return DRT_OK;
     const uint32_t n = r->view.n_tris;
     if (n > 0x7fffffffu / 3u) return fail(DRT_ERR_INVALID, "fewer than 2^31 half-edges expected");

@@ -169,6 +169,8 @@ struct drt_renderer {
     // copy) and the scratch of kernel_contour.hip (contour.hpp: contour_scratch_words), grown on demand as section_work is
     DeviceArray<int32_t> d_adj;
     bool adj_built = false;
+    bool adjacency_host = false;               // DRT_ADJACENCY=host: the table is the host's sort, uploaded (unset, or any other value: kernel_adjacency.hip)
+    int adjacency_route = 0;                   // drt_renderer_adjacency_route: 0 = no table yet, 1 = made on the host, 2 = on the device
     DeviceArray<uint32_t> contour_work;
     // mesh topology (drt_capi_topology.cpp): what depends on the adjacency alone is made by the first call after an upload and lives as
     // long as d_adj does -- the shell labels, the counts {shells, open, bad half-edges} on the device and on the host, the ascending
@@ -279,6 +281,7 @@ struct drt_renderer {
         mv_armed = false;
         d_adj.release();
         adj_built = false;
+        adjacency_route = 0;
         topo_labels.release(); topo_counts.release(); topo_boundary.release();
         topo_built = false;
         sf_normals.release(); sf_order.release();
@@ -323,6 +326,9 @@ bool on_renderer_device(const drt_renderer *r, const void *p);
 int query_order(drt_renderer *r, hipStream_t s);
 int query_recorded(drt_renderer *r, hipStream_t s);
 int traversal_scratch(drt_renderer *r, hipStream_t s, bool occluded, bool heads);
+// The uploaded scene's edge adjacency in d_adj (drt_capi_adjacency.cpp), made by the first call after an upload on stream `s`, which
+// the caller has ordered with the query in flight: by kernel_adjacency.hip from the host scene's positions, or by the host's sort
+int scene_adjacency(drt_renderer *r, const drt_scene *scene, hipStream_t s);
 // The uploaded scene's refit plan on the device (refit.hpp: the leaves, the interior nodes by height), made once per upload
 int refit_metadata(drt_renderer *r, const drt_scene *scene);
 // What a call on a finished frame starts with: a frame size, no pending batch, not sharded (`who`, e.g. "the denoiser needs", opens

@@ -387,6 +387,24 @@ public:
         drt::check(drt_renderer_simplify(handle, vertices, n_vertices, faces, n_tris, &grid, placement, cluster, out_vertices, first,
                                          vertex_capacity, out_faces, source, tri_capacity, counts, stream));
     }
+    // new: the edge adjacency of a triangle list on the device, by bit-equal positions (drt_renderer_tri_adjacency; stride 36 or 48) or by
+    // vertex index (drt_renderer_face_adjacency): adj[3 t + e] = the twin half-edge, -1 on a boundary edge, -2 on every other edge --
+    // drt_tri_edge_adjacency's bytes.  With edge, half_edge and edge_count (null together): the undirected edges numbered by first
+    // appearance.  Device arrays, enqueued on `stream`.
+    void TriAdjacency(const void *tris, uint32_t n, uint32_t stride, int32_t *adj, int32_t *edge = nullptr, int32_t *half_edge = nullptr,
+                      uint32_t capacity = 0, uint32_t *edge_count = nullptr, void *stream = nullptr) {
+        drt::check(drt_renderer_tri_adjacency(handle, tris, n, stride, adj, edge, half_edge, capacity, edge_count, stream));
+    }
+    void FaceAdjacency(const int32_t *faces, uint32_t n, int32_t *adj, int32_t *edge = nullptr, int32_t *half_edge = nullptr,
+                       uint32_t capacity = 0, uint32_t *edge_count = nullptr, void *stream = nullptr) {
+        drt::check(drt_renderer_face_adjacency(handle, faces, n, adj, edge, half_edge, capacity, edge_count, stream));
+    }
+    // new: out[v] = 1 iff a half-edge with adj == -1 (with DRT_BOUNDARY_BAD_EDGES also -2) starts or ends at vertex v
+    // (drt_renderer_boundary_vertices); uint8 [V].
+    void BoundaryVertices(const int32_t *faces, const int32_t *adj, uint32_t n_tris, uint32_t n_vertices, uint8_t *out, uint32_t flags = 0,
+                          void *stream = nullptr) {
+        drt::check(drt_renderer_boundary_vertices(handle, faces, adj, n_tris, n_vertices, flags, out, stream));
+    }
     // new: the triangles each ray passes through, sorted by (t, prim) (drt_renderer_list_hits): ray i's records go to
     // hits[offsets[i] .. offsets[i+1]), clamped to hits_capacity, miss records behind them; counts[i] = all of them, stored or not.
     // counts may be null, hits may be null iff hits_capacity == 0.  Device arrays, enqueued on `stream`.

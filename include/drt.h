@@ -38,7 +38,8 @@ extern "C" {
  * drt_renderer_sample_surface), the ambient-occlusion entry point (drt_renderer_ambient_occlusion) and the winding-number entry
  * points (drt_renderer_winding_numbers / _winding_inside / _winding_signed_distance) are additions to it; so is the isosurface
  * entry point (drt_renderer_isosurface), and so are the welding entry points (drt_renderer_weld / _vertex_normals /
- * _smooth_vertices), and so is the simplification entry point (drt_renderer_simplify) */
+ * _smooth_vertices), and so is the simplification entry point (drt_renderer_simplify), and so are the device edge-adjacency entry
+ * points (drt_renderer_tri_adjacency / _face_adjacency / _boundary_vertices / _adjacency_route) */
 #define DRT_ABI_VERSION 2
 
 typedef enum {
@@ -1538,6 +1539,60 @@ int           drt_renderer_simplify(drt_renderer *r, const float *vertices, uint
                                     const drt_grid *grid, int32_t placement, int32_t *cluster, float *out_vertices, int32_t *first,
                                     uint32_t vertex_capacity, int32_t *out_faces, int32_t *source, uint32_t tri_capacity,
                                     uint32_t *counts, void *hip_stream);
+
+/* ---- device edge adjacency (new; drt_scene_edge_adjacency's and drt_tri_edge_adjacency's table made on the device, for triangle
+ * soups, index buffers and the uploaded scene, with the numbering of the undirected edges and the boundary vertices) ----
+ * drt_renderer_tri_adjacency and drt_renderer_face_adjacency need no scene and no tree.  Half-edge h = 3 t + e runs from corner e to
+ * corner (e + 1) % 3 of triangle t.  An END of a half-edge is
+ *   by position (drt_renderer_tri_adjacency): the three 32-bit words of the corner at tris + t * stride + 12 e, stride 36 (float
+ *     [N][3][3]) or 48 (drt_tri), compared as integers -- drt_tri_edge_adjacency's rule exactly: -0.0 and +0.0 differ, NaNs are compared
+ *     by their bits, there is no tolerance;
+ *   by index (drt_renderer_face_adjacency): the int32 word faces[3 t + e], compared as an integer.  No vertex array is read, so no
+ *     value is out of range.
+ * Two half-edges are in one GROUP iff they have the same unordered pair of ends.  The rule, for both kinds of end:
+ *   a half-edge whose two ends are equal (zero length) gets -2 and is in no group;
+ *   a group of one half-edge gets -1;
+ *   a group of exactly two that run in opposite directions (the start of one is the end of the other) are each other's twins:
+ *     adj[h] = the other half-edge;
+ *   every other group -- three or more, two that run the same way -- gets -2.
+ * adj is int32 [3 N], the same bytes as drt_tri_edge_adjacency's table of the same triangles for every input.
+ * Edge numbering (optional: edge, half_edge and edge_count are NULL together): every group is one undirected edge; its representative
+ * is its smallest half-edge; edges are numbered in ascending representative, which is by first appearance.  edge int32 [3 N] is each
+ * half-edge's edge id, -1 for a zero-length one; half_edge int32 [capacity] is the representative of each of the first `capacity`
+ * edges (3 N always suffices; half_edge is NULL iff capacity == 0); *edge_count = E, stored whether or not capacity held all edges.
+ * With V from drt_renderer_weld this gives V - E + F without a host pass.
+ * drt_renderer_boundary_vertices: out uint8 [n_vertices] is zeroed, then out[v] = 1 iff a half-edge with adj == -1 starts or ends at
+ * v, i.e. v is faces[3 t + e] or faces[3 t + (e + 1) % 3] of such a half-edge 3 t + e.  With DRT_BOUNDARY_BAD_EDGES (flag bit 0)
+ * adj == -2 counts as well.  A triangle with an index outside [0, n_vertices) is skipped (a bounds check, never a fault).
+ * The uploaded scene's table (drt_renderer_chain_sections, _chain_intersections, _shell_labels, _boundary_loops,
+ * _edge_adjacency) is made the same way from the host scene's positions in tree order by the first such call after an upload; it is
+ * the same bytes as drt_scene_edge_adjacency, and a device refit leaves it alone.  DRT_ADJACENCY=host in the environment when the
+ * renderer is created selects the host's sort instead.  drt_renderer_adjacency_route: 0 = no table since the last upload, 1 = it was
+ * made on the host, 2 = on the device.
+ * Consequences: the result depends on the input bytes alone: the same bytes on every run, in every launch shape.  (How: the weld's
+ * insert-only hash table, here of half-edge indices keyed by the unordered pair, claimed by compare-and-swap and lowered by an
+ * integer minimum; a second integer minimum finds the second member of a group; a flag scan numbers the edges.  No lane waits for
+ * another; the hash decides nothing that can be observed.)
+ * Checks, each DRT_ERR_INVALID before any device work, in this order: NULL r; a stride other than 36 or 48; 3 N >= 2^31; N == 0 is a
+ * no-op that touches nothing, edge_count included; NULL tris / faces or adj; edge NULL without edge_count NULL or the reverse;
+ * half_edge or a capacity without edge; half_edge NULL without capacity 0 or the reverse; every pointer 4-byte aligned; a pending
+ * asynchronous batch; then every pointer must be device memory on the renderer's device.  drt_renderer_boundary_vertices: NULL r; a
+ * flag bit other than bit 0; 3 N >= 2^31; n_vertices >= 2^31; n_vertices == 0 is a no-op; NULL out; NULL faces or adj with N > 0;
+ * faces and adj 4-byte aligned; a pending batch; device memory.  The table and two words per half-edge are the renderer's scratch,
+ * shared with the welding calls and grown on demand (48 to 72 bytes per triangle); running out of device memory is DRT_ERR_DEVICE.
+ * hip_stream NULL = the renderer's stream; the calls only enqueue, in order with the other queries (the same event), because they
+ * share the renderer's scratch; legal on a sharded renderer; the framebuffer, accumulation, sample count, counters, kernel info and
+ * kernel span are not touched.
+ * What this is not: no vertex-to-triangle lists; no tolerance -- ends that differ in one bit are different ends; no orientation
+ * repair -- two triangles that run the same way along an edge get -2 and stay so; no drt_group_* form and no command line. */
+#define DRT_BOUNDARY_BAD_EDGES 1u
+int           drt_renderer_tri_adjacency(drt_renderer *r, const void *tris, uint32_t n, uint32_t stride, int32_t *adj, int32_t *edge,
+                                         int32_t *half_edge, uint32_t capacity, uint32_t *edge_count, void *hip_stream);
+int           drt_renderer_face_adjacency(drt_renderer *r, const int32_t *faces, uint32_t n, int32_t *adj, int32_t *edge,
+                                          int32_t *half_edge, uint32_t capacity, uint32_t *edge_count, void *hip_stream);
+int           drt_renderer_boundary_vertices(drt_renderer *r, const int32_t *faces, const int32_t *adj, uint32_t n_tris,
+                                             uint32_t n_vertices, uint32_t flags, uint8_t *out, void *hip_stream);
+int           drt_renderer_adjacency_route(const drt_renderer *r);
 
 /* ---- first-hit guide buffers and the a-trous denoiser (new; the reference's TODO list, RayGen.cuh:13-21, starts with "DLSS 3.5
  * like features") ----
