@@ -359,6 +359,7 @@ _sig("drt_renderer_tri_adjacency", C.c_int, _P, _P, C.c_uint32, C.c_uint32, _P, 
 _sig("drt_renderer_face_adjacency", C.c_int, _P, _P, C.c_uint32, _P, _P, _P, C.c_uint32, _P, _P)
 _sig("drt_renderer_boundary_vertices", C.c_int, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P)
 _sig("drt_renderer_adjacency_route", C.c_int, _P)
+_sig("drt_renderer_subdivide", C.c_int, _P, _P, C.c_uint32, _P, C.c_uint32, C.c_int32, _P, _P, C.c_uint32, _P, _P, _P)
 _sig("drt_scene_edge_adjacency", C.c_int, _P, _P, C.c_uint32)
 _sig("drt_renderer_chain_sections", C.c_int, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _P)
 _sig("drt_tri_edge_adjacency", C.c_int, _P, C.c_uint32, _P, C.c_uint32)
@@ -859,6 +860,21 @@ class SimplifiedMesh(collections.namedtuple("SimplifiedMesh", "vertices faces fi
     surviving triangles in input order; first [C] int32, the smallest input vertex of each cluster; cluster [V] int32, the cluster id
     of every input vertex; source [M] int32, the input triangle of every output triangle.  The first three fields are an
     IndexedMesh's, so vertexNormals, smooth and toScene(normals=) take it unchanged.  Device tensors or numpy arrays."""
+
+    triangles = IndexedMesh.triangles
+    toScene = IndexedMesh.toScene
+
+
+SUBDIVIDE_SCHEMES = {"midpoint": 0, "loop": 1}                           # Renderer.subdivide: drt.h DRT_SUBDIVIDE_*
+
+
+class SubdividedMesh(collections.namedtuple("SubdividedMesh", "vertices faces parents")):
+    """A subdivided mesh (Renderer.subdivide): vertices [V', 3] float32 -- the input's V vertices under their old ids, then one per
+    undirected edge, numbered by first appearance; faces [4 N, 3] int32, the four children of input triangle t at 4 t ... 4 t + 3
+    (child k < 3 starts at corner k, the last is the middle one); parents [V', 2] int32 of the last level: (v, v) for a vertex that
+    was there before, the two ends of its edge for a new one, so per-vertex attributes can follow (None with levels=0).  The first
+    two fields are an IndexedMesh's, so vertexNormals, smooth, simplify, edgeAdjacency, subdivide and toScene(normals=) take it
+    unchanged.  Device tensors or numpy arrays."""
 
     triangles = IndexedMesh.triangles
     toScene = IndexedMesh.toScene
@@ -2901,7 +2917,7 @@ class Renderer:
                                                  faces.shape[0], fac.ctypes.data if len(fac) else None, len(fac),
                                                  fx.data_ptr() if fx is not None else None, out.data_ptr(),
                                                  torch.cuda.current_stream(dev).cuda_stream))
-        first = mesh[2] if len(mesh) > 2 else None
+        first = mesh[2] if len(mesh) > 2 and not isinstance(mesh, SubdividedMesh) else None      # (its third field is parents)
         return IndexedMesh(out.cpu().numpy() if from_numpy else out, mesh[1], first)
 
     def _adjacency(self, torch, key, t, stride, n, edges):
@@ -3109,6 +3125,58 @@ class Renderer:
         res = SimplifiedMesh(out_v[:c], out_f[:m], first[:c], cluster, source[:m])
         if from_numpy:
             return SimplifiedMesh(*(x.cpu().numpy().copy() for x in res))
+        return res
+
+    def subdivide(self, mesh, levels=1, scheme="loop"):
+        """A finer mesh (drt_renderer_subdivide): every triangle becomes four, `levels` times.  mesh: an IndexedMesh, a SimplifiedMesh,
+        a SubdividedMesh or a (vertices, faces) pair, as simplify and smooth take it.  scheme="loop": Loop subdivision with Warren's
+        weights -- a new vertex on an interior edge at 3/8 3/8 1/8 1/8 of the edge's ends and the two opposite corners, an old vertex
+        drawn towards its neighbours, so the surface converges to a smooth one; the open edges, and the edges where three or more
+        triangles meet or two run the same way, are creases: their new vertices are midpoints and their old vertices follow the curve
+        rule 1/8 6/8 1/8, or stay where they are if they have other than two such edges.  scheme="midpoint": the same topology with
+        the old vertices left alone and the new ones at the midpoints -- what one wants before displacement, or before smooth or
+        simplify on a finer grid.  The connectivity is edgeAdjacency's by index: the vertex of edge e is V + e, V' = V + E and
+        V' - E' + F' = V - E + F; a closed oriented manifold stays one.  The sums are 64-bit fixed point added with integer atomics
+        and the weights are applied in float64, so the result depends on the input bytes alone.  A vertex or an edge with an index
+        out of range or a coordinate that is not finite is passed through or becomes NaNs; nothing faults.
+        SubdividedMesh(vertices [V', 3], faces [4 N, 3], parents [V', 2]); parents is the last level's, and levels=0 returns the
+        input's arrays with parents None.  Each level allocates V + 3 N vertices as the capacity and costs one read-back of
+        vertex_count to size the result -- its one synchronisation.  Device tensors in, device tensors out (enqueued on the current
+        torch stream); numpy in, numpy out.  Needs no scene.
+        What it is not: no Catmull-Clark, Butterfly or sqrt(3); no user crease tags or sharpness; no limit-surface projection or
+        limit normals; no adaptive refinement; no attribute interpolation beyond parents and the child order; no RendererGroup and
+        no command line."""
+        try:
+            ok = not isinstance(levels, bool) and int(levels) == levels and levels >= 0
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise DrtError(ERR_INVALID, "levels = %r: a non-negative integer expected" % (levels,))
+        if not isinstance(scheme, str) or scheme not in SUBDIVIDE_SCHEMES:
+            raise DrtError(ERR_INVALID, "scheme = %r: 'loop' or 'midpoint' expected" % (scheme,))
+        import torch                             # (only here: importing the package does not import torch)
+        vertices, faces, from_numpy = self._indexed(torch, mesh)
+        if int(levels) == 0:
+            return SubdividedMesh(mesh[0], mesh[1], None)
+        dev = vertices.device
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        parents = None
+        for _ in range(int(levels)):
+            nv, nt = int(vertices.shape[0]), int(faces.shape[0])
+            cap = nv + 3 * nt
+            out_v = torch.empty((cap, 3), dtype=torch.float32, device=dev)
+            parents = torch.empty((cap, 2), dtype=torch.int32, device=dev)
+            out_f = torch.empty((4 * nt, 3), dtype=torch.int32, device=dev)
+            count = torch.zeros(1, dtype=torch.int32, device=dev)
+            _check(_lib.drt_renderer_subdivide(self._h, vertices.data_ptr() if nv else None, nv, faces.data_ptr() if nt else None, nt,
+                                               SUBDIVIDE_SCHEMES[scheme], out_v.data_ptr() if cap else None,
+                                               parents.data_ptr() if cap else None, cap, out_f.data_ptr() if nt else None,
+                                               count.data_ptr(), stream))
+            total = int(count.item())            # the level's one synchronisation: the result's size
+            vertices, faces, parents = out_v[:total], out_f, parents[:total]
+        res = SubdividedMesh(vertices, faces, parents)
+        if from_numpy:
+            return SubdividedMesh(*(x.cpu().numpy().copy() for x in res))
         return res
 
     def debugWindingMoments(self, scene):

@@ -261,6 +261,13 @@ struct drt_renderer {
     // welding calls above (the table, the representatives, the block totals, the maximum, the 64-bit sums) -- a key per vertex and a
     // member count per cluster
     DeviceArray<uint32_t> sp_key, sp_cnt;
+    // mesh subdivision (drt_capi_subdivide.cpp): the scratch of kernel_subdivide.hip (subdivide.hpp) beyond what the adjacency of its
+    // faces takes from the welding calls above -- that adjacency's own outputs (the twins, the edge of every half-edge, the
+    // representative of every edge), the word E with Loop's two counts per vertex behind it, and Loop's second set of 64-bit sums
+    // (the first lies in wd_acc)
+    DeviceArray<int32_t> sd_adj, sd_edge, sd_half_edge;
+    DeviceArray<uint32_t> sd_cnt;
+    DeviceArray<unsigned long long> sd_acc;
 
     drt_renderer() = default;
     ~drt_renderer() {                          // the members release what they own, on this device

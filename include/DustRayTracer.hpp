@@ -399,6 +399,17 @@ public:
                        uint32_t capacity = 0, uint32_t *edge_count = nullptr, void *stream = nullptr) {
         drt::check(drt_renderer_face_adjacency(handle, faces, n, adj, edge, half_edge, capacity, edge_count, stream));
     }
+    // new: one level of subdivision of an indexed mesh (drt_renderer_subdivide): every triangle becomes four, out_faces int32 [4 N][3];
+    // the even vertices keep their ids and the odd vertex of undirected edge e (drt_renderer_face_adjacency's numbering) is V + e.
+    // DRT_SUBDIVIDE_LOOP smooths (Loop's weights, the open and non-manifold edges as creases), DRT_SUBDIVIDE_MIDPOINT only refines.
+    // out_vertices [V'][3] and parents [V'][2] (the two ends an odd vertex lies between; may be null), the first vertex_capacity of
+    // them (V + 3 N always suffices); vertex_count one word, always V' = V + E.  No scene and no tree; device arrays, enqueued on `stream`.
+    void Subdivide(const float *vertices, uint32_t n_vertices, const int32_t *faces, uint32_t n_tris, float *out_vertices, int32_t *parents,
+                   uint32_t vertex_capacity, int32_t *out_faces, uint32_t *vertex_count, int32_t scheme = DRT_SUBDIVIDE_LOOP,
+                   void *stream = nullptr) {
+        drt::check(drt_renderer_subdivide(handle, vertices, n_vertices, faces, n_tris, scheme, out_vertices, parents, vertex_capacity,
+                                          out_faces, vertex_count, stream));
+    }
     // new: out[v] = 1 iff a half-edge with adj == -1 (with DRT_BOUNDARY_BAD_EDGES also -2) starts or ends at vertex v
     // (drt_renderer_boundary_vertices); uint8 [V].
     void BoundaryVertices(const int32_t *faces, const int32_t *adj, uint32_t n_tris, uint32_t n_vertices, uint8_t *out, uint32_t flags = 0,

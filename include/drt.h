@@ -39,7 +39,8 @@ extern "C" {
  * points (drt_renderer_winding_numbers / _winding_inside / _winding_signed_distance) are additions to it; so is the isosurface
  * entry point (drt_renderer_isosurface), and so are the welding entry points (drt_renderer_weld / _vertex_normals /
  * _smooth_vertices), and so is the simplification entry point (drt_renderer_simplify), and so are the device edge-adjacency entry
- * points (drt_renderer_tri_adjacency / _face_adjacency / _boundary_vertices / _adjacency_route) */
+ * points (drt_renderer_tri_adjacency / _face_adjacency / _boundary_vertices / _adjacency_route), and so is the subdivision entry
+ * point (drt_renderer_subdivide) */
 #define DRT_ABI_VERSION 2
 
 typedef enum {
@@ -1593,6 +1594,67 @@ int           drt_renderer_face_adjacency(drt_renderer *r, const int32_t *faces,
 int           drt_renderer_boundary_vertices(drt_renderer *r, const int32_t *faces, const int32_t *adj, uint32_t n_tris,
                                              uint32_t n_vertices, uint32_t flags, uint8_t *out, void *hip_stream);
 int           drt_renderer_adjacency_route(const drt_renderer *r);
+
+/* ---- mesh subdivision (new; one level of Loop or midpoint refinement of an indexed mesh, on the connectivity above: the odd vertex
+ * of edge e is vertex V + e, so nothing is sorted and no host pass is needed) ----
+ * drt_renderer_subdivide needs no scene and no tree; it works on any indexed mesh in device memory, drt_renderer_weld's and
+ * drt_renderer_simplify's output included: vertices float [V][3], faces int32 [N][3].  One call is one level: every triangle
+ * becomes four.  Callers loop for more levels.
+ * Topology, identical for both schemes.  The connectivity is drt_renderer_face_adjacency's of faces -- by index, with the edges
+ * numbered: adj, edge and half_edge below are its outputs and E is its edge count; next(h) is the half-edge after h in its triangle,
+ * 3 t + (e + 1) % 3 for h = 3 t + e.  Even vertices keep their ids 0 ... V - 1; the odd vertex of edge e is V + e;
+ * *vertex_count = V + E always.  Only the first vertex_capacity vertices are stored in out_vertices and parents (V + 3 N always
+ * suffices); out_vertices and parents are NULL iff vertex_capacity == 0, and parents alone may be NULL.
+ * m(h) = V + edge[h] if edge[h] >= 0, otherwise faces[h]: an index edge of zero length has no new vertex.  out_faces is int32
+ * [4 N][3], always complete, with no compaction: for t = (a, b, c) and m0 = m(3 t), m1 = m(3 t + 1), m2 = m(3 t + 2),
+ *   child 4 t + 0 = (a, m0, m2),  child 4 t + 1 = (b, m1, m0),  child 4 t + 2 = (c, m2, m1),  child 4 t + 3 = (m0, m1, m2).
+ * Orientation is kept; child k < 3 starts at corner k; the source triangle of child j is j >> 2.  Out-of-range indices are copied
+ * as they are (the children read no position), and nothing faults.
+ * parents is int32 [V'][2]: (v, v) for an even vertex; for the odd vertex V + e, with h = half_edge[e], (faces[h], faces[next(h)]):
+ * the ends of the representative half-edge, in that order.
+ * Consequences: a closed oriented manifold input gives a closed oriented manifold output, adj >= 0 everywhere;
+ * V' - E' + F' = V - E + F; a same-way pair, a fan or a boundary stays one in the output.
+ * Positions: float64 with one rounding per operation, in the order written, then one rounding to fp32.  An edge is USABLE iff both
+ * ends of its representative half-edge are inside [0, V) (a bounds check, never a fault) and all six coordinates are finite.  The odd
+ * vertex of an unusable edge is three words 0x7FC00000.  pa and pb below are a coordinate of the two ends.
+ * DRT_SUBDIVIDE_MIDPOINT (0): even vertices copy their 12 bytes; an odd vertex is (float)(((double)pa + (double)pb) * 0.5), the same
+ * bits whichever half-edge represents the edge.
+ * DRT_SUBDIVIDE_LOOP (1): an edge is INTERIOR iff its representative h has adj[h] >= 0; every other edge (-1 or -2: boundary, fan,
+ * same-way pair) is a CREASE.  Interior odd vertex: c and d are the corners opposite h and opposite adj[h] -- faces[next(next(h))] and
+ * the same of adj[h] -- and the position is (float)(((double)pa + (double)pb) * 0.375 + ((double)pc + (double)pd) * 0.125); if c or d
+ * is out of range or not finite, the midpoint.  A crease odd vertex is the midpoint.
+ * Even vertices need sums over neighbours; these are int64 fixed point added with integer atomics, exactly
+ * drt_renderer_smooth_vertices' quantisation: M is the largest finite |coordinate| over the input vertices, e = floor(log2 M),
+ * k = 27 - e (M = 0: k = 0), q(x) = (int64) trunc((double)x * 2^k).  One pass over the EDGES, not the half-edges, so an edge counts
+ * once however many triangles share it: each usable edge (a, b) adds q(pb) to acc[a] and q(pa) to acc[b], in the interior or the
+ * crease set of sums according to its kind, and adds 1 to the matching count, n_int or n_cr, of each end.  Unusable edges add nothing.
+ * Finish per vertex, with S = (double)acc * 2^-k per coordinate:
+ *   a coordinate that is not finite, or n_cr == 0 && n_int == 0: the vertex keeps its bits;
+ *   n_cr == 0: beta = (n_int == 3) ? 0.1875 : 0.375 / (double)n_int (Warren's weights),
+ *     p' = (float)((double)p + beta * (S_int - (double)n_int * (double)p));
+ *   n_cr == 2: p' = (float)((double)p + 0.125 * (S_cr - 2.0 * (double)p)); interior edges are ignored;
+ *   any other n_cr (a dart, a corner where three creases meet, a non-manifold vertex): the vertex keeps its bits.
+ * The result depends on the input bytes alone: the same bytes on every run, in every launch shape.  (How: the adjacency's integers,
+ * integer sums, and float64 operations that are each rounded once; the hash decides nothing that can be observed.)
+ * Checks, each DRT_ERR_INVALID before any device work, in this order: NULL r or vertex_count; a scheme other than 0 or 1;
+ * 3 N >= 2^31; V + 3 N >= 2^31; 12 N >= 2^31.  N == 0 stores *vertex_count = V, copies the stored vertices -- with (v, v) in parents --
+ * and is otherwise a no-op; the checks below apply to it as far as they name something it touches.  NULL vertices with V > 0; NULL
+ * faces or out_faces with N > 0; out_vertices NULL without vertex_capacity 0 or the reverse; parents without out_vertices; every
+ * pointer 4-byte aligned; an output overlapping vertices or faces; a pending asynchronous batch; then every pointer must be device
+ * memory on the renderer's device.  The adjacency's table and outputs, the counts and the sums are the renderer's scratch, shared
+ * with the welding calls and grown on demand (84 to 108 bytes per triangle, and 56 per vertex with Loop); running out of device
+ * memory is DRT_ERR_DEVICE.
+ * hip_stream NULL = the renderer's stream; the call only enqueues, in order with the other queries (the same event), because it
+ * shares the renderer's scratch; legal on a sharded renderer; the framebuffer, accumulation, sample count, counters, kernel info and
+ * kernel span are not touched.
+ * What this is not: no Catmull-Clark, Butterfly or sqrt(3); no user crease tags or sharpness -- the creases are the edges that are
+ * not a twin pair; no limit-surface projection or limit normals; no adaptive refinement; no attribute interpolation beyond parents
+ * and the child order; no drt_group_* form and no command line. */
+#define DRT_SUBDIVIDE_MIDPOINT 0
+#define DRT_SUBDIVIDE_LOOP 1
+int           drt_renderer_subdivide(drt_renderer *r, const float *vertices, uint32_t n_vertices, const int32_t *faces, uint32_t n_tris,
+                                     int32_t scheme, float *out_vertices, int32_t *parents, uint32_t vertex_capacity,
+                                     int32_t *out_faces, uint32_t *vertex_count, void *hip_stream);
 
 /* ---- first-hit guide buffers and the a-trous denoiser (new; the reference's TODO list, RayGen.cuh:13-21, starts with "DLSS 3.5
  * like features") ----
