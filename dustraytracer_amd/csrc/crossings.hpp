@@ -31,12 +31,8 @@ enum class CrossingsOut : uint32_t {
 struct CrossingsArgs {
     const void *in;              // drt_ray[n] (32 B, 16-B aligned) or drt_point[n] (16 B, 16-B aligned)
     void *out;                   // what `kind` says
-    uint32_t n;                  // < 2^31
-    uint32_t stack_levels;       // tree depth (<= 64): the stack never holds more entries
-    uint32_t refill_min;         // a wave claims new queries once this many of its lanes are idle (1..64)
+    QueryFrame frame;            // n, tree depth, refill threshold, claim heads, HBM stack: 4 B stack entries
     uint32_t rule;               // point mode: 0 parity (count odd), 1 winding (winding != 0)
-    unsigned int *heads;         // kRqHeadWords zeroed words
-    uint32_t *stack_hbm;         // levels beyond the LDS ones: [(level - K) * grid threads + thread], 4 B entries
 };
 
 hipError_t launch_crossings(const SceneView &scene, CrossingsOut kind, const CrossingsArgs &args, int num_cus, hipStream_t stream);

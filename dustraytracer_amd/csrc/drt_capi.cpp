@@ -202,6 +202,53 @@ int drt::traversal_scratch(drt_renderer *r, hipStream_t s, bool occluded, bool h
     return DRT_OK;
 }
 
+// operands: [first, last) with ptr_of(*it) the pointer; null ones are absent optional operands
+template <class It, class PtrOf>
+static int query_open_impl(drt_renderer *r, const drt_scene *scene, uint32_t n, It first, It last, PtrOf ptr_of, const char *noun,
+                           const char *names, void *hip_stream, bool occluded, hipStream_t *s) {
+    if (n > 0x7fffffffu) return fail(DRT_ERR_INVALID, std::string("at most 2^31 - 1 ") + noun + " per call");
+    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
+    HIP_TRY(hipSetDevice(r->device));
+    (void)hipGetLastError();                   // (see render_batch_impl: only this call's own errors count)
+    for (It it = first; it != last; ++it)
+        if (ptr_of(*it) && !on_renderer_device(r, ptr_of(*it)))
+            return fail(DRT_ERR_INVALID, std::string(names) + " must be device memory on the renderer's device");
+    if (int rc = upload_scene(r, scene)) return rc;
+    *s = hip_stream ? (hipStream_t)hip_stream : r->stream;
+    if (int rc = query_order(r, *s)) return rc;
+    return traversal_scratch(r, *s, occluded, true);
+}
+
+int drt::query_open(drt_renderer *r, const drt_scene *scene, uint32_t n, std::initializer_list<const void *> operands, const char *noun,
+                    const char *names, void *hip_stream, bool occluded, hipStream_t *s) {
+    return query_open_impl(r, scene, n, operands.begin(), operands.end(), [](const void *p) { return p; }, noun, names, hip_stream, occluded, s);
+}
+
+bool drt::query_begin(drt_renderer *r, const drt_scene *scene, uint32_t n, std::initializer_list<QueryOperand> ops, const QueryWords &w,
+                      void *hip_stream, bool occluded, hipStream_t *s, int *rc) {
+    const auto stop = [rc](int code) { *rc = code; return false; };
+    if (!r || !scene) return stop(fail(DRT_ERR_INVALID, "null argument"));
+    if (n == 0) return stop(DRT_OK);
+    for (const QueryOperand &o : ops)
+        if (!o.p) return stop(fail(DRT_ERR_INVALID, w.null_msg));
+    for (const QueryOperand &o : ops)
+        if (((uintptr_t)o.p & (o.align - 1)) != 0) return stop(fail(DRT_ERR_INVALID, w.align_msg));
+    *rc = query_open_impl(r, scene, n, ops.begin(), ops.end(), [](const QueryOperand &o) { return o.p; }, w.noun, w.names, hip_stream, occluded, s);
+    return *rc == DRT_OK;
+}
+
+uint32_t drt::query_stack_levels(const drt_renderer *r) { return (uint32_t)std::max(1, r->bvh_depth); }
+
+QueryFrame drt::query_frame(const drt_renderer *r, uint32_t n) {
+    QueryFrame f;
+    f.n = n;
+    f.stack_levels = query_stack_levels(r);
+    f.refill_min = (uint32_t)r->rq_refill_min;
+    f.heads = r->rq_heads.ptr;
+    f.stack_hbm = r->rq_stack.ptr;
+    return f;
+}
+
 int drt::whole_frame(const drt_renderer *r, const char *who) {
     if (r->world > 1) return fail(DRT_ERR_UNSUPPORTED, std::string(who) + " the whole frame: a sharded renderer (world > 1) holds only its stripes");
     return DRT_OK;
@@ -812,27 +859,12 @@ int drt_renderer_wait(drt_renderer *r, float *delta_ms) {
 // ------------------------------------------------------------------ batched ray queries (kernel_ray_query.hip)
 static int ray_query_impl(drt_renderer *r, const drt_scene *scene, const drt_ray *rays, void *out, uint32_t n, void *hip_stream,
                           bool occluded) {
-    if (!r || !scene) return fail(DRT_ERR_INVALID, "null argument");
-    if (n == 0) return DRT_OK;
-    if (!rays || !out) return fail(DRT_ERR_INVALID, "null ray or result pointer");
-    if (((uintptr_t)rays & 15u) != 0 || (!occluded && ((uintptr_t)out & 15u) != 0))
-        return fail(DRT_ERR_INVALID, "rays and hits must be 16-byte aligned");
-    if (n > 0x7fffffffu) return fail(DRT_ERR_INVALID, "at most 2^31 - 1 rays per call");
-    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
-    HIP_TRY(hipSetDevice(r->device));
-    (void)hipGetLastError();                   // (see render_batch_impl: only this call's own errors count)
-    if (!on_renderer_device(r, rays) || !on_renderer_device(r, out))
-        return fail(DRT_ERR_INVALID, "rays and results must be device memory on the renderer's device");
-    if (int rc = upload_scene(r, scene)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : r->stream;
-    if (int rc = query_order(r, s)) return rc;
-    if (int rc = traversal_scratch(r, s, occluded, true)) return rc;
+    static const QueryWords words = {"null ray or result pointer", "rays and hits must be 16-byte aligned", "rays", "rays and results"};
+    hipStream_t s;
+    int rc;
+    if (!query_begin(r, scene, n, {{rays, 16}, {out, occluded ? 1u : 16u}}, words, hip_stream, occluded, &s, &rc)) return rc;
     RayQueryArgs a;
-    a.rays = rays; a.out = out; a.n = n;
-    a.stack_levels = (uint32_t)std::max(1, r->bvh_depth);
-    a.refill_min = (uint32_t)r->rq_refill_min;
-    a.heads = r->rq_heads.ptr;
-    a.stack_hbm = r->rq_stack.ptr;
+    a.rays = rays; a.out = out; a.frame = query_frame(r, n);
     const char *name = nullptr;                // (kernel_info names the last render kernel: queries leave it alone)
     HIP_TRY(launch_ray_query(r->view, occluded, a, r->num_cus, s, &name));
     return query_recorded(r, s);
@@ -847,63 +879,35 @@ int drt_renderer_occluded(drt_renderer *r, const drt_scene *scene, const drt_ray
 }
 
 // ------------------------------------------------------------------ nearest-surface queries (kernel_nearest.hip)
-// Validated, ordered and given scratch as the ray queries are: the kernel shares their claim heads and the closest-hit HBM stack.
+// The closest-hit HBM stack ({ref, box2} entries).
 int drt_renderer_nearest(drt_renderer *r, const drt_scene *scene, const drt_point *points, drt_nearest *out, uint32_t n, void *hip_stream) {
-    if (!r || !scene) return fail(DRT_ERR_INVALID, "null argument");
-    if (n == 0) return DRT_OK;
-    if (!points || !out) return fail(DRT_ERR_INVALID, "null point or result pointer");
-    if (((uintptr_t)points & 15u) != 0 || ((uintptr_t)out & 15u) != 0) return fail(DRT_ERR_INVALID, "points and results must be 16-byte aligned");
-    if (n > 0x7fffffffu) return fail(DRT_ERR_INVALID, "at most 2^31 - 1 points per call");
-    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
-    HIP_TRY(hipSetDevice(r->device));
-    (void)hipGetLastError();                   // (see render_batch_impl: only this call's own errors count)
-    if (!on_renderer_device(r, points) || !on_renderer_device(r, out))
-        return fail(DRT_ERR_INVALID, "points and results must be device memory on the renderer's device");
-    if (int rc = upload_scene(r, scene)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : r->stream;
-    if (int rc = query_order(r, s)) return rc;
-    if (int rc = traversal_scratch(r, s, false, true)) return rc;
+    static const QueryWords words = {"null point or result pointer", "points and results must be 16-byte aligned", "points", "points and results"};
+    hipStream_t s;
+    int rc;
+    if (!query_begin(r, scene, n, {{points, 16}, {out, 16}}, words, hip_stream, false, &s, &rc)) return rc;
     NearestArgs a;
-    a.points = points; a.out = out; a.n = n;
-    a.stack_levels = (uint32_t)std::max(1, r->bvh_depth);
-    a.refill_min = (uint32_t)r->rq_refill_min;
-    a.heads = r->rq_heads.ptr;
-    a.stack_hbm = r->rq_stack.ptr;
+    a.points = points; a.out = out; a.frame = query_frame(r, n);
     HIP_TRY(launch_nearest(r->view, a, r->num_cus, s));
     return query_recorded(r, s);
 }
 
 // ------------------------------------------------------------------ sphere casts (kernel_sphere_cast.hip)
-// Validated, ordered and given scratch as drt_renderer_nearest is: the kernel shares the claim heads and the closest-hit HBM stack.
+// The closest-hit HBM stack ({ref, enter} entries).
 int drt_renderer_sphere_cast(drt_renderer *r, const drt_scene *scene, const drt_ray *rays, const float *radii, drt_sweep_hit *out, uint32_t n,
                              void *hip_stream) {
-    if (!r || !scene) return fail(DRT_ERR_INVALID, "null argument");
-    if (n == 0) return DRT_OK;
-    if (!rays || !radii || !out) return fail(DRT_ERR_INVALID, "null ray, radius or result pointer");
-    if (((uintptr_t)rays & 15u) != 0 || ((uintptr_t)out & 15u) != 0 || ((uintptr_t)radii & 3u) != 0)
-        return fail(DRT_ERR_INVALID, "rays and results must be 16-byte aligned, radii 4-byte aligned");
-    if (n > 0x7fffffffu) return fail(DRT_ERR_INVALID, "at most 2^31 - 1 casts per call");
-    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
-    HIP_TRY(hipSetDevice(r->device));
-    (void)hipGetLastError();                   // (see render_batch_impl: only this call's own errors count)
-    if (!on_renderer_device(r, rays) || !on_renderer_device(r, radii) || !on_renderer_device(r, out))
-        return fail(DRT_ERR_INVALID, "rays, radii and results must be device memory on the renderer's device");
-    if (int rc = upload_scene(r, scene)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : r->stream;
-    if (int rc = query_order(r, s)) return rc;
-    if (int rc = traversal_scratch(r, s, false, true)) return rc;
+    static const QueryWords words = {"null ray, radius or result pointer", "rays and results must be 16-byte aligned, radii 4-byte aligned", "casts",
+                                     "rays, radii and results"};
+    hipStream_t s;
+    int rc;
+    if (!query_begin(r, scene, n, {{rays, 16}, {radii, 4}, {out, 16}}, words, hip_stream, false, &s, &rc)) return rc;
     SphereCastArgs a;
-    a.rays = rays; a.radii = radii; a.out = out; a.n = n;
-    a.stack_levels = (uint32_t)std::max(1, r->bvh_depth);
-    a.refill_min = (uint32_t)r->rq_refill_min;
-    a.heads = r->rq_heads.ptr;
-    a.stack_hbm = r->rq_stack.ptr;
+    a.rays = rays; a.radii = radii; a.out = out; a.frame = query_frame(r, n);
     HIP_TRY(launch_sphere_cast(r->view, a, r->num_cus, s));
     return query_recorded(r, s);
 }
 
 // ------------------------------------------------------------------ crossing counts, inside votes, signed distance (kernel_crossings.hip)
-// Validated, ordered and given scratch as the ray queries are: the kernel shares their claim heads and the occlusion query's HBM stack.
+// The occlusion query's HBM stack (ref entries).
 static int bad_rule(int32_t rule) {
     return fail(DRT_ERR_INVALID, "rule " + std::to_string(rule) + ": 0 (parity) or 1 (winding) expected");
 }
@@ -916,23 +920,11 @@ static int crossings_impl(drt_renderer *r, const drt_scene *scene, const void *i
     if (!in || !out) return fail(DRT_ERR_INVALID, "null query or result pointer");
     if (((uintptr_t)in & 15u) != 0 || ((uintptr_t)out & (out_align - 1)) != 0)
         return fail(DRT_ERR_INVALID, "queries must be 16-byte aligned, results " + std::to_string(out_align) + "-byte aligned");
-    if (n > 0x7fffffffu) return fail(DRT_ERR_INVALID, "at most 2^31 - 1 queries per call");
-    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
-    HIP_TRY(hipSetDevice(r->device));
-    (void)hipGetLastError();                   // (see render_batch_impl: only this call's own errors count)
-    if (!on_renderer_device(r, in) || !on_renderer_device(r, out))
-        return fail(DRT_ERR_INVALID, "queries and results must be device memory on the renderer's device");
-    if (int rc = upload_scene(r, scene)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : r->stream;
-    if (int rc = query_order(r, s)) return rc;
-    if (int rc = traversal_scratch(r, s, true, true)) return rc;
+    hipStream_t s;
+    if (int rc = query_open(r, scene, n, {in, out}, "queries", "queries and results", hip_stream, true, &s)) return rc;
     CrossingsArgs a;
-    a.in = in; a.out = out; a.n = n;
-    a.stack_levels = (uint32_t)std::max(1, r->bvh_depth);
-    a.refill_min = (uint32_t)r->rq_refill_min;
+    a.in = in; a.out = out; a.frame = query_frame(r, n);
     a.rule = (uint32_t)rule;
-    a.heads = r->rq_heads.ptr;
-    a.stack_hbm = r->rq_stack.ptr;
     HIP_TRY(launch_crossings(r->view, kind, a, r->num_cus, s));
     return query_recorded(r, s);
 }
@@ -955,8 +947,7 @@ int drt_renderer_signed_distance(drt_renderer *r, const drt_scene *scene, const 
 }
 
 // ------------------------------------------------------------------ ordered hit lists of rays (kernel_list_hits.hip)
-// Validated in crossings_impl's order, ordered and given scratch as it is: the kernel shares the claim heads and the occlusion query's
-// HBM stack.  counts may be null; hits may be null iff hits_capacity == 0 (a pure count); not both.
+// The occlusion query's HBM stack (ref entries).  counts may be null; hits may be null iff hits_capacity == 0 (a pure count); not both.
 int drt_renderer_list_hits(drt_renderer *r, const drt_scene *scene, const drt_ray *rays, const uint32_t *offsets, drt_hit *hits,
                            uint32_t hits_capacity, uint32_t *counts, uint32_t n, void *hip_stream) {
     if (!r || !scene) return fail(DRT_ERR_INVALID, "null argument");
@@ -966,32 +957,18 @@ int drt_renderer_list_hits(drt_renderer *r, const drt_scene *scene, const drt_ra
     if ((hits == nullptr) != (hits_capacity == 0)) return fail(DRT_ERR_INVALID, "hits must be null if and only if hits_capacity is 0");
     if (((uintptr_t)rays & 15u) != 0 || ((uintptr_t)hits & 15u) != 0 || ((uintptr_t)offsets & 3u) != 0 || ((uintptr_t)counts & 3u) != 0)
         return fail(DRT_ERR_INVALID, "rays and hits must be 16-byte aligned, offsets and counts 4-byte aligned");
-    if (n > 0x7fffffffu) return fail(DRT_ERR_INVALID, "at most 2^31 - 1 rays per call");
-    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
-    HIP_TRY(hipSetDevice(r->device));
-    (void)hipGetLastError();                   // (see render_batch_impl: only this call's own errors count)
-    if (!on_renderer_device(r, rays) || !on_renderer_device(r, offsets) || (hits && !on_renderer_device(r, hits)) ||
-        (counts && !on_renderer_device(r, counts)))
-        return fail(DRT_ERR_INVALID, "rays, offsets, hits and counts must be device memory on the renderer's device");
-    if (int rc = upload_scene(r, scene)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : r->stream;
-    if (int rc = query_order(r, s)) return rc;
-    if (int rc = traversal_scratch(r, s, true, true)) return rc;
+    hipStream_t s;
+    if (int rc = query_open(r, scene, n, {rays, offsets, hits, counts}, "rays", "rays, offsets, hits and counts", hip_stream, true, &s)) return rc;
     ListHitsArgs a;
     a.rays = rays; a.offsets = offsets; a.hits = hits; a.counts = counts;
-    a.hits_capacity = hits_capacity; a.n = n;
-    a.stack_levels = (uint32_t)std::max(1, r->bvh_depth);
-    a.refill_min = (uint32_t)r->rq_refill_min;
-    a.heads = r->rq_heads.ptr;
-    a.stack_hbm = r->rq_stack.ptr;
+    a.hits_capacity = hits_capacity; a.frame = query_frame(r, n);
     HIP_TRY(launch_list_hits(r->view, a, r->num_cus, s));
     return query_recorded(r, s);
 }
 
 // ------------------------------------------------------------------ nearest-triangle lists of points (kernel_near_list.hip)
-// Validated in drt_renderer_list_hits' order with the mode first after the handles, ordered and given scratch as drt_renderer_nearest
-// is: the kernel shares the claim heads and the closest-hit HBM stack.  counts and surf may be null; near may be null iff
-// near_capacity == 0 (a pure count); near and counts not both.
+// drt_renderer_list_hits' checks in its order with the mode first after the handles; the closest-hit HBM stack ({ref, box2} entries).
+// counts and surf may be null; near may be null iff near_capacity == 0 (a pure count); near and counts not both.
 int drt_renderer_nearest_list(drt_renderer *r, const drt_scene *scene, const drt_point *points, const uint32_t *offsets, drt_near *near,
                               drt_near_surf *surf, uint32_t near_capacity, uint32_t *counts, uint32_t n, int32_t mode, void *hip_stream) {
     if (!r || !scene) return fail(DRT_ERR_INVALID, "null argument");
@@ -1004,32 +981,20 @@ int drt_renderer_nearest_list(drt_renderer *r, const drt_scene *scene, const drt
     if (((uintptr_t)points & 15u) != 0 || ((uintptr_t)near & 15u) != 0 || ((uintptr_t)surf & 15u) != 0 || ((uintptr_t)offsets & 3u) != 0 ||
         ((uintptr_t)counts & 3u) != 0)
         return fail(DRT_ERR_INVALID, "points, near and surf must be 16-byte aligned, offsets and counts 4-byte aligned");
-    if (n > 0x7fffffffu) return fail(DRT_ERR_INVALID, "at most 2^31 - 1 points per call");
-    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
-    HIP_TRY(hipSetDevice(r->device));
-    (void)hipGetLastError();                   // (see render_batch_impl: only this call's own errors count)
-    if (!on_renderer_device(r, points) || !on_renderer_device(r, offsets) || (near && !on_renderer_device(r, near)) ||
-        (surf && !on_renderer_device(r, surf)) || (counts && !on_renderer_device(r, counts)))
-        return fail(DRT_ERR_INVALID, "points, offsets, near, surf and counts must be device memory on the renderer's device");
-    if (int rc = upload_scene(r, scene)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : r->stream;
-    if (int rc = query_order(r, s)) return rc;
-    if (int rc = traversal_scratch(r, s, false, true)) return rc;
+    hipStream_t s;
+    if (int rc = query_open(r, scene, n, {points, offsets, near, surf, counts}, "points", "points, offsets, near, surf and counts", hip_stream, false, &s))
+        return rc;
     NearListArgs a;
     a.points = points; a.offsets = offsets; a.near = near; a.surf = near_capacity ? surf : nullptr; a.counts = counts;
-    a.near_capacity = near_capacity; a.n = n;
-    a.stack_levels = (uint32_t)std::max(1, r->bvh_depth);
-    a.refill_min = (uint32_t)r->rq_refill_min;
-    a.heads = r->rq_heads.ptr;
-    a.stack_hbm = r->rq_stack.ptr;
+    a.near_capacity = near_capacity; a.frame = query_frame(r, n);
     HIP_TRY(launch_near_list(r->view, mode == DRT_NEAR_K, a, r->num_cus, s));
     return query_recorded(r, s);
 }
 
 // ------------------------------------------------------------------ box overlap queries (kernel_overlap.hip)
-// Validated in drt_renderer_nearest_list's order with the mode first after the handles, ordered and given scratch as
-// drt_renderer_list_hits is: the kernel shares the claim heads and the occlusion query's HBM stack.  Mode LIST: counts may be null,
-// prims may be null iff prims_capacity == 0 (a pure count), not both.  Mode ANY: no prims, no capacity, offsets is not read.
+// drt_renderer_nearest_list's checks in its order with the mode first after the handles; the occlusion query's HBM stack (ref entries).
+// Mode LIST: counts may be null, prims may be null iff prims_capacity == 0 (a pure count), not both.  Mode ANY: no prims, no
+// capacity, offsets is not read.
 int drt_renderer_overlap_boxes(drt_renderer *r, const drt_scene *scene, const drt_box *boxes, const uint32_t *offsets, int32_t *prims,
                                uint32_t prims_capacity, uint32_t *counts, uint32_t n, int32_t mode, void *hip_stream) {
     if (!r || !scene) return fail(DRT_ERR_INVALID, "null argument");
@@ -1048,31 +1013,18 @@ int drt_renderer_overlap_boxes(drt_renderer *r, const drt_scene *scene, const dr
     }
     if (((uintptr_t)boxes & 15u) != 0 || ((uintptr_t)prims & 3u) != 0 || ((uintptr_t)offsets & 3u) != 0 || ((uintptr_t)counts & 3u) != 0)
         return fail(DRT_ERR_INVALID, "boxes must be 16-byte aligned, offsets, prims and counts 4-byte aligned");
-    if (n > 0x7fffffffu) return fail(DRT_ERR_INVALID, "at most 2^31 - 1 boxes per call");
-    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
-    HIP_TRY(hipSetDevice(r->device));
-    (void)hipGetLastError();                   // (see render_batch_impl: only this call's own errors count)
-    if (!on_renderer_device(r, boxes) || (offsets && !on_renderer_device(r, offsets)) || (prims && !on_renderer_device(r, prims)) ||
-        (counts && !on_renderer_device(r, counts)))
-        return fail(DRT_ERR_INVALID, "boxes, offsets, prims and counts must be device memory on the renderer's device");
-    if (int rc = upload_scene(r, scene)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : r->stream;
-    if (int rc = query_order(r, s)) return rc;
-    if (int rc = traversal_scratch(r, s, true, true)) return rc;
+    hipStream_t s;
+    if (int rc = query_open(r, scene, n, {boxes, offsets, prims, counts}, "boxes", "boxes, offsets, prims and counts", hip_stream, true, &s))
+        return rc;
     OverlapArgs a;
     a.boxes = boxes; a.offsets = offsets; a.prims = prims; a.counts = counts;
-    a.prims_capacity = prims_capacity; a.n = n;
-    a.stack_levels = (uint32_t)std::max(1, r->bvh_depth);
-    a.refill_min = (uint32_t)r->rq_refill_min;
-    a.heads = r->rq_heads.ptr;
-    a.stack_hbm = r->rq_stack.ptr;
+    a.prims_capacity = prims_capacity; a.frame = query_frame(r, n);
     HIP_TRY(launch_overlap(r->view, any, a, r->num_cus, s));
     return query_recorded(r, s);
 }
 
 // ------------------------------------------------------------------ triangle overlap queries (kernel_tri_overlap.hip)
-// drt_renderer_overlap_boxes' checks in its order, word for word, and its scratch: the kernel shares the claim heads and the occlusion
-// query's HBM stack.
+// drt_renderer_overlap_boxes' checks in its order, word for word; the occlusion query's HBM stack (ref entries).
 int drt_renderer_overlap_triangles(drt_renderer *r, const drt_scene *scene, const drt_tri *tris, const uint32_t *offsets, int32_t *prims,
                                    uint32_t prims_capacity, uint32_t *counts, uint32_t n, int32_t mode, void *hip_stream) {
     if (!r || !scene) return fail(DRT_ERR_INVALID, "null argument");
@@ -1091,24 +1043,12 @@ int drt_renderer_overlap_triangles(drt_renderer *r, const drt_scene *scene, cons
     }
     if (((uintptr_t)tris & 15u) != 0 || ((uintptr_t)prims & 3u) != 0 || ((uintptr_t)offsets & 3u) != 0 || ((uintptr_t)counts & 3u) != 0)
         return fail(DRT_ERR_INVALID, "tris must be 16-byte aligned, offsets, prims and counts 4-byte aligned");
-    if (n > 0x7fffffffu) return fail(DRT_ERR_INVALID, "at most 2^31 - 1 triangles per call");
-    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
-    HIP_TRY(hipSetDevice(r->device));
-    (void)hipGetLastError();                   // (see render_batch_impl: only this call's own errors count)
-    if (!on_renderer_device(r, tris) || (offsets && !on_renderer_device(r, offsets)) || (prims && !on_renderer_device(r, prims)) ||
-        (counts && !on_renderer_device(r, counts)))
-        return fail(DRT_ERR_INVALID, "tris, offsets, prims and counts must be device memory on the renderer's device");
-    if (int rc = upload_scene(r, scene)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : r->stream;
-    if (int rc = query_order(r, s)) return rc;
-    if (int rc = traversal_scratch(r, s, true, true)) return rc;
+    hipStream_t s;
+    if (int rc = query_open(r, scene, n, {tris, offsets, prims, counts}, "triangles", "tris, offsets, prims and counts", hip_stream, true, &s))
+        return rc;
     TriOverlapArgs a;
     a.tris = tris; a.offsets = offsets; a.prims = prims; a.counts = counts;
-    a.prims_capacity = prims_capacity; a.n = n;
-    a.stack_levels = (uint32_t)std::max(1, r->bvh_depth);
-    a.refill_min = (uint32_t)r->rq_refill_min;
-    a.heads = r->rq_heads.ptr;
-    a.stack_hbm = r->rq_stack.ptr;
+    a.prims_capacity = prims_capacity; a.frame = query_frame(r, n);
     HIP_TRY(launch_tri_overlap(r->view, any, a, r->num_cus, s));
     return query_recorded(r, s);
 }
@@ -1162,12 +1102,8 @@ int drt_renderer_radiance(drt_renderer *r, const drt_scene *scene, const drt_pat
     std::memset(&fp, 0, sizeof fp);
     fill_frame_params(r, nullptr, fp);
     RadianceArgs a;
-    a.rays = rays; a.out = reinterpret_cast<float4 *>(out); a.n = n;
-    a.stack_levels = (uint32_t)std::max(1, r->bvh_depth);
-    a.refill_min = (uint32_t)r->rq_refill_min;
+    a.rays = rays; a.out = reinterpret_cast<float4 *>(out); a.frame = query_frame(r, n);
     a.accumulate = accumulate != 0;
-    a.heads = r->rq_heads.ptr;
-    a.stack_hbm = r->rq_stack.ptr;
     HIP_TRY(launch_radiance(r->view, fp, r->scene_has_alpha, a, r->num_cus, s));
     return query_recorded(r, s);
 }

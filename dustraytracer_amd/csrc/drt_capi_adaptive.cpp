@@ -130,12 +130,8 @@ int drt_renderer_render_adaptive(drt_renderer *r, const drt_camera *cam, const d
             if (int rc = traversal_scratch(r, s, false, true)) return rc;
             HIP_TRY(launch_adaptive_rays(ra, s));
             RadianceArgs a;
-            a.rays = r->ad_rays.ptr; a.out = r->ad_samples.ptr; a.n = ra.n_rays;
-            a.stack_levels = (uint32_t)std::max(1, r->bvh_depth);
-            a.refill_min = (uint32_t)r->rq_refill_min;
+            a.rays = r->ad_rays.ptr; a.out = r->ad_samples.ptr; a.frame = query_frame(r, ra.n_rays);
             a.accumulate = 0;
-            a.heads = r->rq_heads.ptr;
-            a.stack_hbm = r->rq_stack.ptr;
             HIP_TRY(launch_radiance(r->view, fp, r->scene_has_alpha, a, r->num_cus, s));
             if (int rc = query_recorded(r, s)) return rc;
         }

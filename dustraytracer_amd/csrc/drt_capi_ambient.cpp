@@ -36,7 +36,7 @@ int drt_renderer_ambient_occlusion(drt_renderer *r, const drt_scene *scene, cons
     AmbientArgs a;
     a.pts = reinterpret_cast<const AoPoint *>(pts); a.out = reinterpret_cast<AoResult *>(out); a.n = n;
     a.samples = params->samples; a.seed_hash = ao_pcg(params->seed); a.first = params->first;
-    a.stack_levels = (uint32_t)std::max(1, r->bvh_depth);
+    a.stack_levels = query_stack_levels(r);
     a.heads = r->ao_heads.ptr;
     a.stack_hbm = r->rq_stack.ptr;
     HIP_TRY(launch_ambient_init(a, s));

@@ -9,7 +9,7 @@ using namespace drt;
 
 extern "C" {
 
-// The kernel shares the claim heads and the closest-hit query's HBM stack ({ref, enter} entries), as drt_renderer_sphere_cast does.
+// The closest-hit query's HBM stack ({ref, enter} entries).
 int drt_renderer_triangle_cast(drt_renderer *r, const drt_scene *scene, const drt_tri *tris, const drt_motion *motions, drt_tri_hit *out,
                                uint32_t n, int32_t mode, void *hip_stream) {
     if (!r || !scene) return fail(DRT_ERR_INVALID, "null argument");
@@ -19,22 +19,10 @@ int drt_renderer_triangle_cast(drt_renderer *r, const drt_scene *scene, const dr
     if (!tris || !motions || !out) return fail(DRT_ERR_INVALID, "null triangle, motion or result pointer");
     if (((uintptr_t)tris & 15u) != 0 || ((uintptr_t)motions & 15u) != 0 || ((uintptr_t)out & 15u) != 0)
         return fail(DRT_ERR_INVALID, "tris, motions and results must be 16-byte aligned");
-    if (n > 0x7fffffffu) return fail(DRT_ERR_INVALID, "at most 2^31 - 1 casts per call");
-    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
-    HIP_TRY(hipSetDevice(r->device));
-    (void)hipGetLastError();                   // (see render_batch_impl: only this call's own errors count)
-    if (!on_renderer_device(r, tris) || !on_renderer_device(r, motions) || !on_renderer_device(r, out))
-        return fail(DRT_ERR_INVALID, "tris, motions and results must be device memory on the renderer's device");
-    if (int rc = upload_scene(r, scene)) return rc;
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : r->stream;
-    if (int rc = query_order(r, s)) return rc;
-    if (int rc = traversal_scratch(r, s, false, true)) return rc;
+    hipStream_t s;
+    if (int rc = query_open(r, scene, n, {tris, motions, out}, "casts", "tris, motions and results", hip_stream, false, &s)) return rc;
     TriCastArgs a;
-    a.tris = tris; a.motions = motions; a.out = out; a.n = n;
-    a.stack_levels = (uint32_t)std::max(1, r->bvh_depth);
-    a.refill_min = (uint32_t)r->rq_refill_min;
-    a.heads = r->rq_heads.ptr;
-    a.stack_hbm = r->rq_stack.ptr;
+    a.tris = tris; a.motions = motions; a.out = out; a.frame = query_frame(r, n);
     HIP_TRY(launch_tri_cast(r->view, mode == DRT_TRICAST_ANY, a, r->num_cus, s));
     return query_recorded(r, s);
 }

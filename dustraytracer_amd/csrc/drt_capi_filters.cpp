@@ -70,7 +70,7 @@ static int enqueue_guides(drt_renderer *r, const drt_camera *cam, const drt_scen
     GuideArgs a;
     a.out = guides;
     a.frame = frame_index;
-    a.stack_levels = (uint32_t)std::max(1, r->bvh_depth);
+    a.stack_levels = query_stack_levels(r);
     a.stack_hbm = r->rq_stack.ptr;
     HIP_TRY(launch_guides(r->view, fp, a, r->num_cus, s));
     return query_recorded(r, s);

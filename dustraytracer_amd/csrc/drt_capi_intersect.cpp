@@ -10,7 +10,8 @@ using namespace drt;
 extern "C" {
 
 // drt_renderer_plane_sections' checks in mode LIST, in its order (tris for planes; out 16-byte aligned: the kernel writes a record as
-// two 16-byte words).  The kernel shares the claim heads and the occlusion query's HBM stack, as drt_renderer_overlap_triangles does.
+// two 16-byte words).  The occlusion query's HBM stack (ref entries).  The opening is written out, not query_open: the check of
+// leaves_ascending stands between the upload and the scratch.
 int drt_renderer_intersect_triangles(drt_renderer *r, const drt_scene *scene, const drt_tri *tris, const uint32_t *offsets, drt_isect *out,
                                      uint32_t out_capacity, uint32_t *counts, uint32_t n, void *hip_stream) {
     if (!r || !scene) return fail(DRT_ERR_INVALID, "null argument");
@@ -36,11 +37,7 @@ int drt_renderer_intersect_triangles(drt_renderer *r, const drt_scene *scene, co
     if (int rc = traversal_scratch(r, s, true, true)) return rc;
     IntersectArgs a;
     a.tris = tris; a.offsets = offsets; a.out = out; a.counts = counts;
-    a.out_capacity = out_capacity; a.n = n;
-    a.stack_levels = (uint32_t)std::max(1, r->bvh_depth);
-    a.refill_min = (uint32_t)r->rq_refill_min;
-    a.heads = r->rq_heads.ptr;
-    a.stack_hbm = r->rq_stack.ptr;
+    a.out_capacity = out_capacity; a.frame = query_frame(r, n);
     HIP_TRY(launch_intersect(r->view, a, r->num_cus, s));
     return query_recorded(r, s);
 }

@@ -41,26 +41,14 @@ int winding_impl(drt_renderer *r, const drt_scene *scene, const drt_point *point
     if (!points || !out) return fail(DRT_ERR_INVALID, "null point or result pointer");
     if (((uintptr_t)points & 15u) != 0 || ((uintptr_t)out & (out_align - 1)) != 0)
         return fail(DRT_ERR_INVALID, "points must be 16-byte aligned, results " + std::to_string(out_align) + "-byte aligned");
-    if (n > 0x7fffffffu) return fail(DRT_ERR_INVALID, "at most 2^31 - 1 points per call");
-    if (r->pending) return fail(DRT_ERR_INVALID, "an asynchronous render batch is pending: drt_renderer_wait first");
-    HIP_TRY(hipSetDevice(r->device));
-    (void)hipGetLastError();                   // (see render_batch_impl: only this call's own errors count)
-    if (!on_renderer_device(r, points) || !on_renderer_device(r, out))
-        return fail(DRT_ERR_INVALID, "points and results must be device memory on the renderer's device");
-    if (int rc = upload_scene(r, scene)) return rc;             // (refuses a tree deeper than 64 levels, as the traversing queries do)
-    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : r->stream;
-    if (int rc = query_order(r, s)) return rc;
-    if (int rc = traversal_scratch(r, s, true, true)) return rc;
+    hipStream_t s;              // (query_open's upload refuses a tree deeper than 64 levels, as the traversing queries do)
+    if (int rc = query_open(r, scene, n, {points, out}, "points", "points and results", hip_stream, true, &s)) return rc;
     if (int rc = winding_moments(r, scene, s)) return rc;
     WindingArgs a;
-    a.points = points; a.out = out; a.n = n;
-    a.stack_levels = (uint32_t)std::max(1, r->bvh_depth);
-    a.refill_min = (uint32_t)r->rq_refill_min;
+    a.points = points; a.out = out; a.frame = query_frame(r, n);
     a.beta2 = beta * beta;
     a.threshold = threshold;
     a.moments = r->wn_moments.ptr;
-    a.heads = r->rq_heads.ptr;
-    a.stack_hbm = r->rq_stack.ptr;
     HIP_TRY(launch_winding(r->view, kind, a, r->num_cus, s));
     return query_recorded(r, s);
 }

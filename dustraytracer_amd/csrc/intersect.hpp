@@ -25,11 +25,7 @@ struct IntersectArgs {
     void *out;                   // drt_isect[out_capacity] (32 B, 16-B aligned); null when out_capacity == 0
     uint32_t *counts;            // n words or null: every record of the query, stored or not
     uint32_t out_capacity;
-    uint32_t n;                  // < 2^31
-    uint32_t stack_levels;       // tree depth (<= 64): the stack never holds more entries
-    uint32_t refill_min;         // a wave claims new queries once this many of its lanes are idle (1..64)
-    unsigned int *heads;         // kRqHeadWords zeroed words
-    uint32_t *stack_hbm;         // levels beyond the LDS ones: [(level - K) * grid threads + thread], 4 B entries
+    QueryFrame frame;            // n, tree depth, refill threshold, claim heads, HBM stack: 4 B stack entries
 };
 
 // The launch bounds and the workgroups per CU of the two instantiations' grids (kernel_intersect.hip's header says how they were

@@ -10,11 +10,7 @@
 //   vote       three rays from the point, tmin = 0, tmax = +inf, directions kInsideDirs; ray j votes inside iff count_j is odd
 //              (rule 0) or winding_j != 0 (rule 1); the answer is the number of votes, inside = 2 or more
 //
-// Shape: kernel_ray_query.hip's ray_query_kernel<true>.  Persistent grid (8 workgroups of 256 threads per CU = 8 waves per SIMD),
-// one query per lane, every trip of a wave's loop pops one node per lane, and when at least `refill_min` lanes are idle the wave
-// claims that many queries with ONE atomic on one of kRqShards sharded heads (ballot / mbcnt hand the claim out).  Traversal
-// stack: 32-bit node references at [level][thread] -- the bottom kRqLdsLevelsOccluded levels in LDS (one bank per lane), the rest
-// in the renderer's HBM array with the same coalesced layout.  A result depends only on its query and the scene.
+// Grid, claim and stack: query_frame.hpp.  One query per lane; stack entries ref, kRqLdsLevelsOccluded levels in LDS.
 //
 // Point mode keeps a lane on its point for all three rays: when the stack empties the lane banks the ray's vote in a register and
 // starts the next direction on the same trip, and it stores once, after the third.
@@ -24,15 +20,11 @@
 #include "device_scene.hpp"
 #include "device_access.hpp"
 #include "crossings.hpp"
+#include "query_frame.hpp"
 
 namespace drt {
 
 namespace {
-
-// rank of this lane among the lanes set in `mask` (v_mbcnt): the claim hands queries to idle lanes in lane order
-DRT_DEV int lane_rank(uint64_t mask) {
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
 
 DRT_DEV f3 inside_dir(int j) {
     return mk3(j == 0 ? kInsideDirs[0][0] : (j == 1 ? kInsideDirs[1][0] : kInsideDirs[2][0]),
@@ -44,11 +36,11 @@ template <bool POINTS>
 __global__ __launch_bounds__(kRqThreads, kRqWavesPerSimd) void crossings_kernel(const SceneView sc, const CrossingsArgs a, const CrossingsOut kind) {
     constexpr int K = kRqLdsLevelsOccluded;
     __shared__ uint32_t s_ref[K][kRqThreads];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const uint32_t gthread = blockIdx.x * kRqThreads + tid, gthreads = gridDim.x * kRqThreads;
-    uint32_t shard = (gthread >> 6) % kRqShards;            // home shard of this wave; on to the next one when it is empty
+    const int tid = threadIdx.x;
+    const uint32_t gthread = blockIdx.x * kRqThreads + tid;
+    const StackLane st = {tid, gthread, gridDim.x * kRqThreads, a.frame.stack_levels, a.frame.stack_hbm};
+    uint32_t shard = home_shard(gthread);
     int shards_empty = 0;
-    const uint32_t levels = a.stack_levels;                  // = tree depth: the stack never holds more entries
 
     int rid = -1;                                            // this lane's query, -1 = idle
     Ray ray;
@@ -72,30 +64,10 @@ __global__ __launch_bounds__(kRqThreads, kRqWavesPerSimd) void crossings_kernel(
     for (;;) {
         // ---- refill: claim queries for the idle lanes (wave-uniform) ----
         const uint64_t idle = __ballot(rid < 0);
-        const uint32_t n_idle = (uint32_t)__popcll(idle);
-        if (shards_empty < kRqShards && (n_idle >= a.refill_min || n_idle == 64u)) {
-            const int my_rank = lane_rank(idle);
+        if (claim_due(shards_empty, idle, a.frame)) {
             const bool was_idle = rid < 0;
-            uint32_t filled = 0;
-            while (filled < n_idle && shards_empty < kRqShards) {
-                const uint32_t want = n_idle - filled;
-                const uint32_t s_begin = (uint32_t)((uint64_t)a.n * shard / kRqShards);
-                const uint32_t len = (uint32_t)((uint64_t)a.n * (shard + 1) / kRqShards) - s_begin;
-                // lane 0 claims and clips the claim to the shard; start / got go to the wave (64-bit signed arithmetic: the
-                // shard's remainder len - b is negative once other waves have emptied it)
-                int64_t start = 0, got = 0;
-                if (lane == 0) {
-                    const int64_t b = (int64_t)atomicAdd(a.heads + shard * kRqShardStride, want);
-                    const int64_t left = (int64_t)len - b;
-                    if (left > 0) { start = (int64_t)s_begin + b; got = left < (int64_t)want ? left : (int64_t)want; }
-                }
-                start = __shfl(start, 0);
-                got = __shfl(got, 0);
-                if (got <= 0) { shard = (shard + 1) % kRqShards; shards_empty++; continue; }
-                const int64_t k = (int64_t)my_rank - (int64_t)filled;
-                if (was_idle && k >= 0 && k < got && start + k < (int64_t)a.n) rid = (int)(start + k);
-                filled += (uint32_t)got;
-            }
+            const Claimed c = claim_take(shard, shards_empty, rid, idle, a.frame);
+            shard = c.shard; shards_empty = c.shards_empty; rid = c.rid;
             if (was_idle && rid >= 0) {
                 if (POINTS) {
                     // a new point: one 16-byte load (drt_point = p, max_dist; max_dist is not used); the first of its three rays
@@ -112,12 +84,11 @@ __global__ __launch_bounds__(kRqThreads, kRqWavesPerSimd) void crossings_kernel(
                 }
             }
         }
-        if (shards_empty >= kRqShards && __ballot(rid >= 0) == 0) break;
+        if (claim_drained(shards_empty, rid)) break;
 
         // ---- one traversal step per busy lane ----
         if (rid >= 0 && sp > 0) {
-            --sp;
-            const uint32_t ref = sp < (uint32_t)K ? s_ref[sp][tid] : a.stack_hbm[(size_t)(sp - K) * gthreads + gthread];
+            const uint32_t ref = stack_pop(s_ref, st, sp);
             if (ref & kLeafBit) {
                 const LeafRange leaf = sc.leaves[ref & ~kLeafBit];
                 for (int i = leaf.start; i < leaf.start + leaf.count; i++) {
@@ -131,19 +102,7 @@ __global__ __launch_bounds__(kRqThreads, kRqWavesPerSimd) void crossings_kernel(
                 const float d1 = slab_intersect(c.min1, c.max1, ray);
                 const float d2 = slab_intersect(c.min2, c.max2, ray);
                 const bool push1 = d1 >= 0 && !(d1 > tmax), push2 = d2 >= 0 && !(d2 > tmax);
-                const bool far1 = d1 > d2;                                                            // farther child first
-                const uint32_t ra = far1 ? c.ref1 : c.ref2, rb = far1 ? c.ref2 : c.ref1;
-                const bool pa = far1 ? push1 : push2, pb = far1 ? push2 : push1;
-#pragma unroll
-                for (int k = 0; k < 2; k++) {
-                    const bool p = k == 0 ? pa : pb;
-                    if (p && sp < levels) {
-                        const uint32_t r = k == 0 ? ra : rb;
-                        if (sp < (uint32_t)K) s_ref[sp][tid] = r;
-                        else a.stack_hbm[(size_t)(sp - K) * gthreads + gthread] = r;
-                        ++sp;
-                    }
-                }
+                push_far_first(s_ref, st, sp, c.ref1, d1, push1, c.ref2, d2, push2);            // farther child first
             }
         }
 
@@ -169,9 +128,8 @@ __global__ __launch_bounds__(kRqThreads, kRqWavesPerSimd) void crossings_kernel(
 }  // namespace
 
 hipError_t launch_crossings(const SceneView &sc, CrossingsOut kind, const CrossingsArgs &args, int num_cus, hipStream_t stream) {
-    if (args.n == 0) return hipSuccess;
-    const uint32_t want = (args.n + kRqThreads - 1) / kRqThreads;
-    const uint32_t blocks = std::min<uint32_t>(want, (uint32_t)ray_query_max_blocks(num_cus));
+    if (args.frame.n == 0) return hipSuccess;
+    const uint32_t blocks = query_blocks(args.frame.n, num_cus);
     if (kind == CrossingsOut::crossings) hipLaunchKernelGGL(crossings_kernel<false>, dim3(blocks), dim3(kRqThreads), 0, stream, sc, args, kind);
     else hipLaunchKernelGGL(crossings_kernel<true>, dim3(blocks), dim3(kRqThreads), 0, stream, sc, args, kind);
     return hipGetLastError();

@@ -13,10 +13,7 @@
 //   segment    D = cross(nq, nt), its largest axis j, the four cut points, the overlap of the two intervals on axis j, oriented along D
 //   list       drt_renderer_plane_sections' in mode LIST: cap slots, the records, the miss record behind them, counts[i] = total
 //
-// Shape: kernel_tri_overlap.hip's.  Persistent grid of 256-thread workgroups, one query per lane, every trip of a wave's loop pops one
-// node per lane, and when at least `refill_min` lanes are idle the wave claims that many queries with ONE atomic on one of kRqShards
-// sharded heads.  Traversal stack: 32-bit node references at [level][thread] -- the bottom kRqLdsLevelsOccluded levels in LDS, the rest
-// in the renderer's HBM array.
+// Grid, claim and stack: query_frame.hpp.  One query per lane; stack entries ref, kRqLdsLevelsOccluded levels in LDS.
 //
 // The list is appended to and never inserted into: child 1 is popped before child 2, and the entry point refuses a tree whose leaves,
 // child 1 first, do not hold ascending triangle ranges (leaves_ascending), so a query's records arrive in ascending triangle index.
@@ -37,25 +34,21 @@
 #include "device_scene.hpp"
 #include "device_access.hpp"
 #include "intersect.hpp"
+#include "query_frame.hpp"
 
 namespace drt {
 
 namespace {
 
-// rank of this lane among the lanes set in `mask` (v_mbcnt): the claim hands queries to idle lanes in lane order
-DRT_DEV int lane_rank(uint64_t mask) {
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
-
 template <bool STORE>
 __global__ __launch_bounds__(kRqThreads, STORE ? kIntersectFillWavesPerSimd : kIntersectCountWavesPerSimd) void intersect_kernel(const SceneView sc, const IntersectArgs a) {
     constexpr int K = kRqLdsLevelsOccluded;
     __shared__ uint32_t s_ref[K][kRqThreads];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const uint32_t gthread = blockIdx.x * kRqThreads + tid, gthreads = gridDim.x * kRqThreads;
-    uint32_t shard = (gthread >> 6) % kRqShards;            // home shard of this wave; on to the next one when it is empty
+    const int tid = threadIdx.x;
+    const uint32_t gthread = blockIdx.x * kRqThreads + tid;
+    const StackLane st = {tid, gthread, gridDim.x * kRqThreads, a.frame.stack_levels, a.frame.stack_hbm};
+    uint32_t shard = home_shard(gthread);
     int shards_empty = 0;
-    const uint32_t levels = a.stack_levels;                  // = tree depth: the stack never holds more entries
     float4 *const out = reinterpret_cast<float4 *>(a.out);
 
     int rid = -1;                                            // this lane's query, -1 = idle
@@ -68,30 +61,10 @@ __global__ __launch_bounds__(kRqThreads, STORE ? kIntersectFillWavesPerSimd : kI
     for (;;) {
         // ---- refill: claim queries for the idle lanes (wave-uniform) ----
         const uint64_t idle = __ballot(rid < 0);
-        const uint32_t n_idle = (uint32_t)__popcll(idle);
-        if (shards_empty < kRqShards && (n_idle >= a.refill_min || n_idle == 64u)) {
-            const int my_rank = lane_rank(idle);
+        if (claim_due(shards_empty, idle, a.frame)) {
             const bool was_idle = rid < 0;
-            uint32_t filled = 0;
-            while (filled < n_idle && shards_empty < kRqShards) {
-                const uint32_t want = n_idle - filled;
-                const uint32_t s_begin = (uint32_t)((uint64_t)a.n * shard / kRqShards);
-                const uint32_t len = (uint32_t)((uint64_t)a.n * (shard + 1) / kRqShards) - s_begin;
-                // lane 0 claims and clips the claim to the shard; start / got go to the wave (64-bit signed arithmetic: the
-                // shard's remainder len - b is negative once other waves have emptied it)
-                int64_t start = 0, got = 0;
-                if (lane == 0) {
-                    const int64_t b = (int64_t)atomicAdd(a.heads + shard * kRqShardStride, want);
-                    const int64_t left = (int64_t)len - b;
-                    if (left > 0) { start = (int64_t)s_begin + b; got = left < (int64_t)want ? left : (int64_t)want; }
-                }
-                start = __shfl(start, 0);
-                got = __shfl(got, 0);
-                if (got <= 0) { shard = (shard + 1) % kRqShards; shards_empty++; continue; }
-                const int64_t k = (int64_t)my_rank - (int64_t)filled;
-                if (was_idle && k >= 0 && k < got && start + k < (int64_t)a.n) rid = (int)(start + k);
-                filled += (uint32_t)got;
-            }
+            const Claimed c = claim_take(shard, shards_empty, rid, idle, a.frame);
+            shard = c.shard; shards_empty = c.shards_empty; rid = c.rid;
             if (was_idle && rid >= 0) {
                 // a new query: three 16-byte loads (drt_tri), its bounds and normal, and the two offsets of its segment
                 const TriOverlapVerts t = tri_overlap_load(a.tris, (uint32_t)rid);
@@ -114,12 +87,11 @@ __global__ __launch_bounds__(kRqThreads, STORE ? kIntersectFillWavesPerSimd : kI
                 }
             }
         }
-        if (shards_empty >= kRqShards && __ballot(rid >= 0) == 0) break;
+        if (claim_drained(shards_empty, rid)) break;
 
         // ---- one traversal step per busy lane ----
         if (rid >= 0 && sp > 0) {
-            --sp;
-            const uint32_t ref = sp < (uint32_t)K ? s_ref[sp][tid] : a.stack_hbm[(size_t)(sp - K) * gthreads + gthread];
+            const uint32_t ref = stack_pop(s_ref, st, sp);
             if (ref & kLeafBit) {
                 const LeafRange leaf = sc.leaves[ref & ~kLeafBit];
                 for (int i = leaf.start; i < leaf.start + leaf.count; i++) {
@@ -137,16 +109,8 @@ __global__ __launch_bounds__(kRqThreads, STORE ? kIntersectFillWavesPerSimd : kI
                 const ChildPair c = load_children(sc.inner, ref);
                 const bool push1 = overlap_cull_passes(qmin, qmax, c.min1, c.max1);
                 const bool push2 = overlap_cull_passes(qmin, qmax, c.min2, c.max2);
-#pragma unroll
-                for (int k = 0; k < 2; k++) {                                           // child 2 first
-                    const bool p = k == 0 ? push2 : push1;
-                    if (p && sp < levels) {
-                        const uint32_t r = k == 0 ? c.ref2 : c.ref1;
-                        if (sp < (uint32_t)K) s_ref[sp][tid] = r;
-                        else a.stack_hbm[(size_t)(sp - K) * gthreads + gthread] = r;
-                        ++sp;
-                    }
-                }
+                stack_push(s_ref, st, sp, c.ref2, push2);                               // child 2 first
+                stack_push(s_ref, st, sp, c.ref1, push1);
             }
         }
 
@@ -168,13 +132,9 @@ __global__ __launch_bounds__(kRqThreads, STORE ? kIntersectFillWavesPerSimd : kI
 }  // namespace
 
 hipError_t launch_intersect(const SceneView &sc, const IntersectArgs &args, int num_cus, hipStream_t stream) {
-    if (args.n == 0) return hipSuccess;
-    const uint32_t want = (args.n + kRqThreads - 1) / kRqThreads;
-    // the instantiation's waves per SIMD as workgroups per CU (4 waves each, one per SIMD): never more than ray_query_max_blocks, whose
-    // HBM stack it uses
+    if (args.frame.n == 0) return hipSuccess;
     const bool fill = args.out_capacity != 0;
-    const uint32_t resident = (uint32_t)std::max(1, num_cus) * (uint32_t)(fill ? kIntersectFillWavesPerSimd : kIntersectCountWavesPerSimd);
-    const uint32_t blocks = std::min<uint32_t>(want, std::min<uint32_t>(resident, (uint32_t)ray_query_max_blocks(num_cus)));
+    const uint32_t blocks = query_blocks(args.frame.n, num_cus, fill ? kIntersectFillWavesPerSimd : kIntersectCountWavesPerSimd);
     if (fill) hipLaunchKernelGGL(intersect_kernel<true>, dim3(blocks), dim3(kRqThreads), 0, stream, sc, args);
     else hipLaunchKernelGGL(intersect_kernel<false>, dim3(blocks), dim3(kRqThreads), 0, stream, sc, args);
     return hipGetLastError();

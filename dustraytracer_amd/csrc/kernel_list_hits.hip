@@ -11,10 +11,7 @@
 //   segment    cap = offsets[i+1] > offsets[i] ? the difference : 0, clamped so that offsets[i] + cap <= hits_capacity; slots
 //              0 .. min(cap, total) - 1 the list, the rest of the cap slots the miss record {tmax, -1, 0, 0}; counts[i] = total
 //
-// Shape: kernel_crossings.hip's crossings_kernel<false>.  Persistent grid (8 workgroups of 256 threads per CU = 8 waves per SIMD), one
-// ray per lane, every trip of a wave's loop pops one node per lane, and when at least `refill_min` lanes are idle the wave claims that
-// many rays with ONE atomic on one of kRqShards sharded heads.  Traversal stack: 32-bit node references at [level][thread] -- the
-// bottom kRqLdsLevelsOccluded levels in LDS, the rest in the renderer's HBM array.
+// Grid, claim and stack: query_frame.hpp.  One ray per lane; stack entries ref, kRqLdsLevelsOccluded levels in LDS.
 //
 // The list: a ray's segment in global memory IS its sorted list.  The lane keeps base, cap, stored, total and, once stored == cap, the
 // key of the last stored record in registers, so a candidate that is not before the tail of a full list touches no memory.  Any other
@@ -27,15 +24,11 @@
 #include "device_scene.hpp"
 #include "device_access.hpp"
 #include "list_hits.hpp"
+#include "query_frame.hpp"
 
 namespace drt {
 
 namespace {
-
-// rank of this lane among the lanes set in `mask` (v_mbcnt): the claim hands rays to idle lanes in lane order
-DRT_DEV int lane_rank(uint64_t mask) {
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
 
 // the order of the list: ascending t, equal t by ascending prim
 DRT_DEV bool comes_before(float t, int prim, float other_t, int other_prim) {
@@ -45,11 +38,11 @@ DRT_DEV bool comes_before(float t, int prim, float other_t, int other_prim) {
 __global__ __launch_bounds__(kRqThreads, kRqWavesPerSimd) void list_hits_kernel(const SceneView sc, const ListHitsArgs a) {
     constexpr int K = kRqLdsLevelsOccluded;
     __shared__ uint32_t s_ref[K][kRqThreads];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const uint32_t gthread = blockIdx.x * kRqThreads + tid, gthreads = gridDim.x * kRqThreads;
-    uint32_t shard = (gthread >> 6) % kRqShards;            // home shard of this wave; on to the next one when it is empty
+    const int tid = threadIdx.x;
+    const uint32_t gthread = blockIdx.x * kRqThreads + tid;
+    const StackLane st = {tid, gthread, gridDim.x * kRqThreads, a.frame.stack_levels, a.frame.stack_hbm};
+    uint32_t shard = home_shard(gthread);
     int shards_empty = 0;
-    const uint32_t levels = a.stack_levels;                  // = tree depth: the stack never holds more entries
     float4 *const hits = reinterpret_cast<float4 *>(a.hits);
 
     int rid = -1;                                            // this lane's ray, -1 = idle
@@ -64,30 +57,10 @@ __global__ __launch_bounds__(kRqThreads, kRqWavesPerSimd) void list_hits_kernel(
     for (;;) {
         // ---- refill: claim rays for the idle lanes (wave-uniform) ----
         const uint64_t idle = __ballot(rid < 0);
-        const uint32_t n_idle = (uint32_t)__popcll(idle);
-        if (shards_empty < kRqShards && (n_idle >= a.refill_min || n_idle == 64u)) {
-            const int my_rank = lane_rank(idle);
+        if (claim_due(shards_empty, idle, a.frame)) {
             const bool was_idle = rid < 0;
-            uint32_t filled = 0;
-            while (filled < n_idle && shards_empty < kRqShards) {
-                const uint32_t want = n_idle - filled;
-                const uint32_t s_begin = (uint32_t)((uint64_t)a.n * shard / kRqShards);
-                const uint32_t len = (uint32_t)((uint64_t)a.n * (shard + 1) / kRqShards) - s_begin;
-                // lane 0 claims and clips the claim to the shard; start / got go to the wave (64-bit signed arithmetic: the
-                // shard's remainder len - b is negative once other waves have emptied it)
-                int64_t start = 0, got = 0;
-                if (lane == 0) {
-                    const int64_t b = (int64_t)atomicAdd(a.heads + shard * kRqShardStride, want);
-                    const int64_t left = (int64_t)len - b;
-                    if (left > 0) { start = (int64_t)s_begin + b; got = left < (int64_t)want ? left : (int64_t)want; }
-                }
-                start = __shfl(start, 0);
-                got = __shfl(got, 0);
-                if (got <= 0) { shard = (shard + 1) % kRqShards; shards_empty++; continue; }
-                const int64_t k = (int64_t)my_rank - (int64_t)filled;
-                if (was_idle && k >= 0 && k < got && start + k < (int64_t)a.n) rid = (int)(start + k);
-                filled += (uint32_t)got;
-            }
+            const Claimed c = claim_take(shard, shards_empty, rid, idle, a.frame);
+            shard = c.shard; shards_empty = c.shards_empty; rid = c.rid;
             if (was_idle && rid >= 0) {
                 // a new ray: two 16-byte loads (drt_ray = org, tmin, dir, tmax) and the two offsets that bound its segment
                 const float4 *r = reinterpret_cast<const float4 *>(a.rays) + 2 * (size_t)(uint32_t)rid;
@@ -108,12 +81,11 @@ __global__ __launch_bounds__(kRqThreads, kRqWavesPerSimd) void list_hits_kernel(
                 }
             }
         }
-        if (shards_empty >= kRqShards && __ballot(rid >= 0) == 0) break;
+        if (claim_drained(shards_empty, rid)) break;
 
         // ---- one traversal step per busy lane ----
         if (rid >= 0 && sp > 0) {
-            --sp;
-            const uint32_t ref = sp < (uint32_t)K ? s_ref[sp][tid] : a.stack_hbm[(size_t)(sp - K) * gthreads + gthread];
+            const uint32_t ref = stack_pop(s_ref, st, sp);
             if (ref & kLeafBit) {
                 const LeafRange leaf = sc.leaves[ref & ~kLeafBit];
                 for (int i = leaf.start; i < leaf.start + leaf.count; i++) {
@@ -146,19 +118,7 @@ __global__ __launch_bounds__(kRqThreads, kRqWavesPerSimd) void list_hits_kernel(
                 const float d1 = slab_intersect(c.min1, c.max1, ray);
                 const float d2 = slab_intersect(c.min2, c.max2, ray);
                 const bool push1 = d1 >= 0 && !(d1 > tmax), push2 = d2 >= 0 && !(d2 > tmax);
-                const bool far1 = d1 > d2;                                                            // farther child first
-                const uint32_t ra = far1 ? c.ref1 : c.ref2, rb = far1 ? c.ref2 : c.ref1;
-                const bool pa = far1 ? push1 : push2, pb = far1 ? push2 : push1;
-#pragma unroll
-                for (int k = 0; k < 2; k++) {
-                    const bool p = k == 0 ? pa : pb;
-                    if (p && sp < levels) {
-                        const uint32_t r = k == 0 ? ra : rb;
-                        if (sp < (uint32_t)K) s_ref[sp][tid] = r;
-                        else a.stack_hbm[(size_t)(sp - K) * gthreads + gthread] = r;
-                        ++sp;
-                    }
-                }
+                push_far_first(s_ref, st, sp, c.ref1, d1, push1, c.ref2, d2, push2);            // farther child first
             }
         }
 
@@ -175,9 +135,8 @@ __global__ __launch_bounds__(kRqThreads, kRqWavesPerSimd) void list_hits_kernel(
 }  // namespace
 
 hipError_t launch_list_hits(const SceneView &sc, const ListHitsArgs &args, int num_cus, hipStream_t stream) {
-    if (args.n == 0) return hipSuccess;
-    const uint32_t want = (args.n + kRqThreads - 1) / kRqThreads;
-    const uint32_t blocks = std::min<uint32_t>(want, (uint32_t)ray_query_max_blocks(num_cus));
+    if (args.frame.n == 0) return hipSuccess;
+    const uint32_t blocks = query_blocks(args.frame.n, num_cus);
     hipLaunchKernelGGL(list_hits_kernel, dim3(blocks), dim3(kRqThreads), 0, stream, sc, args);
     return hipGetLastError();
 }

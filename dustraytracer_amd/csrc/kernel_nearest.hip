@@ -8,11 +8,7 @@
 //   traversal  best = max_dist^2; a popped entry is dropped unless box2 < best; a leaf's triangles in order, strict <; an
 //              interior node pushes each child with box2 < best, the farther one (b1 > b2 -> child 1) first
 //
-// Shape: kernel_ray_query.hip's.  Persistent grid (8 workgroups of 256 threads per CU = 8 waves per SIMD), one point per lane,
-// every trip of a wave's loop pops one node per lane, and when at least `refill_min` lanes are idle the wave claims that many
-// points with ONE atomic on one of kRqShards sharded heads (ballot / mbcnt hand the claim out).  Traversal stack: entry
-// {ref, box2} at [level][thread] -- the bottom kRqLdsLevelsClosest levels in LDS (one bank per lane), the rest in the renderer's
-// HBM array with the same coalesced layout.  A result depends only on its point and the scene.
+// Grid, claim and stack: query_frame.hpp.  One point per lane; stack entries {ref, box2}, kRqLdsLevelsClosest levels in LDS.
 //
 // The seven cases are not seven blocks: all of them share the dot products, four of them are one quotient each, so the case chain
 // selects the quotient's operands and then (u, v) -- one division per triangle, no divergence inside the test.
@@ -22,15 +18,11 @@
 #include "device_scene.hpp"
 #include "device_access.hpp"
 #include "nearest.hpp"
+#include "query_frame.hpp"
 
 namespace drt {
 
 namespace {
-
-// rank of this lane among the lanes set in `mask` (v_mbcnt): the claim hands points to idle lanes in lane order
-DRT_DEV int lane_rank(uint64_t mask) {
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
 
 // drt.h "box distance": a NaN coordinate of p drops out of both max (v_max_f32 in IEEE mode), so its axis contributes 0
 DRT_DEV float box_dist2(f3 bmin, f3 bmax, f3 p) {
@@ -79,11 +71,11 @@ __global__ __launch_bounds__(kRqThreads, kRqWavesPerSimd) void nearest_kernel(co
     constexpr int K = kRqLdsLevelsClosest;
     __shared__ uint32_t s_ref[K][kRqThreads];
     __shared__ float s_box2[K][kRqThreads];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const uint32_t gthread = blockIdx.x * kRqThreads + tid, gthreads = gridDim.x * kRqThreads;
-    uint32_t shard = (gthread >> 6) % kRqShards;            // home shard of this wave; on to the next one when it is empty
+    const int tid = threadIdx.x;
+    const uint32_t gthread = blockIdx.x * kRqThreads + tid;
+    const StackLane st = {tid, gthread, gridDim.x * kRqThreads, a.frame.stack_levels, a.frame.stack_hbm};
+    uint32_t shard = home_shard(gthread);
     int shards_empty = 0;
-    const uint32_t levels = a.stack_levels;                  // = tree depth: the stack never holds more entries
 
     int rid = -1;                                            // this lane's point, -1 = idle
     f3 p = mk3(0.f, 0.f, 0.f);
@@ -94,30 +86,10 @@ __global__ __launch_bounds__(kRqThreads, kRqWavesPerSimd) void nearest_kernel(co
     for (;;) {
         // ---- refill: claim points for the idle lanes (wave-uniform) ----
         const uint64_t idle = __ballot(rid < 0);
-        const uint32_t n_idle = (uint32_t)__popcll(idle);
-        if (shards_empty < kRqShards && (n_idle >= a.refill_min || n_idle == 64u)) {
-            const int my_rank = lane_rank(idle);
+        if (claim_due(shards_empty, idle, a.frame)) {
             const bool was_idle = rid < 0;
-            uint32_t filled = 0;
-            while (filled < n_idle && shards_empty < kRqShards) {
-                const uint32_t want = n_idle - filled;
-                const uint32_t s_begin = (uint32_t)((uint64_t)a.n * shard / kRqShards);
-                const uint32_t len = (uint32_t)((uint64_t)a.n * (shard + 1) / kRqShards) - s_begin;
-                // lane 0 claims and clips the claim to the shard; start / got go to the wave (64-bit signed arithmetic: the
-                // shard's remainder len - b is negative once other waves have emptied it)
-                int64_t start = 0, got = 0;
-                if (lane == 0) {
-                    const int64_t b = (int64_t)atomicAdd(a.heads + shard * kRqShardStride, want);
-                    const int64_t left = (int64_t)len - b;
-                    if (left > 0) { start = (int64_t)s_begin + b; got = left < (int64_t)want ? left : (int64_t)want; }
-                }
-                start = __shfl(start, 0);
-                got = __shfl(got, 0);
-                if (got <= 0) { shard = (shard + 1) % kRqShards; shards_empty++; continue; }
-                const int64_t k = (int64_t)my_rank - (int64_t)filled;
-                if (was_idle && k >= 0 && k < got && start + k < (int64_t)a.n) rid = (int)(start + k);
-                filled += (uint32_t)got;
-            }
+            const Claimed c = claim_take(shard, shards_empty, rid, idle, a.frame);
+            shard = c.shard; shards_empty = c.shards_empty; rid = c.rid;
             if (was_idle && rid >= 0) {
                 // a new point: one 16-byte load (drt_point = p, max_dist)
                 const float4 q = reinterpret_cast<const float4 *>(a.points)[(uint32_t)rid];
@@ -128,19 +100,12 @@ __global__ __launch_bounds__(kRqThreads, kRqWavesPerSimd) void nearest_kernel(co
                 }
             }
         }
-        if (shards_empty >= kRqShards && __ballot(rid >= 0) == 0) break;
+        if (claim_drained(shards_empty, rid)) break;
 
         // ---- one traversal step per busy lane ----
         if (rid >= 0 && sp > 0) {
-            --sp;
-            uint32_t ref;
             float box2;
-            if (sp < (uint32_t)K) {
-                ref = s_ref[sp][tid]; box2 = s_box2[sp][tid];
-            } else {
-                const uint2 e = reinterpret_cast<const uint2 *>(a.stack_hbm)[(size_t)(sp - K) * gthreads + gthread];
-                ref = e.x; box2 = __uint_as_float(e.y);
-            }
+            const uint32_t ref = stack_pop(s_ref, s_box2, st, sp, box2);
             if (box2 < best) {
                 if (ref & kLeafBit) {
                     const LeafRange leaf = sc.leaves[ref & ~kLeafBit];
@@ -155,24 +120,7 @@ __global__ __launch_bounds__(kRqThreads, kRqWavesPerSimd) void nearest_kernel(co
                     const float b1 = box_dist2(c.min1, c.max1, p);
                     const float b2 = box_dist2(c.min2, c.max2, p);
                     const bool push1 = b1 < best, push2 = b2 < best;
-                    const bool far1 = b1 > b2;                                                        // farther child first
-                    const uint32_t ra = far1 ? c.ref1 : c.ref2, rb = far1 ? c.ref2 : c.ref1;
-                    const float da = far1 ? b1 : b2, db = far1 ? b2 : b1;
-                    const bool pa = far1 ? push1 : push2, pb = far1 ? push2 : push1;
-#pragma unroll
-                    for (int k = 0; k < 2; k++) {
-                        const bool push = k == 0 ? pa : pb;
-                        if (push && sp < levels) {
-                            const uint32_t r = k == 0 ? ra : rb;
-                            const float d = k == 0 ? da : db;
-                            if (sp < (uint32_t)K) {
-                                s_ref[sp][tid] = r; s_box2[sp][tid] = d;
-                            } else {
-                                reinterpret_cast<uint2 *>(a.stack_hbm)[(size_t)(sp - K) * gthreads + gthread] = make_uint2(r, __float_as_uint(d));
-                            }
-                            ++sp;
-                        }
-                    }
+                    push_far_first(s_ref, s_box2, st, sp, c.ref1, b1, push1, c.ref2, b2, push2);        // farther child first
                 }
             }
         }
@@ -198,9 +146,8 @@ __global__ __launch_bounds__(kRqThreads, kRqWavesPerSimd) void nearest_kernel(co
 }  // namespace
 
 hipError_t launch_nearest(const SceneView &sc, const NearestArgs &args, int num_cus, hipStream_t stream) {
-    if (args.n == 0) return hipSuccess;
-    const uint32_t want = (args.n + kRqThreads - 1) / kRqThreads;
-    const uint32_t blocks = std::min<uint32_t>(want, (uint32_t)ray_query_max_blocks(num_cus));
+    if (args.frame.n == 0) return hipSuccess;
+    const uint32_t blocks = query_blocks(args.frame.n, num_cus);
     hipLaunchKernelGGL(nearest_kernel, dim3(blocks), dim3(kRqThreads), 0, stream, sc, args);
     return hipGetLastError();
 }

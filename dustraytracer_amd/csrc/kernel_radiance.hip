@@ -8,12 +8,10 @@
 // dielectric lobes); the tone curve with the ray's exposure and gamma at the end.  The leaf arithmetic is the renderer's
 // (device_math.hpp / device_access.hpp), so a radiance query fed with camera_rays' output is the renderer's sample bit for bit.
 //
-// Shape: the ray query's (kernel_ray_query.hip).  A persistent grid, one path per lane; every trip of a wave's loop is one
-// traversal step of each busy lane (closest-hit or shadow, per lane), and a lane whose traversal is over shades in the same
-// trip and starts its next traversal (shadow ray, next bounce) or writes its result and goes idle.  Paths end at different
-// bounces: once `refill_min` lanes are idle the wave claims that many new paths with one atomic on one of kRqShards sharded
-// heads (ballot / mbcnt hand them out).  Stack entries [level][thread] {ref, entry distance}: the bottom kRqLdsLevelsClosest
-// levels in LDS, the rest in the renderer's HBM array (the closest-hit query's layout); 32-bit node references.
+// Grid, claim and stack: query_frame.hpp.  One path per lane; every trip of a wave's loop is one traversal step of each busy
+// lane (closest-hit or shadow, per lane), and a lane whose traversal is over shades in the same trip and starts its next
+// traversal (shadow ray, next bounce) or writes its result and goes idle.  Stack entries {ref, entry distance},
+// kRqLdsLevelsClosest levels in LDS (the closest-hit query's layout).
 // Builds: SUN (the shadow ray and the continuation ray it holds back: 6 more registers), ALPHA (AnyHit reads the texture),
 // EXT (the material model); the lean build reads neither.
 #include <hip/hip_runtime.h>
@@ -21,16 +19,12 @@
 #include "device_math.hpp"
 #include "device_scene.hpp"
 #include "device_access.hpp"
-#include "ray_query.hpp"
+#include "query_frame.hpp"
 #include "radiance.hpp"
 
 namespace drt {
 
 namespace {
-
-DRT_DEV int lane_rank(uint64_t mask) {
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
 
 // waves per SIMD each build is compiled for (VGPR budget: 8 -> 64, 7 -> 72): the full build spills at 64
 template <bool SUN, bool ALPHA, bool EXT>
@@ -42,11 +36,11 @@ __global__ __launch_bounds__(kRqThreads, (radiance_waves<SUN, ALPHA, EXT>())) vo
     constexpr int K = kRqLdsLevelsClosest;
     __shared__ uint32_t s_ref[K][kRqThreads];
     __shared__ float s_dist[K][kRqThreads];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const uint32_t gthread = blockIdx.x * kRqThreads + tid, gthreads = gridDim.x * kRqThreads;
-    uint32_t shard = (gthread >> 6) % kRqShards;
+    const int tid = threadIdx.x;
+    const uint32_t gthread = blockIdx.x * kRqThreads + tid;
+    const StackLane st = {tid, gthread, gridDim.x * kRqThreads, a.frame.stack_levels, a.frame.stack_hbm};
+    uint32_t shard = home_shard(gthread);
     int shards_empty = 0;
-    const uint32_t levels = a.stack_levels;
 
     int rid = -1;                                            // this lane's path, -1 = idle
     Ray ray;
@@ -71,28 +65,10 @@ __global__ __launch_bounds__(kRqThreads, (radiance_waves<SUN, ALPHA, EXT>())) vo
     for (;;) {
         // ---- refill: claim paths for the idle lanes (wave-uniform) ----
         const uint64_t idle = __ballot(rid < 0);
-        const uint32_t n_idle = (uint32_t)__popcll(idle);
-        if (shards_empty < kRqShards && (n_idle >= a.refill_min || n_idle == 64u)) {
-            const int my_rank = lane_rank(idle);
+        if (claim_due(shards_empty, idle, a.frame)) {
             const bool was_idle = rid < 0;
-            uint32_t filled = 0;
-            while (filled < n_idle && shards_empty < kRqShards) {
-                const uint32_t want = n_idle - filled;
-                const uint32_t s_begin = (uint32_t)((uint64_t)a.n * shard / kRqShards);
-                const uint32_t len = (uint32_t)((uint64_t)a.n * (shard + 1) / kRqShards) - s_begin;
-                int64_t start = 0, got = 0;
-                if (lane == 0) {
-                    const int64_t b = (int64_t)atomicAdd(a.heads + shard * kRqShardStride, want);
-                    const int64_t left = (int64_t)len - b;
-                    if (left > 0) { start = (int64_t)s_begin + b; got = left < (int64_t)want ? left : (int64_t)want; }
-                }
-                start = __shfl(start, 0);
-                got = __shfl(got, 0);
-                if (got <= 0) { shard = (shard + 1) % kRqShards; shards_empty++; continue; }
-                const int64_t k = (int64_t)my_rank - (int64_t)filled;
-                if (was_idle && k >= 0 && k < got && start + k < (int64_t)a.n) rid = (int)(start + k);
-                filled += (uint32_t)got;
-            }
+            const Claimed c = claim_take(shard, shards_empty, rid, idle, a.frame);
+            shard = c.shard; shards_empty = c.shards_empty; rid = c.rid;
             if (was_idle && rid >= 0) {
                 // a new path: drt_path_ray = org, seed, dir, exposure (two 16-byte loads); RayGen.cuh:80-88
                 const float4 *r = reinterpret_cast<const float4 *>(a.rays) + 2 * (size_t)(uint32_t)rid;
@@ -105,20 +81,12 @@ __global__ __launch_bounds__(kRqThreads, (radiance_waves<SUN, ALPHA, EXT>())) vo
                 if (!done) start_closest();
             }
         }
-        if (shards_empty >= kRqShards && __ballot(rid >= 0) == 0) break;
+        if (claim_drained(shards_empty, rid)) break;
 
         // ---- one traversal step per busy lane: closest hit (BVHTraversal.cuh:14-73) or, SUN, the shadow test (:76-134) ----
         if (rid >= 0 && !done && sp > 0 && !occluded) {
-            --sp;
-            uint32_t ref;
             float dist;
-            if (sp < (uint32_t)K) {
-                ref = s_ref[sp][tid];
-                dist = s_dist[sp][tid];
-            } else {
-                const uint2 e = reinterpret_cast<const uint2 *>(a.stack_hbm)[(size_t)(sp - K) * gthreads + gthread];
-                ref = e.x; dist = __uint_as_float(e.y);
-            }
+            const uint32_t ref = stack_pop(s_ref, s_dist, st, sp, dist);
             bool visit = true;
             if (!(SUN && shadow)) {
                 if (!(-1.0f < dist && dist < FLT_MAX)) visit = false;                      // :38 interval (-1, FLT_MAX)
@@ -144,25 +112,7 @@ __global__ __launch_bounds__(kRqThreads, (radiance_waves<SUN, ALPHA, EXT>())) vo
                     const float d2 = slab_intersect(c.min2, c.max2, ray);
                     const bool sh = SUN && shadow;
                     const bool push1 = d1 >= 0 && (sh || d1 < best_t), push2 = d2 >= 0 && (sh || d2 < best_t);   // :63-70 / :122-129
-                    const bool far1 = d1 > d2;                                                                 // farther child first
-                    const uint32_t ra = far1 ? c.ref1 : c.ref2, rb = far1 ? c.ref2 : c.ref1;
-                    const float da = far1 ? d1 : d2, db = far1 ? d2 : d1;
-                    const bool pa = far1 ? push1 : push2, pb = far1 ? push2 : push1;
-#pragma unroll
-                    for (int k = 0; k < 2; k++) {
-                        const bool p = k == 0 ? pa : pb;
-                        if (p && sp < levels) {
-                            const uint32_t r = k == 0 ? ra : rb;
-                            const float d = k == 0 ? da : db;
-                            if (sp < (uint32_t)K) {
-                                s_ref[sp][tid] = r;
-                                s_dist[sp][tid] = d;
-                            } else {
-                                reinterpret_cast<uint2 *>(a.stack_hbm)[(size_t)(sp - K) * gthreads + gthread] = make_uint2(r, __float_as_uint(d));
-                            }
-                            ++sp;
-                        }
-                    }
+                    push_far_first(s_ref, s_dist, st, sp, c.ref1, d1, push1, c.ref2, d2, push2);        // farther child first
                 }
             }
         }
@@ -288,9 +238,7 @@ __global__ __launch_bounds__(256) void camera_rays_kernel(const CameraRaysArgs a
 
 template <bool SUN, bool ALPHA, bool EXT>
 hipError_t launch_radiance_t(const SceneView &sc, const FrameParams &fp, const RadianceArgs &a, int num_cus, hipStream_t stream) {
-    const uint32_t want = (a.n + kRqThreads - 1) / kRqThreads;
-    // one 256-thread workgroup per SIMD and resident wave: at most the ray query's grid (8 per CU), whose HBM stack this shares
-    const uint32_t blocks = std::min<uint32_t>(want, (uint32_t)std::max(1, num_cus) * (uint32_t)radiance_waves<SUN, ALPHA, EXT>());
+    const uint32_t blocks = query_blocks(a.frame.n, num_cus, radiance_waves<SUN, ALPHA, EXT>());
     hipLaunchKernelGGL((radiance_kernel<SUN, ALPHA, EXT>), dim3(blocks), dim3(kRqThreads), 0, stream, sc, fp, a);
     return hipGetLastError();
 }
@@ -305,7 +253,7 @@ hipError_t launch_camera_rays(const CameraRaysArgs &a, hipStream_t stream) {
 }
 
 hipError_t launch_radiance(const SceneView &sc, const FrameParams &fp, bool alpha, const RadianceArgs &a, int num_cus, hipStream_t stream) {
-    if (a.n == 0) return hipSuccess;
+    if (a.frame.n == 0) return hipSuccess;
     const bool sun = fp.enable_sunlight != 0, ext = fp.ext_emissive || fp.ext_specular || fp.ext_transmission;
     const int v = (sun ? 4 : 0) | (alpha ? 2 : 0) | (ext ? 1 : 0);
     switch (v) {

@@ -9,39 +9,28 @@
 //             a triangle counts iff t > tmin && t < tmax && AnyHit (:107-115)
 // The leaf arithmetic is the renderer's: make_ray, slab_intersect, tri_intersect_flat, any_hit, load_children, load_tri.
 //
-// Shape: persistent grid (8 workgroups of 256 threads per CU = 8 waves per SIMD), one ray per lane, "while-while with
-// dynamic fetch" (Aila & Laine 2009): every trip of a wave's loop is one traversal step (one node popped per lane), and when
-// at least `refill_min` lanes are idle the wave claims that many rays with ONE atomic on one of kRqShards sharded heads
-// (ballot / mbcnt hand the claim out).  refill_min = 64 is the plain form (a wave takes 64 new rays only once all are done).
-// Traversal stack: entry [level][thread] -- the bottom kRqLdsLevels levels in LDS (one bank per lane), the rest in a
-// renderer-owned HBM array with the same coalesced [level][thread] layout.  32-bit node references throughout.
-// A result depends only on its ray and the scene: traversal order is per lane, the claim only decides who runs it.
+// Grid, claim and stack: query_frame.hpp.  One ray per lane; stack entries {ref, entry distance} (closest) or ref (occluded).
 #include <hip/hip_runtime.h>
 
 #include "device_math.hpp"
 #include "device_scene.hpp"
 #include "device_access.hpp"
-#include "ray_query.hpp"
+#include "query_frame.hpp"
 
 namespace drt {
 
 namespace {
-
-// rank of this lane among the lanes set in `mask` (v_mbcnt): the claim hands rays to idle lanes in lane order
-DRT_DEV int lane_rank(uint64_t mask) {
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
 
 template <bool OCC>
 __global__ __launch_bounds__(kRqThreads, kRqWavesPerSimd) void ray_query_kernel(const SceneView sc, const RayQueryArgs a) {
     constexpr int K = OCC ? kRqLdsLevelsOccluded : kRqLdsLevelsClosest;
     __shared__ uint32_t s_ref[K][kRqThreads];
     __shared__ float s_dist[OCC ? 1 : K][kRqThreads];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const uint32_t gthread = blockIdx.x * kRqThreads + tid, gthreads = gridDim.x * kRqThreads;
-    uint32_t shard = (gthread >> 6) % kRqShards;            // home shard of this wave; on to the next one when it is empty
+    const int tid = threadIdx.x;
+    const uint32_t gthread = blockIdx.x * kRqThreads + tid;
+    const StackLane st = {tid, gthread, gridDim.x * kRqThreads, a.frame.stack_levels, a.frame.stack_hbm};
+    uint32_t shard = home_shard(gthread);
     int shards_empty = 0;
-    const uint32_t levels = a.stack_levels;                  // = tree depth: the stack never holds more entries
 
     int rid = -1;                                            // this lane's ray, -1 = idle
     Ray ray;
@@ -54,30 +43,10 @@ __global__ __launch_bounds__(kRqThreads, kRqWavesPerSimd) void ray_query_kernel(
     for (;;) {
         // ---- refill: claim rays for the idle lanes (wave-uniform) ----
         const uint64_t idle = __ballot(rid < 0);
-        const uint32_t n_idle = (uint32_t)__popcll(idle);
-        if (shards_empty < kRqShards && (n_idle >= a.refill_min || n_idle == 64u)) {
-            const int my_rank = lane_rank(idle);
+        if (claim_due(shards_empty, idle, a.frame)) {
             const bool was_idle = rid < 0;
-            uint32_t filled = 0;
-            while (filled < n_idle && shards_empty < kRqShards) {
-                const uint32_t want = n_idle - filled;
-                const uint32_t s_begin = (uint32_t)((uint64_t)a.n * shard / kRqShards);
-                const uint32_t len = (uint32_t)((uint64_t)a.n * (shard + 1) / kRqShards) - s_begin;
-                // lane 0 claims and clips the claim to the shard; start / got go to the wave (64-bit signed arithmetic: the
-                // shard's remainder len - b is negative once other waves have emptied it)
-                int64_t start = 0, got = 0;
-                if (lane == 0) {
-                    const int64_t b = (int64_t)atomicAdd(a.heads + shard * kRqShardStride, want);
-                    const int64_t left = (int64_t)len - b;
-                    if (left > 0) { start = (int64_t)s_begin + b; got = left < (int64_t)want ? left : (int64_t)want; }
-                }
-                start = __shfl(start, 0);
-                got = __shfl(got, 0);
-                if (got <= 0) { shard = (shard + 1) % kRqShards; shards_empty++; continue; }
-                const int64_t k = (int64_t)my_rank - (int64_t)filled;
-                if (was_idle && k >= 0 && k < got && start + k < (int64_t)a.n) rid = (int)(start + k);
-                filled += (uint32_t)got;
-            }
+            const Claimed c = claim_take(shard, shards_empty, rid, idle, a.frame);
+            shard = c.shard; shards_empty = c.shards_empty; rid = c.rid;
             if (was_idle && rid >= 0) {
                 // a new ray: two 16-byte loads (drt_ray = org, tmin, dir, tmax)
                 const float4 *r = reinterpret_cast<const float4 *>(a.rays) + 2 * (size_t)(uint32_t)rid;
@@ -95,22 +64,14 @@ __global__ __launch_bounds__(kRqThreads, kRqWavesPerSimd) void ray_query_kernel(
                 }
             }
         }
-        if (shards_empty >= kRqShards && __ballot(rid >= 0) == 0) break;
+        if (claim_drained(shards_empty, rid)) break;
 
         // ---- one traversal step per busy lane ----
         if (rid >= 0 && sp > 0 && !occluded) {
-            --sp;
             uint32_t ref;
             float dist = 0.f;
-            if (sp < (uint32_t)K) {
-                ref = s_ref[sp][tid];
-                if (!OCC) dist = s_dist[sp][tid];
-            } else if (OCC) {
-                ref = a.stack_hbm[(size_t)(sp - K) * gthreads + gthread];
-            } else {
-                const uint2 e = reinterpret_cast<const uint2 *>(a.stack_hbm)[(size_t)(sp - K) * gthreads + gthread];
-                ref = e.x; dist = __uint_as_float(e.y);
-            }
+            if constexpr (OCC) ref = stack_pop(s_ref, st, sp);
+            else ref = stack_pop(s_ref, s_dist, st, sp, dist);
             bool visit = true;
             if (!OCC) {
                 if (!(-1.0f < dist && dist < tmax)) visit = false;                         // :38 interval (-1, tmax)
@@ -137,27 +98,8 @@ __global__ __launch_bounds__(kRqThreads, kRqWavesPerSimd) void ray_query_kernel(
                     bool push1, push2;
                     if (OCC) { push1 = d1 >= 0 && !(d1 > tmax); push2 = d2 >= 0 && !(d2 > tmax); }      // :122-129 with tmax
                     else { push1 = d1 >= 0 && d1 < best_t; push2 = d2 >= 0 && d2 < best_t; }             // :63-70
-                    const bool far1 = d1 > d2;                                                            // farther child first
-                    const uint32_t ra = far1 ? c.ref1 : c.ref2, rb = far1 ? c.ref2 : c.ref1;
-                    const float da = far1 ? d1 : d2, db = far1 ? d2 : d1;
-                    const bool pa = far1 ? push1 : push2, pb = far1 ? push2 : push1;
-#pragma unroll
-                    for (int k = 0; k < 2; k++) {
-                        const bool p = k == 0 ? pa : pb;
-                        if (p && sp < levels) {
-                            const uint32_t r = k == 0 ? ra : rb;
-                            const float d = k == 0 ? da : db;
-                            if (sp < (uint32_t)K) {
-                                s_ref[sp][tid] = r;
-                                if (!OCC) s_dist[sp][tid] = d;
-                            } else if (OCC) {
-                                a.stack_hbm[(size_t)(sp - K) * gthreads + gthread] = r;
-                            } else {
-                                reinterpret_cast<uint2 *>(a.stack_hbm)[(size_t)(sp - K) * gthreads + gthread] = make_uint2(r, __float_as_uint(d));
-                            }
-                            ++sp;
-                        }
-                    }
+                    if constexpr (OCC) push_far_first(s_ref, st, sp, c.ref1, d1, push1, c.ref2, d2, push2);
+                    else push_far_first(s_ref, s_dist, st, sp, c.ref1, d1, push1, c.ref2, d2, push2);
                 }
             }
         }
@@ -180,9 +122,8 @@ __global__ __launch_bounds__(kRqThreads, kRqWavesPerSimd) void ray_query_kernel(
 
 hipError_t launch_ray_query(const SceneView &sc, bool occluded_query, const RayQueryArgs &args, int num_cus, hipStream_t stream,
                             const char **kernel_name) {
-    if (args.n == 0) return hipSuccess;
-    const uint32_t want = (args.n + kRqThreads - 1) / kRqThreads;
-    const uint32_t blocks = std::min<uint32_t>(want, (uint32_t)ray_query_max_blocks(num_cus));
+    if (args.frame.n == 0) return hipSuccess;
+    const uint32_t blocks = query_blocks(args.frame.n, num_cus);
     if (occluded_query) {
         if (kernel_name) *kernel_name = "ray_query<occluded>";
         hipLaunchKernelGGL(ray_query_kernel<true>, dim3(blocks), dim3(kRqThreads), 0, stream, sc, args);

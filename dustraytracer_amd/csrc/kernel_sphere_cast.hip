@@ -10,11 +10,7 @@
 //   traversal  best = tmax; a popped entry is dropped unless enter <= best; a leaf's triangles in order, a candidate wins on
 //              t < best or t == best with a smaller triangle index; an interior node pushes the farther child first
 //
-// Shape: kernel_nearest.hip's.  Persistent grid, one cast per lane, every trip of a wave's loop pops one node per lane, and when at
-// least `refill_min` lanes are idle the wave claims that many casts with ONE atomic on one of kRqShards sharded heads (ballot /
-// mbcnt hand the claim out).  Traversal stack: entry {ref, enter} at [level][thread] -- the bottom kRqLdsLevelsClosest levels in
-// LDS (one bank per lane), the rest in the renderer's HBM array with the same coalesced layout.  A result depends only on its
-// cast and the scene.
+// Grid, claim and stack: query_frame.hpp.  One cast per lane; stack entries {ref, enter}, kRqLdsLevelsClosest levels in LDS.
 //
 // The triangle test fits the ray queries' 64 VGPRs (8 waves per SIMD), so the grid is theirs.  The square root and the quotient
 // of a shape are computed only by the lanes whose cheap conditions hold (approaching, disc >= 0).
@@ -24,15 +20,11 @@
 #include "device_scene.hpp"
 #include "device_access.hpp"
 #include "sphere_cast.hpp"
+#include "query_frame.hpp"
 
 namespace drt {
 
 namespace {
-
-// rank of this lane among the lanes set in `mask` (v_mbcnt): the claim hands casts to idle lanes in lane order
-DRT_DEV int lane_rank(uint64_t mask) {
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
 
 // drt.h "traversal": the box inflated by r on every side against the ray (o, inv_dir); fminf / fmaxf drop a NaN operand (0 * inf)
 DRT_DEV bool inflated_slab(f3 bmin, f3 bmax, float r, f3 o, f3 inv_dir, float tmin, float best, float &enter) {
@@ -157,11 +149,11 @@ __global__ __launch_bounds__(kRqThreads, kRqWavesPerSimd) void sphere_cast_kerne
     constexpr int K = kRqLdsLevelsClosest;
     __shared__ uint32_t s_ref[K][kRqThreads];
     __shared__ float s_enter[K][kRqThreads];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const uint32_t gthread = blockIdx.x * kRqThreads + tid, gthreads = gridDim.x * kRqThreads;
-    uint32_t shard = (gthread >> 6) % kRqShards;            // home shard of this wave; on to the next one when it is empty
+    const int tid = threadIdx.x;
+    const uint32_t gthread = blockIdx.x * kRqThreads + tid;
+    const StackLane st = {tid, gthread, gridDim.x * kRqThreads, a.frame.stack_levels, a.frame.stack_hbm};
+    uint32_t shard = home_shard(gthread);
     int shards_empty = 0;
-    const uint32_t levels = a.stack_levels;                  // = tree depth: the stack never holds more entries
 
     int rid = -1;                                            // this lane's cast, -1 = idle
     f3 o = mk3(0.f, 0.f, 0.f), d = o, inv_dir = o, s = o;
@@ -173,30 +165,10 @@ __global__ __launch_bounds__(kRqThreads, kRqWavesPerSimd) void sphere_cast_kerne
     for (;;) {
         // ---- refill: claim casts for the idle lanes (wave-uniform) ----
         const uint64_t idle = __ballot(rid < 0);
-        const uint32_t n_idle = (uint32_t)__popcll(idle);
-        if (shards_empty < kRqShards && (n_idle >= a.refill_min || n_idle == 64u)) {
-            const int my_rank = lane_rank(idle);
+        if (claim_due(shards_empty, idle, a.frame)) {
             const bool was_idle = rid < 0;
-            uint32_t filled = 0;
-            while (filled < n_idle && shards_empty < kRqShards) {
-                const uint32_t want = n_idle - filled;
-                const uint32_t s_begin = (uint32_t)((uint64_t)a.n * shard / kRqShards);
-                const uint32_t len = (uint32_t)((uint64_t)a.n * (shard + 1) / kRqShards) - s_begin;
-                // lane 0 claims and clips the claim to the shard; start / got go to the wave (64-bit signed arithmetic: the
-                // shard's remainder len - b is negative once other waves have emptied it)
-                int64_t start = 0, got = 0;
-                if (lane == 0) {
-                    const int64_t b = (int64_t)atomicAdd(a.heads + shard * kRqShardStride, want);
-                    const int64_t left = (int64_t)len - b;
-                    if (left > 0) { start = (int64_t)s_begin + b; got = left < (int64_t)want ? left : (int64_t)want; }
-                }
-                start = __shfl(start, 0);
-                got = __shfl(got, 0);
-                if (got <= 0) { shard = (shard + 1) % kRqShards; shards_empty++; continue; }
-                const int64_t k = (int64_t)my_rank - (int64_t)filled;
-                if (was_idle && k >= 0 && k < got && start + k < (int64_t)a.n) rid = (int)(start + k);
-                filled += (uint32_t)got;
-            }
+            const Claimed c = claim_take(shard, shards_empty, rid, idle, a.frame);
+            shard = c.shard; shards_empty = c.shards_empty; rid = c.rid;
             if (was_idle && rid >= 0) {
                 // a new cast: two 16-byte loads (drt_ray = org, tmin, dir, tmax) and its radius
                 const float4 *q = reinterpret_cast<const float4 *>(a.rays) + 2 * (size_t)(uint32_t)rid;
@@ -219,19 +191,12 @@ __global__ __launch_bounds__(kRqThreads, kRqWavesPerSimd) void sphere_cast_kerne
                 }
             }
         }
-        if (shards_empty >= kRqShards && __ballot(rid >= 0) == 0) break;
+        if (claim_drained(shards_empty, rid)) break;
 
         // ---- one traversal step per busy lane ----
         if (rid >= 0 && sp > 0) {
-            --sp;
-            uint32_t ref;
             float enter;
-            if (sp < (uint32_t)K) {
-                ref = s_ref[sp][tid]; enter = s_enter[sp][tid];
-            } else {
-                const uint2 e = reinterpret_cast<const uint2 *>(a.stack_hbm)[(size_t)(sp - K) * gthreads + gthread];
-                ref = e.x; enter = __uint_as_float(e.y);
-            }
+            const uint32_t ref = stack_pop(s_ref, s_enter, st, sp, enter);
             if (enter <= best) {
                 if (ref & kLeafBit) {
                     const LeafRange leaf = sc.leaves[ref & ~kLeafBit];
@@ -248,24 +213,7 @@ __global__ __launch_bounds__(kRqThreads, kRqWavesPerSimd) void sphere_cast_kerne
                     float en1, en2;
                     const bool push1 = inflated_slab(c.min1, c.max1, r, o, inv_dir, tmin, best, en1);
                     const bool push2 = inflated_slab(c.min2, c.max2, r, o, inv_dir, tmin, best, en2);
-                    const bool far1 = en1 > en2;                                                      // farther child first
-                    const uint32_t ra = far1 ? c.ref1 : c.ref2, rb = far1 ? c.ref2 : c.ref1;
-                    const float da = far1 ? en1 : en2, db = far1 ? en2 : en1;
-                    const bool pa = far1 ? push1 : push2, pb = far1 ? push2 : push1;
-#pragma unroll
-                    for (int k = 0; k < 2; k++) {
-                        const bool push = k == 0 ? pa : pb;
-                        if (push && sp < levels) {
-                            const uint32_t rr = k == 0 ? ra : rb;
-                            const float e = k == 0 ? da : db;
-                            if (sp < (uint32_t)K) {
-                                s_ref[sp][tid] = rr; s_enter[sp][tid] = e;
-                            } else {
-                                reinterpret_cast<uint2 *>(a.stack_hbm)[(size_t)(sp - K) * gthreads + gthread] = make_uint2(rr, __float_as_uint(e));
-                            }
-                            ++sp;
-                        }
-                    }
+                    push_far_first(s_ref, s_enter, st, sp, c.ref1, en1, push1, c.ref2, en2, push2);        // farther child first
                 }
             }
         }
@@ -294,9 +242,8 @@ __global__ __launch_bounds__(kRqThreads, kRqWavesPerSimd) void sphere_cast_kerne
 }  // namespace
 
 hipError_t launch_sphere_cast(const SceneView &sc, const SphereCastArgs &args, int num_cus, hipStream_t stream) {
-    if (args.n == 0) return hipSuccess;
-    const uint32_t want = (args.n + kRqThreads - 1) / kRqThreads;
-    const uint32_t blocks = std::min<uint32_t>(want, (uint32_t)ray_query_max_blocks(num_cus));
+    if (args.frame.n == 0) return hipSuccess;
+    const uint32_t blocks = query_blocks(args.frame.n, num_cus);
     hipLaunchKernelGGL(sphere_cast_kernel, dim3(blocks), dim3(kRqThreads), 0, stream, sc, args);
     return hipGetLastError();
 }

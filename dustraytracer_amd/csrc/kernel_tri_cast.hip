@@ -14,10 +14,7 @@
 //              pair wins on t < best or t == best with a smaller triangle index; an interior node pushes the farther child first.
 //              Mode ANY ends the cast at the first pair with t < best.
 //
-// Shape: kernel_tri_distance.hip's.  Persistent grid of 256-thread workgroups, one cast per lane, every trip of a wave's loop pops one
-// node per lane, and when at least `refill_min` lanes are idle the wave claims that many casts with ONE atomic on one of kRqShards
-// sharded heads.  Traversal stack: entry {ref, enter} at [level][thread] -- the bottom kRqLdsLevelsClosest levels in LDS, the rest in
-// the renderer's HBM array with the same coalesced layout.  A result depends only on its cast and the scene.
+// Grid, claim and stack: query_frame.hpp.  One cast per lane; stack entries {ref, enter}, kRqLdsLevelsClosest levels in LDS.
 //
 // Registers: a lane keeps q0, a1, a2, g, nq, d, inv_d and the two extents -- 27 floats -- and best, prim and feature for as long as it
 // owns the cast; the contact is not kept but made again from (prim, candidate) when the cast ends.  The table of what was tried is in
@@ -28,26 +25,22 @@
 #include "device_scene.hpp"
 #include "device_access.hpp"
 #include "tri_cast.hpp"
+#include "query_frame.hpp"
 
 namespace drt {
 
 namespace {
-
-// rank of this lane among the lanes set in `mask` (v_mbcnt): the claim hands casts to idle lanes in lane order
-DRT_DEV int lane_rank(uint64_t mask) {
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
 
 template <bool ANY>
 __global__ __launch_bounds__(kRqThreads, kTriCastWavesPerSimd) void tri_cast_kernel(const SceneView sc, const TriCastArgs a) {
     constexpr int K = kRqLdsLevelsClosest;
     __shared__ uint32_t s_ref[K][kRqThreads];
     __shared__ float s_enter[K][kRqThreads];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const uint32_t gthread = blockIdx.x * kRqThreads + tid, gthreads = gridDim.x * kRqThreads;
-    uint32_t shard = (gthread >> 6) % kRqShards;            // home shard of this wave; on to the next one when it is empty
+    const int tid = threadIdx.x;
+    const uint32_t gthread = blockIdx.x * kRqThreads + tid;
+    const StackLane st = {tid, gthread, gridDim.x * kRqThreads, a.frame.stack_levels, a.frame.stack_hbm};
+    uint32_t shard = home_shard(gthread);
     int shards_empty = 0;
-    const uint32_t levels = a.stack_levels;                  // = tree depth: the stack never holds more entries
 
     int rid = -1;                                            // this lane's cast, -1 = idle
     f3 ext_lo = mk3(0.f, 0.f, 0.f), ext_hi = ext_lo;         // the query's bounds relative to q0
@@ -60,30 +53,10 @@ __global__ __launch_bounds__(kRqThreads, kTriCastWavesPerSimd) void tri_cast_ker
     for (;;) {
         // ---- refill: claim casts for the idle lanes (wave-uniform) ----
         const uint64_t idle = __ballot(rid < 0);
-        const uint32_t n_idle = (uint32_t)__popcll(idle);
-        if (shards_empty < kRqShards && (n_idle >= a.refill_min || n_idle == 64u)) {
-            const int my_rank = lane_rank(idle);
+        if (claim_due(shards_empty, idle, a.frame)) {
             const bool was_idle = rid < 0;
-            uint32_t filled = 0;
-            while (filled < n_idle && shards_empty < kRqShards) {
-                const uint32_t want = n_idle - filled;
-                const uint32_t s_begin = (uint32_t)((uint64_t)a.n * shard / kRqShards);
-                const uint32_t len = (uint32_t)((uint64_t)a.n * (shard + 1) / kRqShards) - s_begin;
-                // lane 0 claims and clips the claim to the shard; start / got go to the wave (64-bit signed arithmetic: the
-                // shard's remainder len - b is negative once other waves have emptied it)
-                int64_t start = 0, got = 0;
-                if (lane == 0) {
-                    const int64_t b = (int64_t)atomicAdd(a.heads + shard * kRqShardStride, want);
-                    const int64_t left = (int64_t)len - b;
-                    if (left > 0) { start = (int64_t)s_begin + b; got = left < (int64_t)want ? left : (int64_t)want; }
-                }
-                start = __shfl(start, 0);
-                got = __shfl(got, 0);
-                if (got <= 0) { shard = (shard + 1) % kRqShards; shards_empty++; continue; }
-                const int64_t k = (int64_t)my_rank - (int64_t)filled;
-                if (was_idle && k >= 0 && k < got && start + k < (int64_t)a.n) rid = (int)(start + k);
-                filled += (uint32_t)got;
-            }
+            const Claimed c = claim_take(shard, shards_empty, rid, idle, a.frame);
+            shard = c.shard; shards_empty = c.shards_empty; rid = c.rid;
             if (was_idle && rid >= 0) {
                 // a new cast: three 16-byte loads (drt_tri) and one (drt_motion = d, tmax), its extent and edges
                 const TriOverlapVerts t = tri_overlap_load(a.tris, (uint32_t)rid);
@@ -103,19 +76,12 @@ __global__ __launch_bounds__(kRqThreads, kTriCastWavesPerSimd) void tri_cast_ker
                 }
             }
         }
-        if (shards_empty >= kRqShards && __ballot(rid >= 0) == 0) break;
+        if (claim_drained(shards_empty, rid)) break;
 
         // ---- one traversal step per busy lane ----
         if (rid >= 0 && sp > 0) {
-            --sp;
-            uint32_t ref;
             float enter;
-            if (sp < (uint32_t)K) {
-                ref = s_ref[sp][tid]; enter = s_enter[sp][tid];
-            } else {
-                const uint2 e = reinterpret_cast<const uint2 *>(a.stack_hbm)[(size_t)(sp - K) * gthreads + gthread];
-                ref = e.x; enter = __uint_as_float(e.y);
-            }
+            const uint32_t ref = stack_pop(s_ref, s_enter, st, sp, enter);
             if (enter <= best) {
                 if (ref & kLeafBit) {
                     const LeafRange leaf = sc.leaves[ref & ~kLeafBit];
@@ -136,24 +102,7 @@ __global__ __launch_bounds__(kRqThreads, kTriCastWavesPerSimd) void tri_cast_ker
                     float en1, en2;
                     const bool push1 = tri_cast_slab(c.min1, c.max1, ext_lo, ext_hi, q.q0, inv_d, best, en1);
                     const bool push2 = tri_cast_slab(c.min2, c.max2, ext_lo, ext_hi, q.q0, inv_d, best, en2);
-                    const bool far1 = en1 > en2;                                                      // farther child first
-                    const uint32_t ra = far1 ? c.ref1 : c.ref2, rb = far1 ? c.ref2 : c.ref1;
-                    const float da = far1 ? en1 : en2, db = far1 ? en2 : en1;
-                    const bool pa = far1 ? push1 : push2, pb = far1 ? push2 : push1;
-#pragma unroll
-                    for (int k = 0; k < 2; k++) {
-                        const bool push = k == 0 ? pa : pb;
-                        if (push && sp < levels) {
-                            const uint32_t r = k == 0 ? ra : rb;
-                            const float e = k == 0 ? da : db;
-                            if (sp < (uint32_t)K) {
-                                s_ref[sp][tid] = r; s_enter[sp][tid] = e;
-                            } else {
-                                reinterpret_cast<uint2 *>(a.stack_hbm)[(size_t)(sp - K) * gthreads + gthread] = make_uint2(r, __float_as_uint(e));
-                            }
-                            ++sp;
-                        }
-                    }
+                    push_far_first(s_ref, s_enter, st, sp, c.ref1, en1, push1, c.ref2, en2, push2);        // farther child first
                 }
             }
         }
@@ -189,11 +138,8 @@ __global__ __launch_bounds__(kRqThreads, kTriCastWavesPerSimd) void tri_cast_ker
 }  // namespace
 
 hipError_t launch_tri_cast(const SceneView &sc, bool any_mode, const TriCastArgs &args, int num_cus, hipStream_t stream) {
-    if (args.n == 0) return hipSuccess;
-    const uint32_t want = (args.n + kRqThreads - 1) / kRqThreads;
-    // kTriCastWavesPerSimd workgroups per CU (4 waves each, one per SIMD): never more than ray_query_max_blocks, whose HBM stack it uses
-    const uint32_t resident = (uint32_t)std::max(1, num_cus) * (uint32_t)kTriCastWavesPerSimd;
-    const uint32_t blocks = std::min<uint32_t>(want, std::min<uint32_t>(resident, (uint32_t)ray_query_max_blocks(num_cus)));
+    if (args.frame.n == 0) return hipSuccess;
+    const uint32_t blocks = query_blocks(args.frame.n, num_cus, kTriCastWavesPerSimd);
     if (any_mode) hipLaunchKernelGGL(tri_cast_kernel<true>, dim3(blocks), dim3(kRqThreads), 0, stream, sc, args);
     else hipLaunchKernelGGL(tri_cast_kernel<false>, dim3(blocks), dim3(kRqThreads), 0, stream, sc, args);
     return hipGetLastError();

@@ -12,26 +12,20 @@
 //              iff dot(d, d) > beta^2 r2; else an interior node is descended and a leaf adds its triangles in ascending index; one fp32
 //              accumulator in steradians, in visit order; w = accumulator * (1 / (4 pi)) once, at the end
 //
-// Shape of the evaluation: kernel_crossings.hip's point mode.  Persistent grid (8 workgroups of 256 threads per CU), one point per
-// lane, every trip of a wave's loop pops one node or adds one triangle per lane, and when at least `refill_min` lanes are idle the
-// wave claims that many points with ONE atomic on one of kRqShards sharded heads.  Traversal stack: 32-bit node references at [level][thread] -- the bottom
-// kRqLdsLevelsOccluded levels in LDS, the rest in the renderer's HBM array with the same coalesced layout.  A result depends only on
-// its point, the scene and beta: no float atomics, no cross-lane sums.
+// The evaluation's grid, claim and stack: query_frame.hpp.  One point per lane, every trip of a wave's loop pops one node or adds
+// one triangle per lane; stack entries ref, kRqLdsLevelsOccluded levels in LDS.  A result depends only on its point, the scene
+// and beta: no float atomics, no cross-lane sums.
 #include <hip/hip_runtime.h>
 
 #include "device_math.hpp"
 #include "device_scene.hpp"
 #include "device_access.hpp"
 #include "winding.hpp"
+#include "query_frame.hpp"
 
 namespace drt {
 
 namespace {
-
-// rank of this lane among the lanes set in `mask` (v_mbcnt): the claim hands points to idle lanes in lane order
-DRT_DEV int lane_rank(uint64_t mask) {
-    return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
 
 // where a node reference's moment lies: interior nodes at their record index, leaf l at n_inner + l
 DRT_DEV uint32_t moment_index(const SceneView &sc, uint32_t ref) { return (ref & kLeafBit) ? sc.n_inner + (ref & ~kLeafBit) : ref; }
@@ -126,11 +120,11 @@ template <int MODE>
 __global__ __launch_bounds__(kRqThreads, kRqWavesPerSimd) void winding_kernel(const SceneView sc, const WindingArgs a) {
     constexpr int K = kRqLdsLevelsOccluded;
     __shared__ uint32_t s_ref[K][kRqThreads];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const uint32_t gthread = blockIdx.x * kRqThreads + tid, gthreads = gridDim.x * kRqThreads;
-    uint32_t shard = (gthread >> 6) % kRqShards;            // home shard of this wave; on to the next one when it is empty
+    const int tid = threadIdx.x;
+    const uint32_t gthread = blockIdx.x * kRqThreads + tid;
+    const StackLane st = {tid, gthread, gridDim.x * kRqThreads, a.frame.stack_levels, a.frame.stack_hbm};
+    uint32_t shard = home_shard(gthread);
     int shards_empty = 0;
-    const uint32_t levels = a.stack_levels;                  // = tree depth: the stack never holds more entries
 
     int rid = -1;                                            // this lane's point, -1 = idle
     f3 q = mk3(0.f, 0.f, 0.f);
@@ -147,30 +141,10 @@ __global__ __launch_bounds__(kRqThreads, kRqWavesPerSimd) void winding_kernel(co
     for (;;) {
         // ---- refill: claim points for the idle lanes (wave-uniform) ----
         const uint64_t idle = __ballot(rid < 0);
-        const uint32_t n_idle = (uint32_t)__popcll(idle);
-        if (shards_empty < kRqShards && (n_idle >= a.refill_min || n_idle == 64u)) {
-            const int my_rank = lane_rank(idle);
+        if (claim_due(shards_empty, idle, a.frame)) {
             const bool was_idle = rid < 0;
-            uint32_t filled = 0;
-            while (filled < n_idle && shards_empty < kRqShards) {
-                const uint32_t want = n_idle - filled;
-                const uint32_t s_begin = (uint32_t)((uint64_t)a.n * shard / kRqShards);
-                const uint32_t len = (uint32_t)((uint64_t)a.n * (shard + 1) / kRqShards) - s_begin;
-                // lane 0 claims and clips the claim to the shard; start / got go to the wave (64-bit signed arithmetic: the
-                // shard's remainder len - b is negative once other waves have emptied it)
-                int64_t start = 0, got = 0;
-                if (lane == 0) {
-                    const int64_t b = (int64_t)atomicAdd(a.heads + shard * kRqShardStride, want);
-                    const int64_t left = (int64_t)len - b;
-                    if (left > 0) { start = (int64_t)s_begin + b; got = left < (int64_t)want ? left : (int64_t)want; }
-                }
-                start = __shfl(start, 0);
-                got = __shfl(got, 0);
-                if (got <= 0) { shard = (shard + 1) % kRqShards; shards_empty++; continue; }
-                const int64_t k = (int64_t)my_rank - (int64_t)filled;
-                if (was_idle && k >= 0 && k < got && start + k < (int64_t)a.n) rid = (int)(start + k);
-                filled += (uint32_t)got;
-            }
+            const Claimed c = claim_take(shard, shards_empty, rid, idle, a.frame);
+            shard = c.shard; shards_empty = c.shards_empty; rid = c.rid;
             if (was_idle && rid >= 0) {
                 // a new point: one 16-byte load (drt_point = p, max_dist; max_dist is not used)
                 const float4 p4 = reinterpret_cast<const float4 *>(a.points)[(uint32_t)rid];
@@ -183,7 +157,7 @@ __global__ __launch_bounds__(kRqThreads, kRqWavesPerSimd) void winding_kernel(co
                 } else if (sc.root_ref != kNoNode) { s_ref[0][tid] = sc.root_ref; sp = 1; }
             }
         }
-        if (shards_empty >= kRqShards && __ballot(rid >= 0) == 0) break;
+        if (claim_drained(shards_empty, rid)) break;
 
         // ---- one step per busy lane: the next triangle of the leaf under way, or the next node -- replaced by its dipole, descended,
         // or, a leaf, opened.  A leaf's triangles are steps of their own so that one lane's leaf does not hold the wave for its whole
@@ -193,8 +167,7 @@ __global__ __launch_bounds__(kRqThreads, kRqWavesPerSimd) void winding_kernel(co
             acc = acc + wn_solid_angle(q, t.v0, t.e1, t.e2);
             ++tri;
         } else if (rid >= 0 && sp > 0) {
-            --sp;
-            const uint32_t ref = sp < (uint32_t)K ? s_ref[sp][tid] : a.stack_hbm[(size_t)(sp - K) * gthreads + gthread];
+            const uint32_t ref = stack_pop(s_ref, st, sp);
             const float4 *m = reinterpret_cast<const float4 *>(a.moments + moment_index(sc, ref));
             const float4 m0 = m[0], m1 = m[1];
             // what the node is, read next to its moment and not after the test: a leaf's range or an interior node's two references
@@ -210,15 +183,8 @@ __global__ __launch_bounds__(kRqThreads, kRqWavesPerSimd) void winding_kernel(co
                 tri = (int)what.x; tri_end = tri + (int)what.y;      // LeafRange {start, count}: ascending index, from the next trip on
             } else {
                 const uint2 kids = what;
-#pragma unroll
-                for (int k = 0; k < 2; k++) {                         // child 2 first, so that child 1 is the next one popped
-                    if (sp < levels) {
-                        const uint32_t r = k == 0 ? kids.y : kids.x;
-                        if (sp < (uint32_t)K) s_ref[sp][tid] = r;
-                        else a.stack_hbm[(size_t)(sp - K) * gthreads + gthread] = r;
-                        ++sp;
-                    }
-                }
+                stack_push(s_ref, st, sp, kids.y, true);                        // child 2 first, so that child 1 is the next one popped
+                stack_push(s_ref, st, sp, kids.x, true);
             }
         }
 
@@ -255,9 +221,8 @@ hipError_t launch_winding_moments(const SceneView &sc, const WindingMomentArgs &
 }
 
 hipError_t launch_winding(const SceneView &sc, WindingOut kind, const WindingArgs &args, int num_cus, hipStream_t stream) {
-    if (args.n == 0) return hipSuccess;
-    const uint32_t want = (args.n + kRqThreads - 1) / kRqThreads;
-    const uint32_t blocks = std::min<uint32_t>(want, (uint32_t)ray_query_max_blocks(num_cus));
+    if (args.frame.n == 0) return hipSuccess;
+    const uint32_t blocks = query_blocks(args.frame.n, num_cus);
     if (kind == WindingOut::number) hipLaunchKernelGGL(winding_kernel<0>, dim3(blocks), dim3(kRqThreads), 0, stream, sc, args);
     else if (kind == WindingOut::inside) hipLaunchKernelGGL(winding_kernel<1>, dim3(blocks), dim3(kRqThreads), 0, stream, sc, args);
     else hipLaunchKernelGGL(winding_kernel<2>, dim3(blocks), dim3(kRqThreads), 0, stream, sc, args);

@@ -18,11 +18,7 @@ struct ListHitsArgs {
     void *hits;                  // drt_hit[hits_capacity] (16 B, 16-B aligned); may be null when hits_capacity == 0
     uint32_t *counts;            // n words or null: every listed triangle of the ray, stored or not
     uint32_t hits_capacity;
-    uint32_t n;                  // < 2^31
-    uint32_t stack_levels;       // tree depth (<= 64): the stack never holds more entries
-    uint32_t refill_min;         // a wave claims new rays once this many of its lanes are idle (1..64)
-    unsigned int *heads;         // kRqHeadWords zeroed words
-    uint32_t *stack_hbm;         // levels beyond the LDS ones: [(level - K) * grid threads + thread], 4 B entries
+    QueryFrame frame;            // n, tree depth, refill threshold, claim heads, HBM stack: 4 B stack entries
 };
 
 hipError_t launch_list_hits(const SceneView &scene, const ListHitsArgs &args, int num_cus, hipStream_t stream);

@@ -23,11 +23,7 @@ struct NearListArgs {
     void *surf;                  // drt_near_surf[near_capacity] (16 B, 16-B aligned) or null
     uint32_t *counts;            // n words or null: GATHER every listed triangle of the point, K the stored ones
     uint32_t near_capacity;
-    uint32_t n;                  // < 2^31
-    uint32_t stack_levels;       // tree depth (<= 64): the stack never holds more entries
-    uint32_t refill_min;         // a wave claims new points once this many of its lanes are idle (1..64)
-    unsigned int *heads;         // kRqHeadWords zeroed words
-    uint32_t *stack_hbm;         // levels beyond the LDS ones: [(level - K) * grid threads + thread], 8 B entries
+    QueryFrame frame;            // n, tree depth, refill threshold, claim heads, HBM stack: 8 B stack entries
 };
 
 // k_mode: DRT_NEAR_K (the search bound shrinks to the tail of a full list) or DRT_NEAR_GATHER (it never does)

@@ -15,11 +15,7 @@ namespace drt {
 struct NearestArgs {
     const void *points;          // drt_point[n] (16 B, 16-B aligned)
     void *out;                   // drt_nearest[n] (32 B, 16-B aligned)
-    uint32_t n;                  // < 2^31
-    uint32_t stack_levels;       // tree depth (<= 64): the stack never holds more entries
-    uint32_t refill_min;         // a wave claims new points once this many of its lanes are idle (1..64)
-    unsigned int *heads;         // kRqHeadWords zeroed words
-    uint32_t *stack_hbm;         // levels beyond the LDS ones: [(level - K) * grid threads + thread], 8 B entries
+    QueryFrame frame;            // n, tree depth, refill threshold, claim heads, HBM stack: 8 B stack entries
 };
 
 hipError_t launch_nearest(const SceneView &scene, const NearestArgs &args, int num_cus, hipStream_t stream);

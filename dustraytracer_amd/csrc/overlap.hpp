@@ -22,11 +22,7 @@ struct OverlapArgs {
     int32_t *prims;              // int32[prims_capacity]; null when prims_capacity == 0
     uint32_t *counts;            // n words or null: LIST every listed triangle of the box, ANY 0 or 1
     uint32_t prims_capacity;
-    uint32_t n;                  // < 2^31
-    uint32_t stack_levels;       // tree depth (<= 64): the stack never holds more entries
-    uint32_t refill_min;         // a wave claims new boxes once this many of its lanes are idle (1..64)
-    unsigned int *heads;         // kRqHeadWords zeroed words
-    uint32_t *stack_hbm;         // levels beyond the LDS ones: [(level - K) * grid threads + thread], 4 B entries
+    QueryFrame frame;            // n, tree depth, refill threshold, claim heads, HBM stack: 4 B stack entries
 };
 
 // any_mode: DRT_OVERLAP_ANY (the traversal ends at the first listed triangle) or DRT_OVERLAP_LIST

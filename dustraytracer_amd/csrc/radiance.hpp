@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "device_scene.hpp"
+#include "ray_query.hpp"
 
 namespace drt {
 
@@ -27,12 +28,8 @@ hipError_t launch_camera_rays(const CameraRaysArgs &args, hipStream_t stream);
 struct RadianceArgs {
     const void *rays;            // drt_path_ray[n] (32 B, 16-B aligned)
     float4 *out;                 // float4[n]
-    uint32_t n;                  // < 2^31
-    uint32_t stack_levels;       // tree depth (<= 64)
-    uint32_t refill_min;         // a wave claims new paths once this many of its lanes are idle (1..64)
+    QueryFrame frame;            // n, tree depth, refill threshold, claim heads, HBM stack: the closest-hit ray query's 8 B stack entries
     int32_t accumulate;          // 0: out = (c, 1); else out.rgb += c, alpha kept
-    unsigned int *heads;         // kRqHeadWords zeroed words (the ray query's claim heads)
-    uint32_t *stack_hbm;         // levels beyond the LDS ones, laid out as the closest-hit ray query's (ray_query_stack_bytes)
 };
 // The path loop of RayGen for every ray, with the renderer's settings and material model in `frame` (FrameParams: sun, sky,
 // bounce limit, tone curve, gamma, ext_*; its camera and framebuffer fields are not read).  `alpha`: the scene has an RGBA

@@ -19,14 +19,20 @@ constexpr int kRqShardStride = 32;
 constexpr int kRqHeadWords = kRqShards * kRqShardStride;
 constexpr int kRqMaxLevels = 64;                // the reference's stack (BVHTraversal.cuh:17)
 
+// the five fields every batched query's *Args carries (query_frame.hpp: the claim and the stack that read them).  It is defined
+// here, with the constants, because RayQueryArgs below embeds it and query_frame.hpp includes this header.
+struct QueryFrame {
+    uint32_t n;                  // queries, < 2^31
+    uint32_t stack_levels;       // tree depth (<= 64): the stack never holds more entries
+    uint32_t refill_min;         // a wave claims new queries once this many of its lanes are idle (1..64)
+    unsigned int *heads;         // kRqHeadWords zeroed words
+    uint32_t *stack_hbm;         // levels beyond the LDS ones: [(level - K) * grid threads + thread], 8 B {ref, key} / 4 B ref entries
+};
+
 struct RayQueryArgs {
     const void *rays;            // drt_ray[n] (32 B, 16-B aligned)
     void *out;                   // drt_hit[n] (closest) or uint8_t[n] (occluded)
-    uint32_t n;                  // < 2^31
-    uint32_t stack_levels;       // tree depth (<= 64): the stack never holds more entries
-    uint32_t refill_min;         // a wave claims new rays once this many of its lanes are idle (1..64)
-    unsigned int *heads;         // kRqHeadWords zeroed words
-    uint32_t *stack_hbm;         // levels beyond the LDS ones: [(level - K) * grid threads + thread], 8 B (closest) / 4 B entries
+    QueryFrame frame;            // stack entries: 8 B (closest) / 4 B (occluded)
 };
 
 inline int ray_query_max_blocks(int num_cus) { return std::max(1, num_cus) * (kRqWavesPerSimd * 4 * 64 / kRqThreads); }

@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -333,6 +334,24 @@ bool on_renderer_device(const drt_renderer *r, const void *p);
 int query_order(drt_renderer *r, hipStream_t s);
 int query_recorded(drt_renderer *r, hipStream_t s);
 int traversal_scratch(drt_renderer *r, hipStream_t s, bool occluded, bool heads);
+// The opening every batched query's entry point shares (query_frame.hpp kernels), in the order the checks are documented in.
+//   query_open   n < 2^31, no batch pending, the device, every operand that is not null on it, the scene uploaded, the stream chosen
+//                and ordered behind the last query, the scratch for a stack of 4-byte (`occluded`) or 8-byte entries, the heads zeroed.
+//                noun: "at most 2^31 - 1 <noun> per call"; names: "<names> must be device memory on the renderer's device".
+//                An entry point with checks of its own before it (modes, capacities) makes those and calls this.
+//   query_begin  for an entry point whose operands are all required: the handles, n == 0, the pointers, their alignment, then
+//                query_open.  True: go on, on stream *s.  False: the call is over and returns *rc -- DRT_OK for n == 0, else the
+//                error.  Use: `hipStream_t s; int rc; if (!query_begin(..., &s, &rc)) return rc;`
+int query_open(drt_renderer *r, const drt_scene *scene, uint32_t n, std::initializer_list<const void *> operands, const char *noun,
+               const char *names, void *hip_stream, bool occluded, hipStream_t *s);
+struct QueryOperand { const void *p; size_t align; };
+struct QueryWords { const char *null_msg, *align_msg, *noun, *names; };
+bool query_begin(drt_renderer *r, const drt_scene *scene, uint32_t n, std::initializer_list<QueryOperand> ops, const QueryWords &w,
+                 void *hip_stream, bool occluded, hipStream_t *s, int *rc);
+// the levels a traversal stack is sized for: the uploaded tree's depth
+uint32_t query_stack_levels(const drt_renderer *r);
+// the frame of a launch over n queries, after query_open / traversal_scratch: tree depth, refill threshold, heads, HBM stack
+QueryFrame query_frame(const drt_renderer *r, uint32_t n);
 // The uploaded scene's edge adjacency in d_adj (drt_capi_adjacency.cpp), made by the first call after an upload on stream `s`, which
 // the caller has ordered with the query in flight: by kernel_adjacency.hip from the host scene's positions, or by the host's sort
 int scene_adjacency(drt_renderer *r, const drt_scene *scene, hipStream_t s);

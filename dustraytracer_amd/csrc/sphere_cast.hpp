@@ -17,11 +17,7 @@ struct SphereCastArgs {
     const void *rays;            // drt_ray[n] (32 B, 16-B aligned)
     const float *radii;          // float[n]
     void *out;                   // drt_sweep_hit[n] (32 B, 16-B aligned)
-    uint32_t n;                  // < 2^31
-    uint32_t stack_levels;       // tree depth (<= 64): the stack never holds more entries
-    uint32_t refill_min;         // a wave claims new casts once this many of its lanes are idle (1..64)
-    unsigned int *heads;         // kRqHeadWords zeroed words
-    uint32_t *stack_hbm;         // levels beyond the LDS ones: [(level - K) * grid threads + thread], 8 B entries
+    QueryFrame frame;            // n, tree depth, refill threshold, claim heads, HBM stack: 8 B stack entries
 };
 
 hipError_t launch_sphere_cast(const SceneView &scene, const SphereCastArgs &args, int num_cus, hipStream_t stream);

@@ -23,11 +23,7 @@ struct TriCastArgs {
     const void *tris;            // drt_tri[n] (48 B, 16-B aligned)
     const void *motions;         // drt_motion[n] = {d[3], tmax} (16 B, 16-B aligned)
     void *out;                   // drt_tri_hit[n] (48 B, 16-B aligned)
-    uint32_t n;                  // < 2^31
-    uint32_t stack_levels;       // tree depth (<= 64): the stack never holds more entries
-    uint32_t refill_min;         // a wave claims new casts once this many of its lanes are idle (1..64)
-    unsigned int *heads;         // kRqHeadWords zeroed words
-    uint32_t *stack_hbm;         // levels beyond the LDS ones: [(level - K) * grid threads + thread], 8 B entries
+    QueryFrame frame;            // n, tree depth, refill threshold, claim heads, HBM stack: 8 B stack entries
 };
 
 // A lane keeps the query's 15 floats, the motion's 6 (d, inv_d) and the 6 of its extent for as long as it owns the cast; with the pair

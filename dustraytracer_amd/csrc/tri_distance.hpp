@@ -24,11 +24,7 @@ struct TriDistanceArgs {
     const void *tris;            // drt_tri[n] (48 B, 16-B aligned)
     const float *max_dist;       // n floats or null (= infinite)
     void *out;                   // drt_tri_near[n] (48 B, 16-B aligned)
-    uint32_t n;                  // < 2^31
-    uint32_t stack_levels;       // tree depth (<= 64): the stack never holds more entries
-    uint32_t refill_min;         // a wave claims new queries once this many of its lanes are idle (1..64)
-    unsigned int *heads;         // kRqHeadWords zeroed words
-    uint32_t *stack_hbm;         // levels beyond the LDS ones: [(level - K) * grid threads + thread], 8 B entries
+    QueryFrame frame;            // n, tree depth, refill threshold, claim heads, HBM stack: 8 B stack entries
 };
 
 // The pair test keeps the query's 21 floats and two triangles' worth of edges and offsets live: 107 VGPRs, which do not fit the 96 of

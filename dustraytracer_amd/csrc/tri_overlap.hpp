@@ -22,11 +22,7 @@ struct TriOverlapArgs {
     int32_t *prims;              // int32[prims_capacity]; null when prims_capacity == 0
     uint32_t *counts;            // n words or null: LIST every listed triangle of the query, ANY 0 or 1
     uint32_t prims_capacity;
-    uint32_t n;                  // < 2^31
-    uint32_t stack_levels;       // tree depth (<= 64): the stack never holds more entries
-    uint32_t refill_min;         // a wave claims new queries once this many of its lanes are idle (1..64)
-    unsigned int *heads;         // kRqHeadWords zeroed words
-    uint32_t *stack_hbm;         // levels beyond the LDS ones: [(level - K) * grid threads + thread], 4 B entries
+    QueryFrame frame;            // n, tree depth, refill threshold, claim heads, HBM stack: 4 B stack entries
 };
 
 // The triangle test needs more than the 64 VGPRs of kRqWavesPerSimd waves per SIMD (kernel_tri_overlap.hip): the kernel is bounded to

@@ -49,14 +49,10 @@ hipError_t launch_winding_moments(const SceneView &scene, const WindingMomentArg
 struct WindingArgs {
     const void *points;          // drt_point[n] (16 B, 16-B aligned); max_dist is not read
     void *out;                   // what `kind` says
-    uint32_t n;                  // < 2^31
-    uint32_t stack_levels;       // tree depth (<= 64): the stack never holds more entries
-    uint32_t refill_min;         // a wave claims new points once this many of its lanes are idle (1..64)
+    QueryFrame frame;            // n, tree depth, refill threshold, claim heads, HBM stack: 4 B stack entries
     float beta2;                 // beta * beta in fp32 (+inf: never approximate)
     float threshold;
     const WindingMoment *moments;
-    unsigned int *heads;         // kRqHeadWords zeroed words
-    uint32_t *stack_hbm;         // levels beyond the LDS ones: [(level - K) * grid threads + thread], 4 B entries
 };
 
 hipError_t launch_winding(const SceneView &scene, WindingOut kind, const WindingArgs &args, int num_cus, hipStream_t stream);
